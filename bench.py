@@ -16,6 +16,9 @@ Prints ONE JSON line on rank 0 (schema in the task contract) with two extra obje
                   stream; algorithmic bytes per DESIGN.md: B*T'*C*(4 reads + 1 write)*elem per direction.
   cpu_baseline -- the CPU oracle (reference graph in torch CPU fp32 ops + oracle/wkv6_oracle.c) on a bounded sample
                   of the same features, on this box's host cores (rank 0, N == 1 only).
+
+--dump-outputs DIR writes what the last timed step computed as .npy files (sample_outputs); the inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -231,6 +234,47 @@ def token_checksum(token_lists) -> str:
             toks = getattr(r, "tokens", r)
             h.update((",".join(str(int(t)) for t in toks) + ";").encode())
     return h.hexdigest()[:16]
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: bytes of all dumped .npy files together
+
+
+def sample_outputs(logp: torch.Tensor, out_lens, token_lists) -> dict:
+    """--dump-outputs: what the timed path handed its caller in one step (greedy_decode_batches: the CTC log-probabilities of
+    the last decode batch, and with c2 the greedy token lists of every batch), as host arrays by file name (float32; row
+    indices float64).  Called before any later step can reuse the buffers.
+    ctc_log_probs holds the valid frames of the batch only (utterance b contributes its first out_lens[b] frames; the padded
+    ones past its length carry no result), utterance after utterance, with ctc_log_probs_lengths = out_lens.  It is kept whole
+    when it fits into DUMP_BYTES beside the rest, else as the rows of a fixed seeded sample listed in ctc_log_probs_rows.
+    c2 adds tokens (every utterance's token ids, batch by batch, in issue order) and token_counts (tokens per utterance)."""
+    arrays = {}
+    if token_lists:
+        toks = [[int(t) for t in getattr(r, "tokens", r)] for batch in token_lists for r in batch]
+        arrays["tokens"] = torch.tensor([t for u in toks for t in u], dtype=torch.float32).numpy()
+        arrays["token_counts"] = torch.tensor([len(u) for u in toks], dtype=torch.float32).numpy()
+    out_lens = [int(n) for n in out_lens]
+    assert len(out_lens) == logp.shape[0] and max(out_lens) <= logp.shape[1], (out_lens, tuple(logp.shape))
+    arrays["ctc_log_probs_lengths"] = torch.tensor(out_lens, dtype=torch.float32).numpy()
+    flat = torch.cat([logp[b, :n] for b, n in enumerate(out_lens)])
+    budget = DUMP_BYTES - sum(a.nbytes for a in arrays.values()) - 4 * 128      # .npy headers
+    if flat.numel() * 4 <= budget:
+        arrays["ctc_log_probs"] = flat.float().cpu().numpy()
+    else:
+        n = budget // (4 * flat.shape[1] + 8)       # a float32 row and its float64 index
+        g = torch.Generator(device="cpu").manual_seed(0)
+        rows = torch.randperm(flat.shape[0], generator=g)[:n].sort().values
+        arrays["ctc_log_probs"] = flat[rows.to(flat.device)].float().cpu().numpy()
+        arrays["ctc_log_probs_rows"] = rows.to(torch.float64).numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    return arrays
+
+
+def write_outputs(path: str, arrays: dict) -> dict:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def timed_passes(step, passes: int, warmup: int = 1):
@@ -551,7 +595,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the fp32-model / bf16-slot timing reported under 'extra'")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB: "
+                         "the CTC log-probabilities (a fixed seeded sample of frames when larger) and, with c2, the greedy tokens. "
+                         "The inputs depend on the arguments alone, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     one_gpu = os.environ.get("PAFC_BENCH_ONE_GPU") == "1"   # rehearsal of the N > 1 code path on a single-GPU box
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -634,12 +684,19 @@ def main():
         barrier()
         stage("warm-up done; timed steps")
         torch.cuda.reset_peak_memory_stats(device)
+        logp = None
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            logp = step()
         barrier()
         elapsed = time.perf_counter() - t0
         max_vram_mb = torch.cuda.max_memory_allocated(device) / 1024 / 1024    # encoder-rtf.py:544 (MB, this rank)
+        dumped = None
+        if args.dump_outputs and rank == 0:   # before the next step can overwrite the last timed step's buffers
+            # logp is of the last batch issued (greedy_decode_batches): valid output frames per utterance of that batch
+            out_lens = [model.encoder.embed.subsampled_length(int(n)) for n in batches[-1][1].tolist()]
+            dumped = write_outputs(args.dump_outputs, sample_outputs(logp, out_lens, last_tokens))
+        del logp
         # per-kernel event timers (roofline / mfma objects) run on extra steps OUTSIDE the timed region: recording events
         # on the hot stream costs a few microseconds per timed op, which the headline number should not carry
         profiling.enable(True)
@@ -720,6 +777,8 @@ def main():
     # paper's window shape in the HEADLINE precision on the package's defaults (no knob is set anywhere in this file), the
     # streaming legs (configs[2]; a uni-directional whole-bf16 model, which the reference's uni wrapper does run:
     # rwkv_wrapper.py:57-83 returns the query dtype), and the other precision mode's one-sequence figure
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     out["extra"] = None
     failed_legs = []
     if rank == 0 and world == 1 and args.workload == "c3" and args.chunk_size <= 0 and not args.no_extra:

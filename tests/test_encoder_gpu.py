@@ -777,7 +777,7 @@ def test_bf16slot_token_lists_through_a_head_that_decides(hip):
     top-2 margin exceeds 2 e_t.  Asserted: (i) every utterance all of whose frames are decided yields the oracle's token list
     (collapsed, blanks removed); (ii) at most 0.5 % of the frames flip and >= 90 % of ALL utterances yield the oracle's list (a
     flip at a sign change moves the change by a frame, which the collapse absorbs -- lists differ only where the projection
-    grazes zero).  The oracle runs on 16 host threads whatever the box has.  Recorded in profiles/parity_r06.json."""
+    grazes zero).  The oracle runs on 16 host threads whatever the box has.  Recorded by tests/parity_log.py (parity_r06.json)."""
     import itertools
     import bench
     from paper_accurate_fast_cheap_amd.transformer.ctc import CTC
@@ -1390,7 +1390,8 @@ def test_refused_capture_is_never_silent_in_a_child_process(hip):
     hipErrorStreamCaptureInvalidated, whatever is done to the stream -- found in round 5 the hard way, re-measured in round 6 with
     hipStreamEndCapture + hipGetLastError by hand.  What is asserted is what a caller can rely on: EITHER the call returns the
     eager result and the shape is marked "eager" (a runtime that recovers), OR the error that comes back names the capture
-    (this runtime) -- never a wrong result, never a hang.  Which of the two happened is recorded in profiles/parity_r06.json."""
+    (this runtime) -- never a wrong result, never a hang.  Which of the two happened is recorded by tests/parity_log.py
+    (parity_r06.json)."""
     import os
     import subprocess
     import sys
