@@ -331,6 +331,38 @@ int pafc_ctc_loss_backward(int dtype, int B, int T, int V, const void *logits, l
                            float scale, void *dlogits, long ldg, const void *workspace, size_t workspace_bytes,
                            pafc_stream_t stream);
 
+/* ---- RNN-T joint + loss of the training step, without the (rows, V) logits (csrc/rnnt_loss.hip) -------------------------------
+ * TransducerJoint.forward_optimized (wenet/transducer/joint.py:111-149) for the paper's joint (pre-join projections already
+ * applied, additive join, tanh, no post-join projection) + the transducer loss of Transducer._compute_loss
+ * (wenet/transducer/transducer.py:506-561), and their autograd.  The joint's output is never formed.
+ *   E (B, T, J) bf16 = enc_ffn(encoder_out), frames lde apart, utterances strideE apart; P (B, Up1, J) bf16 = pred_ffn(predictor_out)
+ *   over the blank-prepended targets, rows ldp apart, utterances strideP apart; W (V, J) bf16 contiguous; bias (V) bf16 or NULL;
+ *   hlens / ylens (B) int32 on the device (1 <= hlens[n] <= T, 0 <= ylens[n] < Up1, ylens[n] <= ldy); ys (B, ldy) int64 targets;
+ *   R = sum_n hlens[n] (ylens[n] + 1), known to the host (it sizes the workspace).
+ * Lattice row r = (n, t, u) = off_n + t (ylens[n] + 1) + u (forward_optimized's order).  Rounding points: h_r = bf16(tanh(E[n][t] +
+ * P[n][u])) with the add and tanh in fp32; z_r = W h_r + b accumulated in fp32 and never rounded; log-softmax statistics, lattice
+ * (alpha, beta, "log 0" = -1e30) and per-node gradients in fp32; dz = d loss / d z rounded once to bf16 for the two backward
+ * products; dH = dz W in fp32.  No float atomics: results are bitwise reproducible.  J % 64 == 0, V % 8 == 0, Up1 <= 2559
+ * (lattice LDS), else PAFC_ERR_UNSUPPORTED; E, P, W 16-byte aligned, strides multiples of 8, workspace / scratch 256-byte aligned.
+ * workspace_bytes(backward = 0): the forward's workspace, which holds what backward reads (unmodified in between).
+ * workspace_bytes(backward = 1): backward's scratch for slabs of at most slab_rows rows (whole utterances, grouped in order by
+ *   row_off, a host array of B + 1 row offsets: row_off[0] = 0, row_off[B] = R); 0 if one utterance alone exceeds slab_rows.
+ * forward:  nll[n] = -log p(y_n | x_n) (fp32), NaN for an utterance whose lengths do not fit the operands or R.
+ * backward: with s_n = grad_out[n] * scale (grad_out: B floats on the device), d(sum_n s_n nll[n]) with respect to E, P (dE (B, T,
+ *   J), dP (B, Up1, J) contiguous, grad_dtype PAFC_BF16 or PAFC_F32; rows beyond the lengths are zero), W (dW (V, J) fp32) and the
+ *   bias (db (V) fp32, or NULL).  dW / db are summed over the slabs in fp32 in slab order. */
+size_t pafc_rnnt_joint_loss_workspace_bytes(int B, int J, int V, long R, long slab_rows, const int64_t *row_off, int backward);
+int pafc_rnnt_joint_loss_forward(int B, int T, int Up1, int J, int V, const void *E, long lde, long strideE, const void *P, long ldp,
+                                 long strideP, const void *W, const void *bias, const int32_t *hlens, const int32_t *ylens,
+                                 const int64_t *ys, int ldy, int blank, long R, float *nll, void *workspace, size_t workspace_bytes,
+                                 pafc_stream_t stream);
+int pafc_rnnt_joint_loss_backward(int B, int T, int Up1, int J, int V, const void *E, long lde, long strideE, const void *P, long ldp,
+                                  long strideP, const void *W, const void *bias, const int32_t *hlens, const int32_t *ylens,
+                                  const int64_t *ys, int ldy, int blank, long R, const int64_t *row_off, long slab_rows,
+                                  const float *grad_out, float scale, int grad_dtype, void *dE, void *dP, float *dW, float *db,
+                                  const void *workspace, size_t workspace_bytes, void *scratch, size_t scratch_bytes,
+                                  pafc_stream_t stream);
+
 /* ---- fp32 GEMM with a fused epilogue on the fp32 matrix cores (csrc/gemm_f32.hip) --------------------------------------
  * out (M, N) = act(alpha * A (M, K) . W (N, K)^T + bias (N) + residual (M, N)), batch entries strideX elements apart (0 = shared;
  * bias may be null, residual may be null or alias out).  Exact fp32 products with fp32 accumulation: the arithmetic of the

@@ -1122,6 +1122,131 @@ def ctc_head_loss(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return _CtcHeadLoss.apply(x, weight, bias, hlens, ys, ylens, blank)
 
 
+RNNT_SLAB_BYTES = 1 << 30     # backward's dz (rows, Vp) bf16 + dH (rows, J) fp32 slab: ~85 000 lattice rows at V = 5000, J = 640
+
+
+class _RnntJointLoss(torch.autograd.Function):
+    """RNN-T joint + loss of the training step on hand-written kernels only (csrc/rnnt_loss.hip, include/pafc_encoder_ops.h):
+    h = tanh(E[n, t] + P[n, u]) written once as bf16 (R, J), the logits' row statistics from the epilogue of H W^T + b (the
+    (R, V) logits are never stored), the lattice per utterance, and backwards dz in slabs of whole utterances, dH = dz W,
+    dW / db = dz^T H and the tanh derivative reduced into dE / dP.  One host read of the lengths per call plans the row
+    offsets and the slabs (forward_optimized + transducer_loss make 2 B + 2)."""
+
+    @staticmethod
+    def forward(ctx, E, P, weight, bias, hlens, ys, ylens, blank):
+        B, T, J = E.shape
+        Up1 = P.shape[1]
+        V = weight.shape[0]
+        Eb = E.detach().to(torch.bfloat16).contiguous()
+        Pb = P.detach().to(torch.bfloat16).contiguous()
+        wb = _bf16_shadow(weight).detach().contiguous()
+        bb = None if bias is None else _bf16_shadow(bias).detach().contiguous()
+        hl = hlens.to(device=E.device, dtype=torch.int32).contiguous()
+        yl = ylens.to(device=E.device, dtype=torch.int32).contiguous()
+        ysc = ys.to(device=E.device, dtype=torch.int64).contiguous()
+        ldy = ysc.shape[1]
+        lens = torch.stack([hl, yl]).cpu()             # the one host synchronisation of the call
+        Ts, Us = lens[0].tolist(), lens[1].tolist()
+        for n, (t, u) in enumerate(zip(Ts, Us)):
+            if not (1 <= t <= T and 0 <= u < Up1 and u <= ldy):
+                raise _lib.PafcError(f"rnnt_joint_loss: utterance {n} has {t} frames / {u} labels, outside E (T = {T}), "
+                                     f"P (U + 1 = {Up1}) or ys ({ldy} columns)")
+        row_off = [0]
+        for t, u in zip(Ts, Us):
+            row_off.append(row_off[-1] + t * (u + 1))
+        R = row_off[-1]
+        Vp = (V + 63) // 64 * 64
+        slab_rows = max(max(t * (u + 1) for t, u in zip(Ts, Us)), min(R, RNNT_SLAB_BYTES // (2 * Vp + 4 * J)))
+        L = _bind_rnnt_loss()
+        nbytes = L.pafc_rnnt_joint_loss_workspace_bytes(B, J, V, R, 0, None, 0)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
+        nll = torch.empty(B, dtype=torch.float32, device=E.device)
+        _lib.check(L.pafc_rnnt_joint_loss_forward(B, T, Up1, J, V, _lib.ptr(Eb), J, T * J, _lib.ptr(Pb), J, Up1 * J, _lib.ptr(wb),
+                                                  _lib.ptr(bb), _lib.ptr(hl), _lib.ptr(yl), _lib.ptr(ysc), ldy, int(blank), R,
+                                                  _lib.ptr(nll), _lib.ptr(ws), nbytes, _lib.stream_of(E)),
+                   "pafc_rnnt_joint_loss_forward")
+        ctx.save_for_backward(Eb, Pb, wb, bb, ws, hl, yl, ysc)
+        ctx.plan = (B, T, Up1, J, V, ldy, int(blank), R, row_off, slab_rows)
+        ctx.dtypes = (E.dtype, P.dtype, weight.dtype, None if bias is None else bias.dtype)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        Eb, Pb, wb, bb, ws, hl, yl, ysc = ctx.saved_tensors
+        B, T, Up1, J, V, ldy, blank, R, row_off, slab_rows = ctx.plan
+        e_dt, p_dt, w_dt, b_dt = ctx.dtypes
+        L = _bind_rnnt_loss()
+        off = (ctypes.c_int64 * (B + 1))(*row_off)
+        sbytes = L.pafc_rnnt_joint_loss_workspace_bytes(B, J, V, R, slab_rows, off, 1)
+        if sbytes == 0:
+            raise _lib.PafcError("pafc_rnnt_joint_loss_workspace_bytes: no backward plan for these lengths")
+        scratch = torch.empty(sbytes, dtype=torch.uint8, device=Eb.device)
+        gdt = torch.bfloat16 if (e_dt == torch.bfloat16 and p_dt == torch.bfloat16) else torch.float32
+        dE = torch.empty((B, T, J), dtype=gdt, device=Eb.device)
+        dP = torch.empty((B, Up1, J), dtype=gdt, device=Eb.device)
+        dW = torch.empty((V, J), dtype=torch.float32, device=Eb.device)
+        db = torch.empty(V, dtype=torch.float32, device=Eb.device) if b_dt is not None else None
+        gf = g.detach().to(torch.float32).contiguous()
+        _lib.check(L.pafc_rnnt_joint_loss_backward(B, T, Up1, J, V, _lib.ptr(Eb), J, T * J, _lib.ptr(Pb), J, Up1 * J, _lib.ptr(wb),
+                                                   _lib.ptr(bb), _lib.ptr(hl), _lib.ptr(yl), _lib.ptr(ysc), ldy, blank, R, off, slab_rows,
+                                                   _lib.ptr(gf), 1.0, _lib.dtype_code(gdt), _lib.ptr(dE), _lib.ptr(dP), _lib.ptr(dW),
+                                                   _lib.ptr(db), _lib.ptr(ws), ws.numel(), _lib.ptr(scratch), sbytes,
+                                                   _lib.stream_of(Eb)), "pafc_rnnt_joint_loss_backward")
+        return (dE.to(e_dt), dP.to(p_dt), dW.to(w_dt), None if db is None else db.to(b_dt), None, None, None, None)
+
+
+def _bind_rnnt_loss():
+    L = _lib.lib()
+    if not getattr(L, "_pafc_rnntloss_bound", False):
+        from ctypes import c_float, c_long, c_size_t
+        P, I, G, Z = c_void_p, c_int, c_long, c_size_t
+        _lib._sig(L.pafc_rnnt_joint_loss_workspace_bytes, Z, I, I, I, G, G, P, I)
+        _lib._sig(L.pafc_rnnt_joint_loss_forward, I, I, I, I, I, I, P, G, G, P, G, G, P, P, P, P, P, I, I, G, P, P, Z, P)
+        _lib._sig(L.pafc_rnnt_joint_loss_backward, I, I, I, I, I, I, P, G, G, P, G, G, P, P, P, P, P, I, I, G, P, G, P, c_float, I, P,
+                  P, P, P, P, Z, P, Z, P)
+        L._pafc_rnntloss_bound = True
+    return L
+
+
+def rnnt_joint_loss_unmet(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: torch.Tensor) -> Optional[str]:
+    """The condition the fused RNN-T joint + loss does not meet for these operands, or None (the same conditions as
+    ctc_head_loss_eligible: the GPU training step under bf16 autocast or with a bf16 model, and dims the kernels take)."""
+    if not enc_proj.is_cuda:
+        return "the operands are not on the GPU"
+    if not torch.is_grad_enabled():
+        return "gradients are disabled"
+    if not train_kernels_enabled():
+        return "PAFC_TRAIN_KERNELS=0"
+    if enc_proj.dim() != 3 or pred_proj.dim() != 3 or enc_proj.shape[0] != pred_proj.shape[0]:
+        return "enc_proj (B, T, J) and pred_proj (B, U + 1, J) are expected"
+    V, J = weight.shape
+    if enc_proj.shape[2] != J or pred_proj.shape[2] != J:
+        return "the joint dimension of enc_proj / pred_proj differs from the output layer's"
+    if J % 64:
+        return f"join_dim {J} is not a multiple of 64"
+    if V % 8:
+        return f"vocab_size {V} is not a multiple of 8"
+    if enc_proj.shape[0] > 65535 or pred_proj.shape[1] > 2559:
+        return "more than 65535 utterances or 2558 labels per utterance"
+    bf16_model = enc_proj.dtype == torch.bfloat16 and pred_proj.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+    autocast_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    if not (bf16_model or autocast_bf16):
+        return "neither bf16 autocast nor a bf16 model"
+    return None
+
+
+def rnnt_joint_loss_eligible(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: torch.Tensor) -> bool:
+    return rnnt_joint_loss_unmet(enc_proj, pred_proj, weight) is None
+
+
+def rnnt_joint_loss(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                    hlens: torch.Tensor, ys: torch.Tensor, ylens: torch.Tensor, blank: int = 0) -> torch.Tensor:
+    """Per-utterance RNN-T nll (B,) fp32 of the joint ffn_out(tanh(enc_proj[:, t] + pred_proj[:, u])) (joint.py:111-149 +
+    the transducer loss of transducer.py:506-561), see _RnntJointLoss.  enc_proj (B, T, J), pred_proj (B, U + 1, J) over the
+    blank-prepended targets, weight (V, J) / bias (V) of ffn_out, ys (B, >= U_n) targets."""
+    return _RnntJointLoss.apply(enc_proj, pred_proj, weight, bias, hlens, ys, ylens, blank)
+
+
 def _bind2():
     L = _bind()
     if getattr(L, "_pafc_glue_bound", False):

@@ -15,6 +15,7 @@ from .loss import transducer_loss
 from .search.prefix_beam_search import PrefixBeamSearch
 
 IGNORE_ID = -1
+FUSED_JOINT = "fused_joint"
 
 
 def add_blank(ys_pad: torch.Tensor, blank: int, ignore_id: int) -> torch.Tensor:
@@ -29,8 +30,11 @@ class Transducer(ASRModel):
     def __init__(self, vocab_size: int, blank: int, encoder: torch.nn.Module, predictor: torch.nn.Module,
                  joint: torch.nn.Module, ctc=None, special_tokens: Optional[dict] = None, attention_decoder=None,
                  ctc_weight: float = 0.0, transducer_weight: float = 1.0, attention_weight: float = 0.0,
-                 **_unused_model_conf):
+                 transducer_type: Optional[str] = None, **_unused_model_conf):
         super().__init__(vocab_size, encoder, ctc, ctc_weight, special_tokens)
+        # model_conf.transducer_type (the reference's key, default "optimized_transducer"): every value but "fused_joint" keeps the
+        # restated path below; "fused_joint" asks for the fused joint + loss kernels (hip_ops.rnnt_joint_loss) and never falls back
+        self.fused_joint = transducer_type == FUSED_JOINT
         self.blank = blank
         self.predictor = predictor
         self.joint = joint
@@ -61,10 +65,38 @@ class Transducer(ASRModel):
         ys_in_pad = add_blank(text, self.blank, IGNORE_ID)
         predictor_out = self.predictor(ys_in_pad)
         rnnt_text = torch.where(text == IGNORE_ID, 0, text.to(torch.int64)).to(torch.int32)
+        if self.fused_joint:
+            return self._fused_joint_loss(encoder_out, encoder_out_lens, predictor_out, rnnt_text, text_lengths)
         joint_out = self.joint.forward_optimized(encoder_out.to(predictor_out.dtype), predictor_out,
                                                  encoder_out_lens.to(torch.int32), text_lengths.to(torch.int32))
         return transducer_loss(joint_out, rnnt_text, encoder_out_lens, text_lengths, self.blank, reduction="mean",
                                from_log_softmax=False)
+
+    def _fused_joint_loss(self, encoder_out, encoder_out_lens, predictor_out, rnnt_text, text_lengths) -> torch.Tensor:
+        """transducer_type "fused_joint": the same "mean" (sum_n nll_n / sum_n T_n) from E = enc_ffn(encoder_out) over the padded
+        (B, T) and P = pred_ffn(predictor_out), without the joint's (rows, V) output (hip_ops.rnnt_joint_loss)."""
+        from .. import hip_ops
+        from .._lib import PafcError
+        j = self.joint
+        unmet = None
+        if not getattr(j, "prejoin_linear", False) or j.enc_ffn is None or j.pred_ffn is None:
+            unmet = "the joint has no pre-join projections (prejoin_linear: false)"
+        elif j.postjoin_linear:
+            unmet = "the joint has a post-join projection (postjoin_linear: true)"
+        elif not isinstance(j.activatoin, torch.nn.Tanh):
+            unmet = "the joint's activation is not tanh"
+        elif getattr(j, "hat_joint", False):
+            unmet = "hat_joint"
+        E = P = None
+        if unmet is None:
+            E = j.enc_ffn(encoder_out.to(predictor_out.dtype))
+            P = j.pred_ffn(predictor_out)
+            unmet = hip_ops.rnnt_joint_loss_unmet(E, P, j.ffn_out.weight)
+        if unmet is not None:
+            raise PafcError(f"transducer_type {FUSED_JOINT!r}: {unmet}")
+        nll = hip_ops.rnnt_joint_loss(E, P, j.ffn_out.weight, j.ffn_out.bias, encoder_out_lens, rnnt_text, text_lengths,
+                                      self.blank)
+        return nll.sum() / encoder_out_lens.sum()
 
     def init_bs(self):
         if self.bs is None:
