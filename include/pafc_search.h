@@ -63,6 +63,43 @@ int pafc_rnnt_beam_step(int B, int T, int beam, int blank_id, int t, const int64
 int pafc_rnnt_beam_finish(int B, int T, int beam, void *workspace, size_t workspace_bytes, int32_t *out_tokens,
                           int32_t *out_len, double *out_score, pafc_stream_t stream);
 
+/* RNN-T greedy search (basic_greedy_search, wenet/transducer/search/greedy_search.py) for B utterances at once, in lockstep:
+ * each pafc_rnnt_greedy_step advances every running utterance by one decision -- the LSTM predictor (only for rows whose
+ * last decision was not blank), projection, pred_ffn, the joint reduced to per-slice softmax statistics, argmax (lowest index
+ * on ties) and the state machine: a non-blank is emitted with its frame and commits the pending LSTM state; a blank, or the
+ * n_steps-th symbol of a frame, moves to the next frame; a blank also keeps the predictor's output for the next decision.
+ * All state lives in `workspace`; a step reads nothing from the host, allocates nothing and copies nothing, so it can be
+ * captured in a graph.  The path score of a row is the sum of log p(decision) over all its decisions (blanks included),
+ * accumulated in float64.
+ * net: the weights, every one of them contiguous in nn.Module layout and of net->dtype (PAFC_F32: exact fp32 products and
+ * fp32 accumulation; PAFC_BF16: bf16 operands, fp32 accumulation, the LSTM state, pred_out, P, E + P and tanh rounded to
+ * bf16).  Dimensions multiples of 4, join_dim <= 2048, embed_rows >= vocab, 16-byte aligned weights; b_ih / b_hh may be
+ * NULL (no bias) and so may proj_b, pred_ffn_b, out_b.  The pointer arrays w_ih .. b_hh are host memory.
+ * E: (B, T, join_dim) of net->dtype, enc_ffn(encoder_out).  lens: (B) int64 device frames per utterance (clamped to [0, T]).
+ * B <= 256, T * n_steps < 2^31.  running (device int32, or NULL): receives the number of rows still running after the step.
+ * pafc_rnnt_greedy_finish writes, for row b, ntok[b] and the first min(ntok[b], ld) tokens and their frame indices into row
+ * b of tokens / frames ((B, ld) int32; frames may be NULL), score[b] (or NULL) and the running count. */
+typedef struct pafc_rnnt_greedy_net {
+    int dtype;
+    int num_layers, embed_dim, hidden, pred_dim, join_dim, vocab, embed_rows;
+    const void *embed;                         /* (embed_rows, embed_dim) */
+    const void *const *w_ih;                   /* num_layers x (4 hidden, embed_dim for layer 0 else hidden): gates i, f, g, o */
+    const void *const *w_hh;                   /* num_layers x (4 hidden, hidden) */
+    const void *const *b_ih, *const *b_hh;     /* num_layers x (4 hidden), or NULL */
+    const void *proj_w, *proj_b;               /* (pred_dim, hidden), (pred_dim) */
+    const void *pred_ffn_w, *pred_ffn_b;       /* (join_dim, pred_dim), (join_dim) */
+    const void *out_w, *out_b;                 /* (vocab, join_dim), (vocab) */
+} pafc_rnnt_greedy_net;
+
+size_t pafc_rnnt_greedy_workspace_bytes(const pafc_rnnt_greedy_net *net, int B, int T, int n_steps);
+int pafc_rnnt_greedy_init(const pafc_rnnt_greedy_net *net, int B, int T, int n_steps, int blank_id, const int64_t *lens,
+                          void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+int pafc_rnnt_greedy_step(const pafc_rnnt_greedy_net *net, int B, int T, int n_steps, int blank_id, const void *E, void *workspace,
+                          size_t workspace_bytes, int32_t *running, pafc_stream_t stream);
+int pafc_rnnt_greedy_finish(const pafc_rnnt_greedy_net *net, int B, int T, int n_steps, const void *workspace, size_t workspace_bytes,
+                            int ld, int32_t *tokens, int32_t *frames, int32_t *ntok, double *score, int32_t *running,
+                            pafc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

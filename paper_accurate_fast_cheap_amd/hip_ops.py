@@ -1247,6 +1247,173 @@ def rnnt_joint_loss(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: tor
     return _RnntJointLoss.apply(enc_proj, pred_proj, weight, bias, hlens, ys, ylens, blank)
 
 
+RNNT_GREEDY_CHUNK = 32     # lockstep steps between two reads of the running-row count, after the first T steps
+
+
+class _GreedyNet(ctypes.Structure):
+    """include/pafc_search.h: pafc_rnnt_greedy_net."""
+    _PP = ctypes.POINTER(c_void_p)
+    _fields_ = [("dtype", c_int), ("num_layers", c_int), ("embed_dim", c_int), ("hidden", c_int), ("pred_dim", c_int),
+                ("join_dim", c_int), ("vocab", c_int), ("embed_rows", c_int), ("embed", c_void_p), ("w_ih", _PP), ("w_hh", _PP),
+                ("b_ih", _PP), ("b_hh", _PP), ("proj_w", c_void_p), ("proj_b", c_void_p), ("pred_ffn_w", c_void_p),
+                ("pred_ffn_b", c_void_p), ("out_w", c_void_p), ("out_b", c_void_p)]
+
+
+def _bind_rnnt_greedy():
+    L = _lib.lib()
+    if not getattr(L, "_pafc_rnntgreedy_bound", False):
+        from ctypes import c_size_t
+        P, I, Z = c_void_p, c_int, c_size_t
+        _lib._sig(L.pafc_rnnt_greedy_workspace_bytes, Z, P, I, I, I)
+        _lib._sig(L.pafc_rnnt_greedy_init, I, P, I, I, I, I, P, P, Z, P)
+        _lib._sig(L.pafc_rnnt_greedy_step, I, P, I, I, I, I, P, P, Z, P, P)
+        _lib._sig(L.pafc_rnnt_greedy_finish, I, P, I, I, I, P, Z, I, P, P, P, P, P, P)
+        L._pafc_rnntgreedy_bound = True
+    return L
+
+
+def _greedy_net(predictor, joint):
+    """The weights as a pafc_rnnt_greedy_net, and the tensors it points into (kept alive by the caller)."""
+    rnn = predictor.rnn
+    nl, H = rnn.num_layers, rnn.hidden_size
+    keep = []
+
+    def p(t):
+        if t is None:
+            return None
+        t = t.detach().contiguous()
+        keep.append(t)
+        return t.data_ptr()
+
+    def arr(name):
+        ptrs = [p(getattr(rnn, f"{name}_l{l}", None)) for l in range(nl)]
+        return None if any(v is None for v in ptrs) else (c_void_p * nl)(*ptrs)
+
+    w_ih, w_hh, b_ih, b_hh = arr("weight_ih"), arr("weight_hh"), arr("bias_ih"), arr("bias_hh")
+    keep += [w_ih, w_hh, b_ih, b_hh]
+    cast = lambda a: ctypes.cast(a, ctypes.POINTER(c_void_p)) if a is not None else None
+    proj, pf, out = predictor.projection, joint.pred_ffn, joint.ffn_out
+    net = _GreedyNet(_lib.dtype_code(out.weight.dtype), nl, predictor.embed.embedding_dim, H, proj.out_features, out.in_features,
+                     out.out_features, predictor.embed.num_embeddings, p(predictor.embed.weight), cast(w_ih), cast(w_hh), cast(b_ih),
+                     cast(b_hh), p(proj.weight), p(proj.bias), p(pf.weight), p(pf.bias), p(out.weight), p(out.bias))
+    return net, keep
+
+
+def rnnt_greedy_unmet(predictor, joint, encoder_out: torch.Tensor, n_steps: int = 64) -> Optional[str]:
+    """The condition the greedy-search kernels (csrc/rnnt_greedy.hip) do not meet for this predictor / joint / encoder output,
+    or None.  The kernels take the paper's modules: an LSTM predictor with its projection, a joint with pre-join projections,
+    tanh and no post-join projection or HAT; every weight fp32 or every weight bf16; eval-mode arithmetic."""
+    rnn = getattr(predictor, "rnn", None)
+    if not isinstance(rnn, torch.nn.LSTM) or getattr(predictor, "embed", None) is None or getattr(predictor, "projection", None) is None:
+        return "the predictor is not an LSTM predictor (embedding, nn.LSTM, projection)"
+    if rnn.bidirectional or rnn.proj_size or not rnn.batch_first:
+        return "the predictor's LSTM is bidirectional, has proj_size or is not batch_first"
+    if not getattr(joint, "prejoin_linear", False) or joint.enc_ffn is None or joint.pred_ffn is None:
+        return "the joint has no pre-join projections (prejoin_linear: false)"
+    if joint.postjoin_linear:
+        return "the joint has a post-join projection (postjoin_linear: true)"
+    if getattr(joint, "hat_joint", False):
+        return "hat_joint"
+    if not isinstance(joint.activatoin, torch.nn.Tanh):
+        return "the joint's activation is not tanh"
+    for m in (predictor, joint):
+        if m.training and any(isinstance(d, torch.nn.Dropout) and d.p > 0 for d in m.modules()):
+            return "the predictor or joint is in training mode with dropout (call .eval())"
+    if predictor.training and rnn.dropout > 0 and rnn.num_layers > 1:
+        return "the predictor's LSTM is in training mode with dropout between layers (call .eval())"
+    params = list(predictor.parameters()) + list(joint.parameters())
+    dt = joint.ffn_out.weight.dtype
+    if dt not in (torch.float32, torch.bfloat16) or any(q.dtype != dt for q in params):
+        return "the predictor and joint weights are not all fp32 or all bf16"
+    if not encoder_out.is_cuda:
+        return "the encoder output is not on the GPU"
+    if any(not q.is_cuda or q.device != encoder_out.device for q in params):
+        return "the predictor / joint weights are not on the encoder output's GPU"
+    if encoder_out.dim() != 3 or encoder_out.shape[0] == 0 or encoder_out.shape[1] == 0:
+        return "encoder_out must be (B, T, D) with B, T >= 1"
+    B, T, D = encoder_out.shape
+    E, Hd, Pd, J = predictor.embed.embedding_dim, rnn.hidden_size, predictor.projection.out_features, joint.ffn_out.in_features
+    V = joint.ffn_out.out_features
+    if any(d % 4 for d in (E, Hd, Pd, J)):
+        return "the embedding, hidden, projection and join dimensions must be multiples of 4"
+    if J > 2048:
+        return f"join_dim {J} is above 2048"
+    if predictor.embed.num_embeddings < V:
+        return "the predictor's embedding has fewer rows than the joint's vocabulary"
+    if dt == torch.float32 and D % 4:
+        return f"encoder dimension {D} is not a multiple of 4 (gemm_f32)"
+    if dt == torch.bfloat16 and (D % 64 or J % 8):
+        return f"encoder dimension {D} is not a multiple of 64 or join_dim {J} not of 8 (gemm_bf16)"
+    if B > 256:
+        return f"{B} utterances: at most 256 per call"
+    if n_steps < 1 or T * n_steps >= 2 ** 31:
+        return "n_steps must be >= 1 and T * n_steps below 2^31"
+    return None
+
+
+def rnnt_greedy_search(predictor, joint, encoder_out: torch.Tensor, encoder_out_lens: torch.Tensor, blank: int = 0,
+                       n_steps: int = 64, chunk: int = RNNT_GREEDY_CHUNK):
+    """Greedy search (basic_greedy_search, wenet/transducer/search/greedy_search.py) of every utterance of encoder_out (B, T, D)
+    on the lockstep kernels of csrc/rnnt_greedy.hip (include/pafc_search.h: pafc_rnnt_greedy_*).  E = enc_ffn(encoder_out) once
+    through gemm_f32 / gemm_bf16, then T steps -- the number every utterance of length T needs at least -- and chunks of
+    `chunk` steps until no row is running.  Host reads per call: one 4-byte read of the running-row count after the first T
+    steps and after every further chunk, plus one read of the packed results: 2 + ceil(max(0, S - T) / chunk), S the largest
+    number of decisions of one utterance.  Returns (tokens, frames, scores): per utterance its token list, the frame of each
+    token, and the path log-probability (sum of log p over every decision, blanks included, float64)."""
+    unmet = rnnt_greedy_unmet(predictor, joint, encoder_out, n_steps)
+    if unmet is not None:
+        raise _lib.PafcError(f"rnnt_greedy_search: {unmet}")
+    B, T, D = encoder_out.shape
+    dev = encoder_out.device
+    wdt = joint.ffn_out.weight.dtype
+    x = encoder_out.detach().to(wdt).reshape(B * T, D).contiguous()
+    ef = joint.enc_ffn
+    if wdt == torch.float32:
+        E = gemm_f32(x, ef.weight.detach(), None if ef.bias is None else ef.bias.detach())
+    else:
+        E = gemm_bf16(x, ef.weight.detach().contiguous(), None if ef.bias is None else ef.bias.detach().contiguous())
+    lens = encoder_out_lens.detach().to(device=dev, dtype=torch.int64).contiguous()
+    if lens.shape != (B,):
+        raise _lib.PafcError("rnnt_greedy_search: encoder_out_lens must be (B,)")
+    L = _bind_rnnt_greedy()
+    net, keep = _greedy_net(predictor, joint)
+    pnet = ctypes.byref(net)
+    nbytes = L.pafc_rnnt_greedy_workspace_bytes(pnet, B, T, n_steps)
+    if nbytes == 0:
+        raise _lib.PafcError("pafc_rnnt_greedy_workspace_bytes: unsupported dimensions")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    running = torch.empty(1, dtype=torch.int32, device=dev)
+    st = _lib.stream_of(E)
+    _lib.check(L.pafc_rnnt_greedy_init(pnet, B, T, n_steps, int(blank), _lib.ptr(lens), _lib.ptr(ws), nbytes, st),
+               "pafc_rnnt_greedy_init")
+    args = (pnet, B, T, n_steps, int(blank), _lib.ptr(E), _lib.ptr(ws), nbytes, _lib.ptr(running), st)
+    steps, todo = 0, T
+    while True:
+        for _ in range(todo):
+            _lib.check(L.pafc_rnnt_greedy_step(*args), "pafc_rnnt_greedy_step")
+        steps += todo
+        if int(running.item()) == 0:               # the host read of this chunk
+            break
+        if steps > T * (n_steps + 1):              # every row ends within T (n_steps + 1) decisions
+            raise _lib.PafcError("rnnt_greedy_search: rows still running after T * (n_steps + 1) steps")
+        todo = chunk
+    ld = steps                                     # a row emits at most one token per step
+    out = torch.empty(B * 8 + B * 4 + 2 * B * ld * 4, dtype=torch.uint8, device=dev)
+    score = out[:B * 8].view(torch.float64)
+    ntok = out[B * 8:B * 12].view(torch.int32)
+    toks = out[B * 12:B * 12 + B * ld * 4].view(torch.int32)
+    frames = out[B * 12 + B * ld * 4:].view(torch.int32)
+    _lib.check(L.pafc_rnnt_greedy_finish(pnet, B, T, n_steps, _lib.ptr(ws), nbytes, ld, _lib.ptr(toks), _lib.ptr(frames),
+                                         _lib.ptr(ntok), _lib.ptr(score), None, st), "pafc_rnnt_greedy_finish")
+    h = out.cpu()                                  # the final read
+    del keep
+    n_h = h[B * 8:B * 12].view(torch.int32).tolist()
+    s_h = h[:B * 8].view(torch.float64).tolist()
+    t_h = h[B * 12:B * 12 + B * ld * 4].view(torch.int32).view(B, ld)
+    f_h = h[B * 12 + B * ld * 4:].view(torch.int32).view(B, ld)
+    return ([t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)], s_h)
+
+
 def _bind2():
     L = _bind()
     if getattr(L, "_pafc_glue_bound", False):

@@ -1,5 +1,6 @@
 """Transducer container around the accelerated encoder (reference: wenet/transducer/transducer.py): encoder + CTC +
-RNN predictor + joint, `decode(methods=[...,'rnnt_beam_search'])` (:695-813) and `beam_search_decode` (:644-693).
+RNN predictor + joint, `decode(methods=[...,'rnnt_beam_search', 'rnnt_greedy_search'])` (:695-813), `beam_search_decode`
+(:644-693) and `greedy_search` (:427-472).
 
 Training objective (forward, :105-175): transducer_weight * RNN-T loss + ctc_weight * CTC loss over the accelerated
 encoder.  The reference's RNN-T loss is the third-party `optimized_transducer.transducer_loss` (transducer.py:506-523;
@@ -12,6 +13,7 @@ import torch
 from ..transformer.asr_model import ASRModel
 from ..transformer.search import DecodeResult
 from .loss import transducer_loss
+from .search.greedy_search import batch_greedy_search
 from .search.prefix_beam_search import PrefixBeamSearch
 
 IGNORE_ID = -1
@@ -111,12 +113,26 @@ class Transducer(ASRModel):
                                                  transducer_weight, cat_embs)
 
     @torch.no_grad()
+    def greedy_search(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
+                      num_decoding_left_chunks: int = -1, simulate_streaming: bool = False, n_steps: int = 64
+                      ) -> List[List[int]]:
+        """transducer.py:427-472 for B >= 1 (the reference asserts B = 1): the encoder, then the greedy search of every
+        utterance (search/greedy_search.py: on the GPU the lockstep kernels, on the CPU the reference's loop).
+        simulate_streaming is ignored, as in the reference."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        assert decoding_chunk_size != 0
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
+                                                          num_decoding_left_chunks)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        return [r.tokens for r in batch_greedy_search(self, encoder_out, encoder_out_lens, n_steps)]
+
+    @torch.no_grad()
     def decode(self, methods: List[str], speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int = 10,
                decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0,
                transducer_weight: float = 0.0, simulate_streaming: bool = False, reverse_weight: float = 0.0,
                context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0, cat_embs=None, **_ignored
                ) -> Dict[str, List[DecodeResult]]:
-        rest = [m for m in methods if m != "rnnt_beam_search"]
+        rest = [m for m in methods if m not in ("rnnt_beam_search", "rnnt_greedy_search")]
         encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
                                                           num_decoding_left_chunks, simulate_streaming, cat_embs)
         encoder_lens = encoder_mask.squeeze(1).sum(1)
@@ -135,4 +151,6 @@ class Transducer(ASRModel):
             results["rnnt_beam_search"] = self.beam_search_decode(
                 encoder_outs=encoder_out, encoder_lens=encoder_lens, ctc_probs=ctc_probs, beam_size=beam_size,
                 ctc_weight=ctc_weight, transducer_weight=transducer_weight, cat_embs=cat_embs)
+        if "rnnt_greedy_search" in methods:
+            results["rnnt_greedy_search"] = batch_greedy_search(self, encoder_out, encoder_lens)
         return results
