@@ -100,6 +100,34 @@ int pafc_rnnt_greedy_finish(const pafc_rnnt_greedy_net *net, int B, int T, int n
                             int ld, int32_t *tokens, int32_t *frames, int32_t *ntok, double *score, int32_t *running,
                             pafc_stream_t stream);
 
+/* RNN-T greedy search chunk by chunk, with the decoder state carried from one chunk to the next (pafc_rnnt_greedy_stream_*).
+ * The stream workspace begins with the pafc_rnnt_greedy_* layout for (B, T = Tmax), followed by an int64 frame base per row,
+ * so pafc_rnnt_greedy_step(net, B, Tmax, n_steps, blank_id, E, workspace, ...) advances it, E being a fixed (B, Tmax, join_dim)
+ * buffer that holds enc_ffn of the current chunk.  A row leaves a chunk at a frame boundary, holding the state the
+ * whole-utterance decode holds there, so the decisions over a stream of chunks are those of the decode of the concatenated
+ * frames, given the same E rows.
+ * reset: restarts the rows with row_mask[b] != 0 (device int32 (B), or NULL = every row): zero committed LSTM state,
+ *   predictor input blank, frame base 0, no frames, score 0.  Other rows are untouched.  Call it on every row before the
+ *   first feed.
+ * feed: begins a chunk: per row the frame base advances by the previous chunk's frame count, the row gets
+ *   clamp(nframes[b], 0, Tmax) frames of E (nframes: device int64 (B)), and its per-chunk token count is zeroed; the LSTM
+ *   state, predictor input and output, symbols of the current frame and score carry over.  A row with no frames keeps its
+ *   state.  running (device int32, or NULL) receives the number of rows with frames.  Then pafc_rnnt_greedy_step until no
+ *   row is running.
+ * drain: per row the tokens emitted since the last feed (ntok[b], first min(ntok[b], ld) of them into row b of tokens
+ *   (B, ld) int32), their absolute frame indices (frame base + frame in the chunk, (B, ld) int64, may be NULL) and the
+ *   path score since the row's reset (float64 (B), may be NULL).
+ * Nothing reads the host or allocates: a feed and its steps can be captured in a graph.  B <= 256, Tmax * n_steps < 2^31,
+ * 256-byte aligned workspace. */
+size_t pafc_rnnt_greedy_stream_workspace_bytes(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps);
+int pafc_rnnt_greedy_stream_reset(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, int blank_id, const int32_t *row_mask,
+                                  void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+int pafc_rnnt_greedy_stream_feed(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, int blank_id, const int64_t *nframes,
+                                 void *workspace, size_t workspace_bytes, int32_t *running, pafc_stream_t stream);
+int pafc_rnnt_greedy_stream_drain(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, const void *workspace,
+                                  size_t workspace_bytes, int ld, int32_t *tokens, int64_t *frames, int32_t *ntok, double *score,
+                                  int32_t *running, pafc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

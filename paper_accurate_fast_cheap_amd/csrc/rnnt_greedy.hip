@@ -1,4 +1,5 @@
-// Batched RNN-T greedy search on gfx950 (C ABI: include/pafc_search.h: pafc_rnnt_greedy_*).
+// Batched RNN-T greedy search on gfx950 (C ABI: include/pafc_search.h: pafc_rnnt_greedy_*, and pafc_rnnt_greedy_stream_* for
+// chunk-by-chunk decoding with carried state).
 //
 // basic_greedy_search (wenet/transducer/search/greedy_search.py) for every utterance of a batch at once, in lockstep: one step
 // advances every live row by one decision.  Per row: frame t, predictor input tok, need_pred, k (symbols emitted in this frame),
@@ -41,6 +42,15 @@ __device__ __forceinline__ void ld4(const bf16_t *p, float *f) {
     f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = __uint_as_float(q.y & 0xffff0000u);
 }
 template <typename T> __device__ __forceinline__ float ld1(const T *p) { return Elem<T>::load(p); }
+
+// w . x over four elements as one fixed chain: w0 x0 rounded, then three fmas.  Written out, because the compiler's own
+// contraction of `w0 x0 + w1 x1 + w2 x2 + w3 x3` differs between the unrolled slots of a pass (some fused, some not), which
+// made an fp32 row's result depend on its position among the rows of a step.  (bf16 operands: the products are exact in
+// fp32, so fused and unfused agree and this is the arithmetic bf16 always had.)
+__device__ __forceinline__ float dot4(float w0, float w1, float w2, float w3, float x0, float x1, float x2, float x3) {
+    return fmaf(w3, x3, fmaf(w2, x2, fmaf(w1, x1, w0 * x0)));
+}
+__device__ __forceinline__ float dot4(const float *w, const float *x) { return dot4(w[0], w[1], w[2], w[3], x[0], x[1], x[2], x[3]); }
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -118,7 +128,7 @@ __global__ __launch_bounds__(256) void greedy_lstm_kernel(GState s, int layer, i
                 float x[4];
                 if (EMB) ld4(xe[i] + kk, x); else ld4(xf[i] + kk, x);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) acc[g][i] += w[g][0] * x[0] + w[g][1] * x[1] + w[g][2] * x[2] + w[g][3] * x[3];
+                for (int g = 0; g < 4; ++g) acc[g][i] += dot4(w[g], x);
             }
         }
         for (int kk = lane * 4; kk < H; kk += 256) {
@@ -130,7 +140,7 @@ __global__ __launch_bounds__(256) void greedy_lstm_kernel(GState s, int layer, i
                 float x[4];
                 ld4(hr[i] + kk, x);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) acc[g][i] += w[g][0] * x[0] + w[g][1] * x[1] + w[g][2] * x[2] + w[g][3] * x[3];
+                for (int g = 0; g < 4; ++g) acc[g][i] += dot4(w[g], x);
             }
         }
 #pragma unroll
@@ -183,7 +193,7 @@ __global__ __launch_bounds__(256) void greedy_matvec_kernel(GState s, int N, int
             for (int i = 0; i < GNB; ++i) {
                 float v[4];
                 ld4(xr[i] + kk, v);
-                acc[i] += w[0] * v[0] + w[1] * v[1] + w[2] * v[2] + w[3] * v[3];
+                acc[i] += dot4(w, v);
             }
         }
 #pragma unroll
@@ -230,7 +240,7 @@ __global__ __launch_bounds__(256) void greedy_joint_kernel(GState s, const WT *E
 #pragma unroll
                 for (int i = 0; i < GNB; ++i) {
                     const float4 h = *reinterpret_cast<const float4 *>(hsh + i * J + kk);
-                    acc[i] += w[0] * h.x + w[1] * h.y + w[2] * h.z + w[3] * h.w;
+                    acc[i] += dot4(w[0], w[1], w[2], w[3], h.x, h.y, h.z, h.w);
                 }
             }
         }
@@ -347,6 +357,72 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(GState s, int ld, in
     }
 }
 
+// ---- streaming (pafc_rnnt_greedy_stream_*) ----------------------------------------------------------------------------------
+// The stream workspace is the GState layout for (B, Tmax) followed by an int64 frame base per row (the absolute index of the
+// current chunk's frame 0), so the step kernels above advance it unchanged with T = Tmax over a fixed (B, Tmax, J) E.  When a
+// row leaves a chunk its state is (t = Tb, k = 0, tok, need, slot, pred, P, score): what the whole-utterance run holds at that
+// frame boundary.  feed only moves the frame window; everything the decisions depend on carries over.
+
+// the lists of running rows / rows that need the predictor, in row order (thread 0 of a block, after a barrier)
+__device__ __forceinline__ void rebuild_lists(const GState &s, int32_t *running) {
+    int na = 0, nl = 0;
+    for (int r = 0; r < s.B; ++r) {
+        if (s.t[r] < s.Tb[r]) {
+            s.live[nl++] = r;
+            if (s.need[r]) s.act[na++] = r;
+        }
+    }
+    s.ctl[0] = na; s.ctl[1] = nl;
+    if (running) running[0] = nl;
+}
+
+__global__ __launch_bounds__(256) void greedy_stream_reset_kernel(GState s, int64_t *base, const int32_t *mask) {
+    const int tid = threadIdx.x;
+    for (int b = tid; b < s.B; b += 256) {
+        if (mask && !mask[b]) continue;
+        s.Tb[b] = 0; s.t[b] = 0; s.tok[b] = s.blank; s.need[b] = 1; s.k[b] = 0; s.ntok[b] = 0; s.slot[b] = 0;
+        s.score[b] = 0.0;
+        base[b] = 0;
+    }
+    const long nh = (long)s.L * s.B * s.H;       // slot 0 = the committed zero state
+    for (long q = tid; q < nh; q += 256) {
+        const int row = (int)((q / s.H) % s.B);
+        if (!mask || mask[row]) { s.hs[q] = 0.f; s.cs[q] = 0.f; }
+    }
+    __syncthreads();
+    if (tid == 0) rebuild_lists(s, nullptr);
+}
+
+__global__ __launch_bounds__(256) void greedy_stream_feed_kernel(GState s, int64_t *base, const int64_t *nframes, int32_t *running) {
+    const int tid = threadIdx.x;
+    for (int b = tid; b < s.B; b += 256) {
+        const int64_t l = nframes[b];
+        base[b] += s.Tb[b];
+        s.Tb[b] = (int)(l < 0 ? 0 : l > s.T ? s.T : l);
+        s.t[b] = 0;
+        s.ntok[b] = 0;
+    }
+    __syncthreads();
+    if (tid == 0) rebuild_lists(s, running);
+}
+
+__global__ __launch_bounds__(256) void greedy_stream_drain_kernel(GState s, const int64_t *base, int ld, int32_t *tokens, int64_t *frames,
+                                                                  int32_t *ntok, double *score, int32_t *running) {
+    const int b = blockIdx.x;
+    const int n = s.ntok[b];
+    const int m = (int)min((long)min(n, ld), s.cap);
+    const int64_t f0 = base[b];
+    for (int i = threadIdx.x; i < m; i += 256) {
+        tokens[(long)b * ld + i] = s.otok[(long)b * s.cap + i];
+        if (frames) frames[(long)b * ld + i] = f0 + s.ofr[(long)b * s.cap + i];
+    }
+    if (threadIdx.x == 0) {
+        ntok[b] = n;
+        if (score) score[b] = s.score[b];
+        if (b == 0 && running) running[0] = s.ctl[1];
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -397,6 +473,15 @@ int check_net(const pafc_rnnt_greedy_net *n) {
     }
     if (!aligned16(n->embed) || !aligned16(n->proj_w) || !aligned16(n->pred_ffn_w) || !aligned16(n->out_w)) return PAFC_ERR_ALIGNMENT;
     return PAFC_OK;
+}
+
+// the stream workspace: the GState layout, then the frame bases
+GState stream_layout(void *ws, const pafc_rnnt_greedy_net *n, int B, int Tmax, int nsteps, int blank, int64_t **base, size_t *bytes) {
+    size_t o = 0;
+    const GState s = layout(ws, B, Tmax, n->num_layers, n->hidden, n->pred_dim, n->join_dim, n->vocab, nsteps, blank, &o);
+    if (base) *base = ws ? (int64_t *)((char *)ws + o) : nullptr;
+    *bytes = o + al256((size_t)B * sizeof(int64_t));
+    return s;
 }
 
 template <typename WT>
@@ -483,6 +568,66 @@ int pafc_rnnt_greedy_finish(const pafc_rnnt_greedy_net *net, int B, int T, int n
                                         net->vocab, n_steps, 0, &bytes);
     hipLaunchKernelGGL(pafc::greedy_finish_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, s, ld, tokens, frames, ntok,
                        score, running);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+size_t pafc_rnnt_greedy_stream_workspace_bytes(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps) {
+    if (!net || net->num_layers <= 0 || net->hidden <= 0 || net->pred_dim <= 0 || net->join_dim <= 0 || net->vocab <= 0) return 0;
+    if (pafc::check_dims(B, Tmax, n_steps, 0, net->vocab) != PAFC_OK) return 0;
+    size_t bytes = 0;
+    pafc::stream_layout(nullptr, net, B, Tmax, n_steps, 0, nullptr, &bytes);
+    return bytes;
+}
+
+static int stream_check(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, int blank_id, const void *workspace,
+                        size_t workspace_bytes) {
+    if (!net || !workspace) return PAFC_ERR_NULL_POINTER;
+    int rc = pafc::check_dims(B, Tmax, n_steps, blank_id, net->vocab);
+    if (rc != PAFC_OK) return rc;
+    if (workspace_bytes < pafc_rnnt_greedy_stream_workspace_bytes(net, B, Tmax, n_steps)) return PAFC_ERR_WORKSPACE;
+    if (((uintptr_t)workspace & 255) != 0) return PAFC_ERR_ALIGNMENT;
+    return PAFC_OK;
+}
+
+int pafc_rnnt_greedy_stream_reset(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, int blank_id, const int32_t *row_mask,
+                                  void *workspace, size_t workspace_bytes, pafc_stream_t stream) {
+    int rc = pafc::check_net(net);
+    if (rc != PAFC_OK) return rc;
+    rc = stream_check(net, B, Tmax, n_steps, blank_id, workspace, workspace_bytes);
+    if (rc != PAFC_OK) return rc;
+    size_t bytes = 0;
+    int64_t *base = nullptr;
+    const pafc::GState s = pafc::stream_layout(workspace, net, B, Tmax, n_steps, blank_id, &base, &bytes);
+    hipLaunchKernelGGL(pafc::greedy_stream_reset_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, s, base, row_mask);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+int pafc_rnnt_greedy_stream_feed(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, int blank_id, const int64_t *nframes,
+                                 void *workspace, size_t workspace_bytes, int32_t *running, pafc_stream_t stream) {
+    int rc = pafc::check_net(net);
+    if (rc != PAFC_OK) return rc;
+    if (!nframes) return PAFC_ERR_NULL_POINTER;
+    rc = stream_check(net, B, Tmax, n_steps, blank_id, workspace, workspace_bytes);
+    if (rc != PAFC_OK) return rc;
+    size_t bytes = 0;
+    int64_t *base = nullptr;
+    const pafc::GState s = pafc::stream_layout(workspace, net, B, Tmax, n_steps, blank_id, &base, &bytes);
+    hipLaunchKernelGGL(pafc::greedy_stream_feed_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, s, base, nframes, running);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+int pafc_rnnt_greedy_stream_drain(const pafc_rnnt_greedy_net *net, int B, int Tmax, int n_steps, const void *workspace,
+                                  size_t workspace_bytes, int ld, int32_t *tokens, int64_t *frames, int32_t *ntok, double *score,
+                                  int32_t *running, pafc_stream_t stream) {
+    if (!tokens || !ntok) return PAFC_ERR_NULL_POINTER;
+    int rc = stream_check(net, B, Tmax, n_steps, 0, workspace, workspace_bytes);
+    if (rc != PAFC_OK) return rc;
+    if (ld <= 0) return PAFC_ERR_BAD_DIMS;
+    size_t bytes = 0;
+    int64_t *base = nullptr;
+    const pafc::GState s = pafc::stream_layout(const_cast<void *>(workspace), net, B, Tmax, n_steps, 0, &base, &bytes);
+    hipLaunchKernelGGL(pafc::greedy_stream_drain_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, s, base, ld, tokens,
+                       frames, ntok, score, running);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 

@@ -4,7 +4,7 @@ import ctypes
 import os
 import threading
 import weakref
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -1412,6 +1412,195 @@ def rnnt_greedy_search(predictor, joint, encoder_out: torch.Tensor, encoder_out_
     t_h = h[B * 12:B * 12 + B * ld * 4].view(torch.int32).view(B, ld)
     f_h = h[B * 12 + B * ld * 4:].view(torch.int32).view(B, ld)
     return ([t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)], s_h)
+
+
+def _bind_rnnt_greedy_stream():
+    L = _bind_rnnt_greedy()
+    if not getattr(L, "_pafc_rnntgreedy_stream_bound", False):
+        from ctypes import c_size_t
+        P, I, Z = c_void_p, c_int, c_size_t
+        _lib._sig(L.pafc_rnnt_greedy_stream_workspace_bytes, Z, P, I, I, I)
+        _lib._sig(L.pafc_rnnt_greedy_stream_reset, I, P, I, I, I, I, P, P, Z, P)
+        _lib._sig(L.pafc_rnnt_greedy_stream_feed, I, P, I, I, I, I, P, P, Z, P, P)
+        _lib._sig(L.pafc_rnnt_greedy_stream_drain, I, P, I, I, I, P, Z, I, P, P, P, P, P, P)
+        L._pafc_rnntgreedy_stream_bound = True
+    return L
+
+
+def rnnt_greedy_stream_unmet(predictor, joint, B: int, Tmax: int, D: int, device, n_steps: int = 64) -> Optional[str]:
+    """The condition the streaming greedy search (RnntGreedyStream) does not meet for B streams of chunks of at most Tmax
+    frames of dimension D on `device`, or None: rnnt_greedy_unmet's conditions, and Tmax >= 1."""
+    if Tmax < 1:
+        return f"Tmax {Tmax}: a chunk must hold at least one frame"
+    if B < 1:
+        return f"{B} streams: at least one"
+    # (an expanded view of one element: the shape, dtype and device of the chunk buffer without allocating it)
+    like = torch.empty(1, 1, 1, device=device).expand(B, Tmax, D)
+    return rnnt_greedy_unmet(predictor, joint, like, n_steps)
+
+
+class RnntGreedyStream:
+    """Greedy search of B streams chunk by chunk on the lockstep kernels of csrc/rnnt_greedy.hip (include/pafc_search.h:
+    pafc_rnnt_greedy_stream_*), the decoder state carried from one chunk to the next.  The object owns the workspace, a fixed
+    (B, Tmax, D) input buffer, the fixed (B, Tmax, J) E = enc_ffn buffer (gemm_f32 / gemm_bf16 into it) and the weights'
+    net struct.  Given the same E rows, the tokens, frames and scores over a stream equal rnnt_greedy_search over the
+    concatenated frames bit for bit: a row leaves a chunk at a frame boundary, in the state the whole-utterance decode
+    holds there.
+
+    feed(chunk (B, n <= Tmax, D), nframes=None): row b decodes its first nframes[b] frames (default n; 0 = the row sits the
+    chunk out with its state unchanged).  Steps: n -- what every row with n frames needs at least --, then chunks of
+    RNNT_GREEDY_CHUNK until no row runs.  Host reads per feed: one 4-byte read of the running-row count after the first n
+    steps and after every further chunk, plus one read of the results: 2 + ceil(max(0, S - n) / chunk), S the largest number
+    of decisions a row makes in this chunk.  Launches per feed: the chunk copied into the input buffer and nframes written to
+    its device buffer (a fill, or a copy of the given counts -- pass a device int64 tensor to keep it off the host), both
+    eager because their sources change from feed to feed; then the fixed part -- E projection, feed kernel, n steps --
+    replayed from a hipGraph captured once per n (eager only where the capture is refused); then the eager chunks of
+    steps, the drain and its read.  Only the package's own kernels run, so a streamer may live on a side stream."""
+
+    def __init__(self, predictor, joint, B: int, Tmax: int, n_steps: int = 64, blank: int = 0, D: Optional[int] = None,
+                 chunk: int = RNNT_GREEDY_CHUNK, use_graph: bool = True):
+        D = joint.enc_ffn.in_features if D is None and getattr(joint, "enc_ffn", None) is not None else D
+        dev = joint.ffn_out.weight.device
+        unmet = rnnt_greedy_stream_unmet(predictor, joint, B, Tmax, D or 0, dev, n_steps)
+        if unmet is not None:
+            raise _lib.PafcError(f"RnntGreedyStream: {unmet}")
+        self.B, self.Tmax, self.D, self.n_steps, self.blank, self.chunk = B, Tmax, D, n_steps, int(blank), chunk
+        self.device, self.use_graph = dev, use_graph
+        self.dtype = joint.ffn_out.weight.dtype
+        ef = joint.enc_ffn
+        self._w = ef.weight.detach().contiguous()
+        self._b = None if ef.bias is None else ef.bias.detach().contiguous()
+        J = joint.ffn_out.in_features
+        self._L = _bind_rnnt_greedy_stream()
+        self._net, self._keep = _greedy_net(predictor, joint)
+        self._pnet = ctypes.byref(self._net)
+        self._nbytes = self._L.pafc_rnnt_greedy_stream_workspace_bytes(self._pnet, B, Tmax, n_steps)
+        if self._nbytes == 0:
+            raise _lib.PafcError("pafc_rnnt_greedy_stream_workspace_bytes: unsupported dimensions")
+        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self._x = torch.zeros(B * Tmax, D, dtype=self.dtype, device=dev)
+        self._E = torch.empty(B * Tmax, J, dtype=self.dtype, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._running = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._graphs = {}
+        self._last_n = None
+        self._score = [0.0] * B
+        self.last_steps = 0
+        self.reset()
+
+    def reset(self, rows=None):
+        """Restart the given rows (all when None): a fresh decode from their next chunk on; other rows are untouched."""
+        st = _lib.stream_of(self._ws)
+        mask = None
+        if rows is not None:
+            m = torch.zeros(self.B, dtype=torch.int32)
+            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
+            self._mask.copy_(m)
+            mask = _lib.ptr(self._mask)
+        for b in (range(self.B) if rows is None else rows):
+            self._score[b] = 0.0
+        _lib.check(self._L.pafc_rnnt_greedy_stream_reset(self._pnet, self.B, self.Tmax, self.n_steps, self.blank, mask,
+                                                          _lib.ptr(self._ws), self._nbytes, st), "pafc_rnnt_greedy_stream_reset")
+
+    def _project(self):
+        if self.dtype == torch.float32:
+            gemm_f32(self._x, self._w, self._b, out=self._E)
+        else:
+            gemm_bf16(self._x, self._w, self._b, out=self._E)
+
+    def _step(self, st):
+        _lib.check(self._L.pafc_rnnt_greedy_step(self._pnet, self.B, self.Tmax, self.n_steps, self.blank, _lib.ptr(self._E),
+                                                 _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._running), st),
+                   "pafc_rnnt_greedy_step")
+
+    def _fixed(self, n):
+        """The fixed part of a feed of n frames: E projection, feed kernel, n steps."""
+        st = _lib.stream_of(self._ws)
+        self._project()
+        _lib.check(self._L.pafc_rnnt_greedy_stream_feed(self._pnet, self.B, self.Tmax, self.n_steps, self.blank,
+                                                         _lib.ptr(self._nf), _lib.ptr(self._ws), self._nbytes,
+                                                         _lib.ptr(self._running), st), "pafc_rnnt_greedy_stream_feed")
+        for _ in range(n):
+            self._step(st)
+
+    def _run_fixed(self, n):
+        g = self._graphs.get(n, False)
+        if g is False and self.use_graph:
+            # capture once per n; only a REFUSED capture (nothing ran: the state is as before) finishes eagerly, for good
+            g = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(g):
+                    self._fixed(n)
+            except RuntimeError as e:
+                torch.cuda.synchronize(self.device)
+                if isinstance(e, _lib.PafcError) or "captur" not in str(e).lower():
+                    raise
+                g = None
+            self._graphs[n] = g
+        if g:
+            g.replay()
+        else:
+            self._fixed(n)
+
+    @property
+    def graphed(self) -> bool:
+        """Whether the last feed replayed a captured graph."""
+        return bool(self._graphs.get(self._last_n, None)) if self.use_graph else False
+
+    def feed(self, encoder_chunk: torch.Tensor, nframes=None):
+        """Decode one chunk (B, n, D), n <= Tmax.  Returns (tokens, frames): per row the tokens emitted in this chunk and
+        their absolute frame indices (frames since the row's reset)."""
+        B, Tmax = self.B, self.Tmax
+        if encoder_chunk.dim() != 3 or encoder_chunk.shape[0] != B or encoder_chunk.shape[2] != self.D:
+            raise _lib.PafcError(f"RnntGreedyStream.feed: the chunk must be ({B}, n, {self.D})")
+        n = encoder_chunk.shape[1]
+        if not 0 <= n <= Tmax:
+            raise _lib.PafcError(f"RnntGreedyStream.feed: {n} frames, at most Tmax = {Tmax}")
+        if encoder_chunk.device != self.device:
+            raise _lib.PafcError("RnntGreedyStream.feed: the chunk is not on the weights' GPU")
+        if n:
+            self._x.view(B, Tmax, self.D)[:, :n].copy_(encoder_chunk.detach())
+        if nframes is None:
+            self._nf.fill_(n)
+        else:
+            nf = torch.as_tensor(nframes, dtype=torch.int64)
+            if nf.shape != (B,):
+                raise _lib.PafcError(f"RnntGreedyStream.feed: nframes must be ({B},)")
+            self._nf.copy_(nf.clamp(0, n))
+        self._last_n = n
+        self._run_fixed(n)
+        st = _lib.stream_of(self._ws)
+        steps = n
+        limit = n * (self.n_steps + 1)                 # every row ends its frames within n (n_steps + 1) decisions
+        while int(self._running.item()) != 0:          # the host read after the fixed part and after every further chunk
+            if steps >= limit:
+                raise _lib.PafcError("RnntGreedyStream.feed: rows still running after n * (n_steps + 1) steps")
+            for _ in range(self.chunk):
+                self._step(st)
+            steps += self.chunk
+        self.last_steps = steps
+        ld = max(1, steps)                             # a row emits at most one token per step
+        # one buffer, one read: score (B) f64 | frames (B, ld) i64 | ntok (B) i32 | tokens (B, ld) i32 -- 8-byte fields first
+        o1, o2, o3 = B * 8, B * 8 + B * ld * 8, B * 12 + B * ld * 8
+        out = torch.empty(o3 + B * ld * 4, dtype=torch.uint8, device=self.device)
+        _lib.check(self._L.pafc_rnnt_greedy_stream_drain(self._pnet, B, Tmax, self.n_steps, _lib.ptr(self._ws), self._nbytes, ld,
+                                                          _lib.ptr(out[o3:].view(torch.int32)),
+                                                          _lib.ptr(out[o1:o2].view(torch.int64)),
+                                                          _lib.ptr(out[o2:o3].view(torch.int32)),
+                                                          _lib.ptr(out[:o1].view(torch.float64)), None, st),
+                   "pafc_rnnt_greedy_stream_drain")
+        h = out.cpu()                                  # the final read
+        self._score = h[:o1].view(torch.float64).tolist()
+        f_h = h[o1:o2].view(torch.int64).view(B, ld)
+        n_h = h[o2:o3].view(torch.int32).tolist()
+        t_h = h[o3:].view(torch.int32).view(B, ld)
+        return [t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)]
+
+    @property
+    def score(self) -> List[float]:
+        """Per row the path score (float64 sum of log p over every decision) since its reset, as of the last feed."""
+        return list(self._score)
 
 
 def _bind2():

@@ -1,19 +1,20 @@
 """Transducer container around the accelerated encoder (reference: wenet/transducer/transducer.py): encoder + CTC +
 RNN predictor + joint, `decode(methods=[...,'rnnt_beam_search', 'rnnt_greedy_search'])` (:695-813), `beam_search_decode`
-(:644-693) and `greedy_search` (:427-472).
+(:644-693), `greedy_search` (:427-472), the runtime step API (:474-505) and `stream_greedy_search`: the streaming encoder
+and the greedy search chunk by chunk with carried decoder state.
 
 Training objective (forward, :105-175): transducer_weight * RNN-T loss + ctc_weight * CTC loss over the accelerated
 encoder.  The reference's RNN-T loss is the third-party `optimized_transducer.transducer_loss` (transducer.py:506-523;
 Rev fork, unpinned): restated from the published definition in `loss.py` -- PARITY UNPINNED.  Its attention decoder was
 not released (decoder.py is swallowed by .gitignore:44), so the attention branch does not exist here."""
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
 from ..transformer.asr_model import ASRModel
 from ..transformer.search import DecodeResult
 from .loss import transducer_loss
-from .search.greedy_search import batch_greedy_search
+from .search.greedy_search import GreedyStreamer, batch_greedy_search
 from .search.prefix_beam_search import PrefixBeamSearch
 
 IGNORE_ID = -1
@@ -125,6 +126,64 @@ class Transducer(ASRModel):
                                                           num_decoding_left_chunks)
         encoder_out_lens = encoder_mask.squeeze(1).sum(1)
         return [r.tokens for r in batch_greedy_search(self, encoder_out, encoder_out_lens, n_steps)]
+
+    @torch.no_grad()
+    def stream_greedy_search(self, speech: torch.Tensor, decoding_chunk_size: int, n_steps: int = 64,
+                             on_tokens: Optional[Callable[[int, List[List[int]]], None]] = None) -> List[DecodeResult]:
+        """Streaming greedy search of B equal-length streams (B, T, F), the contract of encoder.stream_chunks: the windows of
+        forward_chunk_by_chunk through the encoder with carried state -- forward_chunk_carry for a causal conv module (or
+        none), forward_chunk_lookahead for the shipped non-causal one, drained with final=True after the last window --
+        and each window's output frames into one GreedyStreamer.  on_tokens(window_index, new_tokens_per_row) is called
+        after every window.  Returns per stream the tokens, their absolute frames and the path score.  Over the stream the
+        decisions equal batch_greedy_search of the concatenated encoder outputs of the same steps."""
+        if decoding_chunk_size <= 0:
+            raise ValueError("stream_greedy_search: decoding_chunk_size must be > 0 (a chunked stream)")
+        from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
+        enc = self.encoder
+        layers = list(getattr(enc, "encoders", []))
+        if not layers or any(type(l.self_attn) is not RWKV_TmixWrapper for l in layers) or not enc.normalize_before:
+            raise ValueError("stream_greedy_search: the encoder must be a pre-norm uni-directional model (rwkv_tmix60 slot); "
+                             "a bidirectional encoder needs the whole utterance")
+        lookahead = any(l.conv_module is not None and l.conv_module.lorder == 0 for l in layers)
+        sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
+        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
+        T = speech.size(1)
+        starts = list(range(0, T - ctx + 1, stride))
+        streamer = GreedyStreamer(self, speech.size(0), decoding_chunk_size, n_steps)
+        state = None
+        for i, c in enumerate(starts):
+            xs = speech[:, c:min(c + window, T)]
+            if lookahead:
+                y, state = enc.forward_chunk_lookahead(xs, state, final=(i == len(starts) - 1))
+            else:
+                y, state = enc.forward_chunk_carry(xs, 0, state)
+            new: List[List[int]] = [[] for _ in range(speech.size(0))]
+            for a in range(0, y.size(1), decoding_chunk_size):      # (the final drain of the look-ahead emits more frames)
+                for b, tk in enumerate(streamer.feed(y[:, a:a + decoding_chunk_size])):
+                    new[b] += tk
+            if on_tokens is not None:
+                on_tokens(i, new)
+        return streamer.results()
+
+    # ---- the reference's runtime step API (transducer.py:474-505), for runtimes that drive their own loop ----
+    def forward_encoder_chunk(self, xs: torch.Tensor, offset: int, required_cache_size: int,
+                              att_cache: torch.Tensor = torch.zeros(0, 0, 0, 0), cnn_cache: torch.Tensor = torch.zeros(0, 0, 0, 0)
+                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.encoder.forward_chunk(xs, offset, required_cache_size, att_cache, cnn_cache)
+
+    def forward_predictor_step(self, xs: torch.Tensor, cache: List[torch.Tensor]) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """B = 1: the reference's fake (1, 1) padding, in the predictor's dtype (bf16 models)."""
+        assert len(cache) == 2
+        padding = torch.zeros(1, 1, dtype=self.predictor.embed.weight.dtype, device=xs.device)
+        return self.predictor.forward_step(xs, padding, cache)
+
+    def forward_joint_step(self, enc_out: torch.Tensor, pred_out: torch.Tensor) -> torch.Tensor:
+        return self.joint(enc_out, pred_out)
+
+    def forward_predictor_init_state(self) -> List[torch.Tensor]:
+        """The zero state of one stream, on the predictor's device and in its dtype."""
+        w = self.predictor.embed.weight
+        return [c.to(w.dtype) for c in self.predictor.init_state(1, device=w.device)]
 
     @torch.no_grad()
     def decode(self, methods: List[str], speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int = 10,
