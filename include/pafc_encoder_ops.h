@@ -321,7 +321,10 @@ size_t pafc_gemm_bf16_f32out_workspace_bytes(long M, int N, int K, int a_split);
  *           statistics and label occupancies in `workspace` for backward.
  * backward: dlogits (B, T, ldg >= V) in the logits' dtype = grad_out[0] * scale * d(sum_b nll[b]) / d logits -- the gradient
  *           through the log-softmax; columns V .. ldg - 1 and rows t >= hlens[b] are written as zeros.  grad_out: one float on
- *           the device.  Same workspace, unmodified since forward. */
+ *           the device.  Same workspace, unmodified since forward.
+ * The lattice runs in fp64 (row statistics and the gradient row in fp32); occupancies are summed in a fixed order, no float
+ * atomics: results are bitwise reproducible.  max_target_len <= 3838 (forward) and V <= 38400 (backward), else
+ * PAFC_ERR_UNSUPPORTED. */
 size_t pafc_ctc_loss_workspace_bytes(int B, int T, int max_target_len);
 int pafc_ctc_loss_forward(int dtype, int B, int T, int V, const void *logits, long ldl, const int32_t *hlens, const int64_t *ys,
                           int ldy, const int32_t *ylens, int max_target_len, int blank, float *nll, void *workspace,

@@ -2634,6 +2634,30 @@ def conv3x3s2_c1_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     return out
 
 
+def conv3x3s2_c1_wgrad(x: torch.Tensor, act: torch.Tensor, dact: torch.Tensor) -> torch.Tensor:
+    """Weight and bias gradient of relu(Conv2d(1, C, 3, 2)) (pafc_conv3x3s2_c1_wgrad_bf16): x (B, T, F) bf16 features, act
+    (B, T1, F1, C) bf16 the forward's ReLU output, dact its incoming gradient.  Returns (10, C) fp32: rows kh * 3 + kw of dW,
+    then db; the partial sums are added in a fixed order."""
+    B, T, Fd = x.shape
+    C = act.shape[-1]
+    L = _bind()
+    if not getattr(L, "_pafc_c1w_bound", False):
+        from ctypes import c_size_t
+        L.pafc_conv3x3s2_c1_wgrad_workspace_bytes.restype = c_size_t
+        L.pafc_conv3x3s2_c1_wgrad_workspace_bytes.argtypes = [c_int, c_int, c_int]
+        _lib._sig(L.pafc_conv3x3s2_c1_wgrad_bf16, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                  c_void_p, c_void_p, c_size_t, c_void_p)
+        L._pafc_c1w_bound = True
+    nbytes = L.pafc_conv3x3s2_c1_wgrad_workspace_bytes(B, T, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty(10, C, dtype=torch.float32, device=x.device)
+    dact = dact.contiguous()
+    rc = L.pafc_conv3x3s2_c1_wgrad_bf16(B, T, Fd, C, _lib.ptr(x), _lib.ptr(act), _lib.ptr(dact), _lib.ptr(out), _lib.ptr(ws),
+                                        nbytes, _lib.stream_of(x))
+    _lib.check(rc, "pafc_conv3x3s2_c1_wgrad_bf16")
+    return out
+
+
 class _Conv1Train(torch.autograd.Function):
     """relu(Conv2d(1, C, 3, 2)(x)) in NHWC for the GPU training step (subsampling.py:201-226, conv[0:2]): forward = the
     inference kernel, backward = pafc_conv3x3s2_c1_wgrad_bf16 (the library runs this layer as im2col + one small GEMM per
@@ -2650,23 +2674,7 @@ class _Conv1Train(torch.autograd.Function):
     @staticmethod
     def backward(ctx, da):
         x, a = ctx.saved_tensors
-        B, T, Fd = x.shape
-        C = a.shape[-1]
-        L = _bind()
-        if not getattr(L, "_pafc_c1w_bound", False):
-            from ctypes import c_size_t
-            L.pafc_conv3x3s2_c1_wgrad_workspace_bytes.restype = c_size_t
-            L.pafc_conv3x3s2_c1_wgrad_workspace_bytes.argtypes = [c_int, c_int, c_int]
-            _lib._sig(L.pafc_conv3x3s2_c1_wgrad_bf16, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                      c_void_p, c_void_p, c_size_t, c_void_p)
-            L._pafc_c1w_bound = True
-        nbytes = L.pafc_conv3x3s2_c1_wgrad_workspace_bytes(B, T, C)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(10, C, dtype=torch.float32, device=x.device)
-        da = da.contiguous()
-        rc = L.pafc_conv3x3s2_c1_wgrad_bf16(B, T, Fd, C, _lib.ptr(x), _lib.ptr(a), _lib.ptr(da), _lib.ptr(out), _lib.ptr(ws),
-                                            nbytes, _lib.stream_of(x))
-        _lib.check(rc, "pafc_conv3x3s2_c1_wgrad_bf16")
+        out = conv3x3s2_c1_wgrad(x, a, da)
         dw = out[:9].t().reshape(ctx.w_shape).to(ctx.w_dtype)
         db = out[9].to(ctx.b_dtype) if ctx.b_dtype is not None else None
         return None, dw, db
