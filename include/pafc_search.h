@@ -32,7 +32,7 @@ int pafc_ctc_greedy(int dtype, int B, int T, int V, const void *scores, const in
 int pafc_log_softmax_rows(int dtype, long rows, int V, const void *x, void *out, pafc_stream_t stream);
 
 /* CTC prefix beam search (ctc_prefix_beam_search, wenet/transformer/search.py:124-248, without context graph and time
- * stamps), one wave per utterance, frames walked on the device.
+ * stamps -- see pafc_ctc_prefix_beam_search_ex for both), one wave per utterance, frames walked on the device.
  * top_logp / top_idx: (B, T, K) the K best log-probabilities and token ids per frame, best first (torch.topk of the CTC
  *   log-probs, as the reference takes them per frame); K <= 16, beam <= 16.  lens: (B) int64 valid frames, or NULL.
  * out_tokens: (B, beam, T) int32, entry (b, n) holds out_len[b][n] ids of the n-th best prefix (best first);
@@ -43,6 +43,29 @@ size_t pafc_ctc_prefix_beam_workspace_bytes(int B, int T, int beam);
 int pafc_ctc_prefix_beam_search(int B, int T, int K, const float *top_logp, const int32_t *top_idx, const int64_t *lens,
                                 int beam, int blank_id, int32_t *out_tokens, int32_t *out_len, double *out_score,
                                 void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+
+/* The same search with the reference's context biasing and token time stamps (the whole of search.py:124-248).
+ * graph: NULL (no biasing) or a host struct of device tables of a ContextGraph (utils/context_graph.py:
+ *   ContextGraph.device_tables), node 0 the root: child_begin (num_nodes + 1) and child_token / child_node (one entry per
+ *   arc) int32, each node's children sorted by token; fail (num_nodes) int32; token_score / node_score / output_score
+ *   (num_nodes) float64.  The prune ranks on score + context bonus; out_score is score + the finalize() bonus
+ *   (-node_score of the survivor's state) -- the order is not revisited after finalize, as in the reference.
+ * out_times: NULL, or (B, beam, T) int32: entry (b, n) holds the frame of every token of the n-th prefix's viterbi path
+ *   (the reference's DecodeResult.times / nbest_times), then -1 up to T.  The list may be shorter than the token list
+ *   where the reference's is.
+ * With graph == NULL and out_times == NULL the results equal pafc_ctc_prefix_beam_search's bit for bit.
+ * workspace: pafc_ctc_prefix_beam_ex_workspace_bytes(B, T, beam) bytes (prefix tries and frame lists). */
+typedef struct pafc_ctc_context_graph {
+    int num_nodes;
+    const int32_t *child_begin, *child_token, *child_node, *fail;
+    const double *token_score, *node_score, *output_score;
+} pafc_ctc_context_graph;
+
+size_t pafc_ctc_prefix_beam_ex_workspace_bytes(int B, int T, int beam);
+int pafc_ctc_prefix_beam_search_ex(int B, int T, int K, const float *top_logp, const int32_t *top_idx,
+                                   const int64_t *lens, int beam, int blank_id, const pafc_ctc_context_graph *graph,
+                                   int32_t *out_tokens, int32_t *out_len, double *out_score, int32_t *out_times,
+                                   void *workspace, size_t workspace_bytes, pafc_stream_t stream);
 
 /* CTC-fused RNN-T prefix beam search (PrefixBeamSearch.prefix_beam_search_decode_batch,
  * wenet/transducer/search/prefix_beam_search.py:428-574): the per-frame candidate walk on the device.  The caller keeps

@@ -2714,35 +2714,56 @@ def conv_sub_train(x: torch.Tensor, c1_weight, c1_bias, c2_weight, c2_bias) -> t
     return _Conv2Train.apply(a, c2_weight, c2_bias)
 
 
+class _CtxGraph(ctypes.Structure):
+    """pafc_ctc_context_graph (include/pafc_search.h)"""
+    _fields_ = [("num_nodes", c_int), ("child_begin", c_void_p), ("child_token", c_void_p), ("child_node", c_void_p),
+                ("fail", c_void_p), ("token_score", c_void_p), ("node_score", c_void_p), ("output_score", c_void_p)]
+
+
 def ctc_prefix_beam(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int,
-                    blank_id: int = 0):
-    """GPU-resident CTC prefix beam search (include/pafc_search.h).  top_logp (B, T, K) float32 / top_idx (B, T, K) =
-    torch.topk of the CTC log-probs.  Returns (tokens (B, beam, T) int32, lengths (B, beam) int32 [-1 = unused],
-    scores (B, beam) float64), best first."""
+                    blank_id: int = 0, graph_tables: Optional[dict] = None, want_times: bool = True):
+    """GPU-resident CTC prefix beam search (include/pafc_search.h: pafc_ctc_prefix_beam_search_ex).  top_logp (B, T, K)
+    float32 / top_idx (B, T, K) = torch.topk of the CTC log-probs.  graph_tables: ContextGraph.device_tables(device) for
+    context biasing, or None.  Returns (tokens (B, beam, T) int32, lengths (B, beam) int32 [-1 = unused],
+    scores (B, beam) float64, times (B, beam, T) int32 [frames of each prefix's tokens, then -1] or None), best first."""
     _lib.require_gpu(top_logp, top_idx, lens)
     from ctypes import c_size_t
     L = _bind()
-    if not getattr(L, "_pafc_beam_bound", False):
+    if not getattr(L, "_pafc_beam_ex_bound", False):
         P, I = c_void_p, c_int
-        _lib._sig(L.pafc_ctc_prefix_beam_workspace_bytes, c_size_t, I, I, I)
-        _lib._sig(L.pafc_ctc_prefix_beam_search, I, I, I, I, P, P, P, I, I, P, P, P, P, c_size_t, P)
-        L._pafc_beam_bound = True
+        _lib._sig(L.pafc_ctc_prefix_beam_ex_workspace_bytes, c_size_t, I, I, I)
+        _lib._sig(L.pafc_ctc_prefix_beam_search_ex, I, I, I, I, P, P, P, I, I, P, P, P, P, P, P, c_size_t, P)
+        L._pafc_beam_ex_bound = True
     if top_logp.dtype != torch.float32 or top_logp.shape != top_idx.shape or top_logp.dim() != 3:
         raise _lib.PafcError("ctc_prefix_beam: top_logp float32 (B, T, K) and top_idx of the same shape")
     B, T, K = top_logp.shape
     idx32 = top_idx.to(torch.int32).contiguous()
     lens64 = None if lens is None else lens.to(torch.int64).contiguous()
     dev = top_logp.device
-    nws = L.pafc_ctc_prefix_beam_workspace_bytes(B, T, beam)
+    graph = None
+    if graph_tables is not None:
+        g = graph_tables
+        for k, dt in (("child_begin", torch.int32), ("child_token", torch.int32), ("child_node", torch.int32),
+                      ("fail", torch.int32), ("token_score", torch.float64), ("node_score", torch.float64),
+                      ("output_score", torch.float64)):
+            if g[k].dtype != dt or g[k].device != dev or not g[k].is_contiguous():
+                raise _lib.PafcError(f"ctc_prefix_beam: graph table {k} must be contiguous {dt} on {dev}")
+        graph = _CtxGraph(int(g["fail"].numel()), *[_lib.ptr(g[k]) for k in ("child_begin", "child_token", "child_node",
+                                                                              "fail", "token_score", "node_score",
+                                                                              "output_score")])
+    nws = L.pafc_ctc_prefix_beam_ex_workspace_bytes(B, T, beam)
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
     tokens = torch.empty(B, beam, T, dtype=torch.int32, device=dev)
     lengths = torch.empty(B, beam, dtype=torch.int32, device=dev)
     scores = torch.empty(B, beam, dtype=torch.float64, device=dev)
-    _lib.check(L.pafc_ctc_prefix_beam_search(B, T, K, _lib.ptr(top_logp), _lib.ptr(idx32), _lib.ptr(lens64), int(beam),
-                                             int(blank_id), _lib.ptr(tokens), _lib.ptr(lengths), _lib.ptr(scores),
-                                             _lib.ptr(ws), nws, _lib.stream_of(top_logp)), "pafc_ctc_prefix_beam_search")
-    return tokens, lengths, scores
-
+    times = torch.empty(B, beam, T, dtype=torch.int32, device=dev) if want_times else None
+    _lib.check(L.pafc_ctc_prefix_beam_search_ex(B, T, K, _lib.ptr(top_logp), _lib.ptr(idx32), _lib.ptr(lens64),
+                                                int(beam), int(blank_id),
+                                                None if graph is None else ctypes.addressof(graph),
+                                                _lib.ptr(tokens), _lib.ptr(lengths), _lib.ptr(scores), _lib.ptr(times),
+                                                _lib.ptr(ws), nws, _lib.stream_of(top_logp)),
+               "pafc_ctc_prefix_beam_search_ex")
+    return tokens, lengths, scores, times
 
 
 class RnntBeamState:

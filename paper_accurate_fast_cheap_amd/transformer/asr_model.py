@@ -53,7 +53,7 @@ class ASRModel(torch.nn.Module):
     def decode(self, methods: List[str], speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int = 10,
                decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0,
                simulate_streaming: bool = False, reverse_weight: float = 0.0, blank_id: int = 0,
-               blank_penalty: float = 0.0, cat_embs: Optional[torch.Tensor] = None, **_ignored
+               blank_penalty: float = 0.0, cat_embs: Optional[torch.Tensor] = None, context_graph=None, **_ignored
                ) -> Dict[str, List[DecodeResult]]:
         assert speech.shape[0] == speech_lengths.shape[0]
         encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
@@ -66,7 +66,7 @@ class ASRModel(torch.nn.Module):
                 results[m] = ctc_greedy_search(ctc_probs, encoder_lens, blank_id)
             elif m == "ctc_prefix_beam_search":
                 from .search import ctc_prefix_beam_search
-                results[m] = ctc_prefix_beam_search(ctc_probs, encoder_lens, beam_size, blank_id=blank_id)
+                results[m] = ctc_prefix_beam_search(ctc_probs, encoder_lens, beam_size, context_graph, blank_id)
             else:
                 raise NotImplementedError(f"decode mode {m!r} is outside the accelerated path")
         return results

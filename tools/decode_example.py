@@ -1,9 +1,10 @@
 """End-to-end decode on the MI355X path, the shape of the reference's recognize.py for this model family:
 waveforms -> HIP fbank -> bidirectional RWKV encoder -> CTC (greedy / prefix beam search on the device) -> SentencePiece
-tokens -> text -> WER report.  Random-init weights (no checkpoint can ship here), so the text is noise: the point is the
+tokens -> text -> WER report, with each token's frame where the search reports one (prefix beam search).  Random-init weights (no checkpoint can ship here), so the text is noise: the point is the
 chain and its interfaces -- pass --checkpoint / --config of a real GigaSpeech model to decode for real.
 
   python tools/decode_example.py [--config conf.yaml --checkpoint model.pt --bpe_model spm.model --units units.txt]
+                                 [--mode ctc_prefix_beam_search --context_list_path hotwords.txt --context_graph_score 3.0]
 """
 import argparse, io, os, sys
 import torch
@@ -25,6 +26,8 @@ def main(argv=None):
     ap.add_argument("--units", default=os.path.join(G, "units.txt"))
     ap.add_argument("--mode", default="ctc_greedy_search", choices=["ctc_greedy_search", "ctc_prefix_beam_search"])
     ap.add_argument("--beam_size", type=int, default=8)
+    ap.add_argument("--context_list_path", default="", help="hotword list, one phrase per line (prefix beam search)")
+    ap.add_argument("--context_graph_score", type=float, default=0.0, help="bonus per matched hotword token")
     args = ap.parse_args(argv)
     dev = torch.device("cuda")
     tok = RevBpeTokenizer(args.bpe_model, args.units, None)
@@ -50,14 +53,21 @@ def main(argv=None):
     batch = torch.zeros(len(feats), int(lens.max()), 80, dtype=torch.bfloat16, device=dev)
     for i, f in enumerate(feats):
         batch[i, :f.shape[0]] = f.to(torch.bfloat16)
+    context_graph = None
+    if args.context_list_path:
+        from paper_accurate_fast_cheap_amd.utils.context_graph import ContextGraph
+        context_graph = ContextGraph(args.context_list_path, tok.symbol_table, args.bpe_model, args.context_graph_score)
     with torch.no_grad():
-        results = model.decode([args.mode], batch, lens, beam_size=args.beam_size)[args.mode]
+        results = model.decode([args.mode], batch, lens, beam_size=args.beam_size,
+                               context_graph=context_graph)[args.mode]
     scorer = WerScorer()
     out = io.StringIO()
     for i, (r, ref) in enumerate(zip(results, refs)):
         text, pieces = tok.detokenize(list(r.tokens))
         al = scorer.add(f"utt{i}", giga_post_process(ref).split(), giga_post_process(text).split())
         out.write(f"utt{i}: {len(r.tokens)} tokens -> {text[:60]!r}   {al.counts.line()}\n")
+        if r.times is not None:    # frame of each token (encoder frames after subsampling)
+            out.write("  frames: " + " ".join(f"{t}:{f}" for t, f in zip(r.tokens, r.times)) + "\n")
     tot = scorer.overall()
     out.write("Overall -> %4.2f %% %s\n" % (tot.wer, tot.line()))
     print(out.getvalue(), end="")
