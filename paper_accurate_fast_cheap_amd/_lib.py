@@ -6,7 +6,7 @@ oracle/ and is test infrastructure; nothing here imports it.)
 """
 import ctypes
 import os
-from ctypes import c_int, c_size_t, c_void_p
+from ctypes import c_float, c_int, c_long, c_size_t, c_ulonglong, c_void_p
 
 import torch
 
@@ -26,11 +26,6 @@ class PafcError(RuntimeError):
 
 
 _lib = None
-
-
-def _sig(fn, restype, *argtypes):
-    fn.restype = restype
-    fn.argtypes = list(argtypes)
 
 
 def lib():
@@ -57,20 +52,131 @@ def lib():
     return _lib
 
 
+# Every prototype of include/*.h: symbol -> (restype, argtypes), grouped by header in header order.  `lib()` applies the
+# whole table once, so a kernel call is a plain call on the CDLL's function attribute.  C types map as int: I, long and
+# int64_t: G, size_t: Z, float: F, unsigned long long and uint64_t: U, any pointer and pafc_stream_t: P (tests/test_abi.py
+# checks the table against the headers).
+P, I, G, Z, F, U = c_void_p, c_int, c_long, c_size_t, c_float, c_ulonglong
+SIGNATURES = {
+    # include/pafc_encoder_ops.h
+    "pafc_dwconv1d_cl": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P]),
+    "pafc_dwconv1d_cl_ex": (I, [I, I, I, I, I, I, I, P, G, P, P, P, I, P, P]),
+    "pafc_dwconv1d_cl_ln_silu": (I, [I, I, I, I, I, I, I, P, G, P, P, P, P, F, P, P, P]),
+    "pafc_dwconv1d_cl_wgrad_workspace_bytes": (Z, [I, I, I, I]),
+    "pafc_dwconv1d_cl_wgrad": (I, [I, I, I, I, I, I, I, P, G, P, P, P, P, Z, P]),
+    "pafc_add_layernorm": (I, [I, I, I, I, P, P, F, P, I, I, P, P, P, P, G, I, I, P, P, P, G, F, P]),
+    "pafc_add_layernorm_ex": (I, [I, I, I, I, I, P, P, F, P, I, I, P, P, P, P, G, I, I, P, P, P, G, F, P, P, P]),
+    "pafc_gemm_bf16_ph_ln": (I, [G, I, I, P, G, P, G, P, P, G, P, G, F, I, I, P, P, I, F, I, P]),
+    "pafc_split_planes": (I, [G, I, P, G, P, G, G, I, P]),
+    "pafc_layernorm_bwd_workspace_bytes": (Z, [G, I]),
+    "pafc_layernorm_bwd": (I, [I, I, G, I, P, P, P, F, P, P, P, Z, P]),
+    "pafc_layernorm_bwd_add": (I, [I, I, G, I, P, P, P, F, P, P, P, P, Z, P]),
+    "pafc_layernorm_silu_fwd": (I, [I, I, G, I, P, P, P, F, P, P]),
+    "pafc_layernorm_silu_bwd": (I, [I, I, G, I, P, P, P, P, F, P, P, P, Z, P]),
+    "pafc_gemm_skinny_bf16": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, P, I, P, F, P, P]),
+    "pafc_gemm_skinny_bf16_ex": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, I, P, I, I, P, F, P, P, P, I,
+        P, P, F, P]),
+    "pafc_decay_lora_skinny_bf16": (I, [G, I, I, P, G, P, P, P, P, G, P]),
+    "pafc_tmix_shift_mix": (I, [I, I, I, I, I, I, P, P, P, P, P]),
+    "pafc_tmix_mix4": (I, [I, I, I, I, I, I, P, P, P, P, P]),
+    "pafc_tmix_lora_mix4_bf16": (I, [I, I, I, I, I, P, P, P, P, P, P]),
+    "pafc_tmix_lora_down_bf16": (I, [I, I, I, I, I, I, P, P, P, P, P]),
+    "pafc_tmix_shift_mix_prev": (I, [I, I, I, I, I, I, P, P, P, P, P, P]),
+    "pafc_tmix_lora_mix4_bf16_prev": (I, [I, I, I, I, I, P, P, P, P, P, P, P]),
+    "pafc_tmix_lora_down_bf16_prev": (I, [I, I, I, I, I, I, P, P, P, P, P, P]),
+    "pafc_decay_lora_bf16": (I, [G, I, I, I, P, P, P, P, P, P]),
+    "pafc_tmix_bwd_workspace_bytes": (Z, [G, I]),
+    "pafc_tmix_shift_mix_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, Z, P]),
+    "pafc_tmix_mix4_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, Z, P]),
+    "pafc_tmix_mix4_bwd_rows": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, Z, P]),
+    "pafc_conv3x3s2_nhwc_bf16": (I, [I, I, I, I, I, P, P, P, P, I, P]),
+    "pafc_conv3x3s2_c1_nhwc_bf16": (I, [I, I, I, I, P, P, P, P, I, P]),
+    "pafc_conv3x3s2_c1_wgrad_workspace_bytes": (Z, [I, I, I]),
+    "pafc_conv3x3s2_c1_wgrad_bf16": (I, [I, I, I, I, P, P, P, P, P, Z, P]),
+    "pafc_conv3x3s2_c1_nhwc_f32split": (I, [I, I, I, I, P, P, P, P, P, I, P]),
+    "pafc_conv3x3s2_c1_nhwc_f32split_ps": (I, [I, I, I, I, P, P, P, P, P, G, I, P]),
+    "pafc_conv3x3s2_nhwc_f32split": (I, [I, I, I, I, I, P, P, P, P, P, P, I, P]),
+    "pafc_gemm_tn_workspace_bytes": (Z, [G, I, I]),
+    "pafc_gemm_tn_bf16": (I, [G, I, I, P, G, P, G, P, P, I, P, Z, P]),
+    "pafc_gemm_tn_batched_workspace_bytes": (Z, [G, I, I, I]),
+    "pafc_gemm_tn_bf16_batched": (I, [G, I, I, I, P, G, G, P, G, G, P, P, I, P, Z, P]),
+    "pafc_gemm_bf16_f32out": (I, [G, I, I, P, G, I, P, G, P, P, G, P, I, G, G, F, I, P, Z, P]),
+    "pafc_gemm_bf16_f32out_pb": (I, [G, I, I, P, G, I, I, P, G, P, P, G, P, I, G, G, F, I, P, Z, P]),
+    "pafc_gemm_bf16_f32out_workspace_bytes": (Z, [G, I, I, I]),
+    "pafc_ctc_loss_workspace_bytes": (Z, [I, I, I]),
+    "pafc_ctc_loss_forward": (I, [I, I, I, I, P, G, P, P, I, P, I, I, P, P, Z, P]),
+    "pafc_ctc_loss_backward": (I, [I, I, I, I, P, G, P, P, I, P, I, I, P, P, F, P, G, P, Z, P]),
+    "pafc_rnnt_joint_loss_workspace_bytes": (Z, [I, I, I, G, G, P, I]),
+    "pafc_rnnt_joint_loss_forward": (I, [I, I, I, I, I, P, G, G, P, G, G, P, P, P, P, P, I, I, G, P, P, Z, P]),
+    "pafc_rnnt_joint_loss_backward": (I, [I, I, I, I, I, P, G, G, P, G, G, P, P, P, P, P, I, I, G, P, G, P, F, I, P, P, P, P,
+        P, Z, P, Z, P]),
+    "pafc_gemm_f32": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, P]),
+    "pafc_mamba2_prep": (I, [I, I, I, I, P, P, G, P, P, P, P, P, P, P, P, P]),
+    "pafc_mamba2_finish": (I, [I, I, I, I, P, P, P, P, G, P, G, P, P, P, F, I, P, P]),
+    "pafc_mamba2_scan_chunk_len": (I, [I, I, I]),
+    "pafc_mamba2_scan_workspace_bytes": (Z, [I, I, I, I]),
+    "pafc_mamba2_scan": (I, [I, I, I, P, G, P, P, P, I, P, Z, P]),
+    "pafc_mamba2_scan_dir": (I, [I, I, I, P, G, P, P, P, I, I, P, Z, P]),
+    "pafc_mamba2_scan_skip_bf16": (I, [I, I, I, P, G, P, P, P, P, I, I, P, Z, P]),
+    "pafc_mamba2_gate_norm": (I, [I, G, I, P, P, G, P, F, P, P]),
+    "pafc_gemm_bf16": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, P]),
+    "pafc_gemm_bf16_glu_half": (I, [G, I, I, I]),
+    "pafc_conv3x3s2_nhwc_bf16_ph": (I, [I, I, I, I, I, P, P, P, P, I, I, P]),
+    "pafc_gemm_bf16_ph": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, I, I, P]),
+    "pafc_gemm_ph_ex": (I, [G, I, I, I, P, G, G, I, P, G, G, P, G, P, I, G, G, P, I, G, G, G, F, I, I, P]),
+    "pafc_gemm_ph_ex2": (I, [G, I, I, I, P, G, G, I, I, P, G, G, P, G, P, I, G, G, P, I, G, G, G, F, I, I, P]),
+    "pafc_conv3x3s2_nhwc_split_ph": (I, [I, I, I, I, I, P, P, P, P, I, I, P]),
+    "pafc_residual_dropout": (I, [I, I, I, G, P, P, P, F, F, U, U, P]),
+    "pafc_silu_dropout": (I, [I, I, G, P, P, P, F, U, U, P]),
+    "pafc_multi_transpose_bf16": (I, [P, I, I, P]),
+    "pafc_multi_cast_bf16": (I, [P, I, I, P]),
+    # include/pafc_fbank.h
+    "pafc_fbank_num_frames": (G, [G]),
+    "pafc_fbank_tables_cols": (I, []),
+    "pafc_fbank_f32": (I, [P, G, P, P, P, P, P, I, P, F, F, P, P]),
+    # include/pafc_search.h
+    "pafc_ctc_greedy": (I, [I, I, I, I, P, P, I, P, P, P, P, P]),
+    "pafc_log_softmax_rows": (I, [I, G, I, P, P, P]),
+    "pafc_ctc_prefix_beam_workspace_bytes": (Z, [I, I, I]),
+    "pafc_ctc_prefix_beam_search": (I, [I, I, I, P, P, P, I, I, P, P, P, P, Z, P]),
+    "pafc_ctc_prefix_beam_ex_workspace_bytes": (Z, [I, I, I]),
+    "pafc_ctc_prefix_beam_search_ex": (I, [I, I, I, P, P, P, I, I, P, P, P, P, P, P, Z, P]),
+    "pafc_rnnt_beam_workspace_bytes": (Z, [I, I, I]),
+    "pafc_rnnt_beam_init": (I, [I, I, I, I, P, Z, P, P, P]),
+    "pafc_rnnt_beam_step": (I, [I, I, I, I, I, P, P, P, P, P, Z, P, P, P]),
+    "pafc_rnnt_beam_finish": (I, [I, I, I, P, Z, P, P, P, P]),
+    "pafc_rnnt_greedy_workspace_bytes": (Z, [P, I, I, I]),
+    "pafc_rnnt_greedy_init": (I, [P, I, I, I, I, P, P, Z, P]),
+    "pafc_rnnt_greedy_step": (I, [P, I, I, I, I, P, P, Z, P, P]),
+    "pafc_rnnt_greedy_finish": (I, [P, I, I, I, P, Z, I, P, P, P, P, P, P]),
+    "pafc_rnnt_greedy_stream_workspace_bytes": (Z, [P, I, I, I]),
+    "pafc_rnnt_greedy_stream_reset": (I, [P, I, I, I, I, P, P, Z, P]),
+    "pafc_rnnt_greedy_stream_feed": (I, [P, I, I, I, I, P, P, Z, P, P]),
+    "pafc_rnnt_greedy_stream_drain": (I, [P, I, I, I, P, Z, I, P, P, P, P, P, P]),
+    # include/pafc_wkv6.h
+    "pafc_abi_version": (I, []),
+    "pafc_selftest_lane_ops": (I, [P, P]),
+    "pafc_wkv6_pick_chunk_len": (I, [I, I, I, I, I]),
+    "pafc_wkv6_fwd_workspace_bytes": (Z, [I, I, I, I, I, I]),
+    "pafc_wkv6_forward_bf16": (I, [I, I, I, I, P, P, P, P, P, P, I, P, Z, P]),
+    "pafc_wkv6_forward_f32": (I, [I, I, I, I, P, P, P, P, P, P, I, P, Z, P]),
+    "pafc_wkv6_forward_state": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, I, I, P, Z, P]),
+    "pafc_wkv6_forward_bidir": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, Z, P]),
+    "pafc_wkv6_forward_bidir_wbias": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, Z, P]),
+    "pafc_wkv6_bwd_workspace_bytes": (Z, [I, I, I, I, I]),
+    "pafc_wkv6_backward": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I, I, P, Z, P]),
+    "pafc_wkv6_backward_state": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, Z, P]),
+
+}
+
+
 def _bind(L):
-    P, I, Z = c_void_p, c_int, c_size_t
-    _sig(L.pafc_abi_version, I)
-    _sig(L.pafc_wkv6_pick_chunk_len, I, I, I, I, I, I)
-    _sig(L.pafc_wkv6_fwd_workspace_bytes, Z, I, I, I, I, I, I)
-    _sig(L.pafc_wkv6_forward_bf16, I, I, I, I, I, P, P, P, P, P, P, I, P, Z, P)
-    _sig(L.pafc_wkv6_forward_f32, I, I, I, I, I, P, P, P, P, P, P, I, P, Z, P)
-    _sig(L.pafc_wkv6_forward_state, I, I, I, I, I, I, P, P, P, P, P, P, P, P, I, I, P, Z, P)
-    _sig(L.pafc_wkv6_forward_bidir, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P, Z, P)
-    _sig(L.pafc_wkv6_forward_bidir_wbias, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, Z, P)
-    _sig(L.pafc_wkv6_bwd_workspace_bytes, Z, I, I, I, I, I)
-    _sig(L.pafc_wkv6_backward, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I, I, P, Z, P)
-    _sig(L.pafc_wkv6_backward_state, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, P, Z, P)
-    _sig(L.pafc_ctc_greedy, I, I, I, I, I, P, P, I, P, P, P, P, P)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise PafcError(f"{name} is declared in include/*.h but missing from {L._name}: rebuild the library") from None
+        fn.restype, fn.argtypes = restype, argtypes
     return L
 
 

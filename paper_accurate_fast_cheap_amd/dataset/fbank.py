@@ -14,22 +14,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from .. import _lib
-from .._lib import c_int, c_void_p
 
 _tables: Dict[Tuple[str, int], dict] = {}
-
-
-def _bind():
-    L = _lib.lib()
-    if getattr(L, "_pafc_fbank_bound", False):
-        return L
-    from ctypes import c_float, c_long
-    P, I = c_void_p, c_int
-    _lib._sig(L.pafc_fbank_num_frames, c_long, c_long)
-    _lib._sig(L.pafc_fbank_tables_cols, I)
-    _lib._sig(L.pafc_fbank_f32, I, P, c_long, P, P, P, P, P, I, P, c_float, c_float, P, P)
-    L._pafc_fbank_bound = True
-    return L
 
 
 def mel_banks(num_bins: int, padded: int = 512, sample_freq: float = 16000.0, low_freq: float = 20.0) -> torch.Tensor:
@@ -55,7 +41,7 @@ def _get_tables(device: torch.device, num_mel_bins: int) -> dict:
     t = _tables.get(key)
     if t is not None:
         return t
-    cols = _bind().pafc_fbank_tables_cols()
+    cols = _lib.lib().pafc_fbank_tables_cols()
     n = torch.arange(400, dtype=torch.float64).unsqueeze(1)
     k = torch.arange(257, dtype=torch.float64).unsqueeze(0)
     ang = 2.0 * math.pi * n * k / 512.0
@@ -86,7 +72,7 @@ def fbank(waveform: torch.Tensor, num_mel_bins: int = 23, frame_length: float = 
     if waveform.dim() != 2:
         raise _lib.PafcError("waveform must be (channels, samples)")
     _lib.require_gpu(waveform)
-    L = _bind()
+    L = _lib.lib()
     wave = waveform[0].to(torch.float32).contiguous()
     S = wave.numel()
     m = L.pafc_fbank_num_frames(S)

@@ -98,20 +98,6 @@ def train_kernels_enabled() -> bool:
     return os.environ.get("PAFC_TRAIN_KERNELS", "1") != "0"
 
 
-def _bind():
-    L = _lib.lib()
-    if getattr(L, "_pafc_ops_bound", False):
-        return L
-    P, I = c_void_p, c_int
-    _lib._sig(L.pafc_dwconv1d_cl, I, I, I, I, I, I, I, I, P, P, P, P, I, P, P)
-    from ctypes import c_long, c_size_t
-    L.pafc_dwconv1d_cl_wgrad_workspace_bytes.restype = c_size_t
-    L.pafc_dwconv1d_cl_wgrad_workspace_bytes.argtypes = [I, I, I, I]
-    _lib._sig(L.pafc_dwconv1d_cl_wgrad, I, I, I, I, I, I, I, I, P, c_long, P, P, P, P, c_size_t, P)
-    L._pafc_ops_bound = True
-    return L
-
-
 def depthwise_conv1d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], left_pad: int,
                         out_len: int, glu: bool = False, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Channels-last depthwise conv1d: x (B, T, C) [or (B, T, 2C) with glu], weight (C, 1, K) -> (B, out_len, C)."""
@@ -124,9 +110,9 @@ def depthwise_conv1d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     if lens is not None and lens.dtype != torch.int32:
         raise _lib.PafcError("lens must be int32")
     y = torch.empty(B, out_len, C, dtype=x.dtype, device=x.device)
-    rc = _bind().pafc_dwconv1d_cl(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x),
-                                  _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), int(glu), _lib.ptr(lens),
-                                  _lib.stream_of(x))
+    rc = _lib.lib().pafc_dwconv1d_cl(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x),
+                                     _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), int(glu), _lib.ptr(lens),
+                                     _lib.stream_of(x))
     _lib.check(rc, "pafc_dwconv1d_cl")
     return y
 
@@ -151,12 +137,7 @@ def depthwise_conv1d_cl_ln_silu(x: torch.Tensor, weight: torch.Tensor, bias: Opt
         raise _lib.PafcError("depthwise_conv1d_cl_ln_silu: x (B, T, C) with unit channel stride")
     if lens is not None and lens.dtype != torch.int32:
         raise _lib.PafcError("lens must be int32")
-    L = _bind()
-    if not getattr(L, "_pafc_dwln_bound", False):
-        from ctypes import c_float, c_long
-        _lib._sig(L.pafc_dwconv1d_cl_ln_silu, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p,
-                  c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p)
-        L._pafc_dwln_bound = True
+    L = _lib.lib()
     y = torch.empty(B, out_len, C, dtype=x.dtype, device=x.device)
     rc = L.pafc_dwconv1d_cl_ln_silu(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x), x.stride(1), _lib.ptr(weight),
                                     _lib.ptr(bias), _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(y), _lib.ptr(lens),
@@ -172,7 +153,7 @@ def depthwise_conv1d_cl_wgrad(x: torch.Tensor, dy: torch.Tensor, K: int, left_pa
     if dy.shape[0] != B or dy.shape[2] != C or dy.dtype != x.dtype or not dy.is_contiguous() or x.stride(2) != 1 \
             or x.stride(0) != T * x.stride(1):
         raise _lib.PafcError("dy must be contiguous (B, T_out, C) in x's dtype; x (B, T, C) with unit channel stride")
-    L = _bind()
+    L = _lib.lib()
     nbytes = L.pafc_dwconv1d_cl_wgrad_workspace_bytes(B, dy.shape[1], C, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     dw = torch.empty(C, 1, K, dtype=torch.float32, device=x.device)
@@ -232,13 +213,6 @@ def layernorm_bwd(x: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, eps: f
     if dy.shape != x.shape or gamma.dtype != x.dtype or gamma.shape != (C,):
         raise _lib.PafcError("layernorm_bwd: dy shaped like x, gamma (C) in x's dtype")
     L = _lib.lib()
-    if not getattr(L, "_pafc_lnb_bound", False):
-        from ctypes import c_float, c_long, c_size_t
-        L.pafc_layernorm_bwd_workspace_bytes.restype = c_size_t
-        L.pafc_layernorm_bwd_workspace_bytes.argtypes = [c_long, c_int]
-        _lib._sig(L.pafc_layernorm_bwd_add, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
-                  c_void_p, c_void_p, c_size_t, c_void_p)
-        L._pafc_lnb_bound = True
     nbytes = L.pafc_layernorm_bwd_workspace_bytes(rows, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     dx = torch.empty_like(x)
@@ -288,14 +262,6 @@ class _LnSiluTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
         L = _lib.lib()
-        if not getattr(L, "_pafc_lns_bound", False):
-            from ctypes import c_float, c_long, c_size_t
-            _lib._sig(L.pafc_layernorm_silu_fwd, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p)
-            _lib._sig(L.pafc_layernorm_silu_bwd, c_int, c_int, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
-                      c_void_p, c_void_p, c_size_t, c_void_p)
-            L.pafc_layernorm_bwd_workspace_bytes.restype = c_size_t
-            L.pafc_layernorm_bwd_workspace_bytes.argtypes = [c_long, c_int]
-            L._pafc_lns_bound = True
         C = x.shape[-1]
         rows = x.numel() // C
         g, b = weight.detach().contiguous(), bias.detach().contiguous()
@@ -389,13 +355,6 @@ def gemm_tn(dy: torch.Tensor, x: torch.Tensor, out_dtype: torch.dtype = torch.fl
             or x.stride(-1) != 1 or out_dtype not in (torch.float32, torch.bfloat16) or (batched and x.shape[0] != Z)):
         raise _lib.PafcError("gemm_tn: dy (R, M) and x (R, N) bf16 with unit column stride (or both with a leading batch); fp32 or bf16 output")
     L = _lib.lib()
-    if not getattr(L, "_pafc_tn_bound", False):
-        from ctypes import c_long, c_size_t
-        L.pafc_gemm_tn_batched_workspace_bytes.restype = c_size_t
-        L.pafc_gemm_tn_batched_workspace_bytes.argtypes = [c_long, c_int, c_int, c_int]
-        _lib._sig(L.pafc_gemm_tn_bf16_batched, c_int, c_long, c_int, c_int, c_int, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
-                  c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p)
-        L._pafc_tn_bound = True
     nbytes = L.pafc_gemm_tn_batched_workspace_bytes(R, M, N, Z)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
     dw = torch.empty((Z, M, N) if batched else (M, N), dtype=out_dtype, device=dy.device)
@@ -428,24 +387,12 @@ def _next_dropout_stream(device=None):
         return int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, _dropout_calls
 
 
-def _bind_train_elementwise():
-    L = _bind()
-    if not getattr(L, "_pafc_te_bound", False):
-        from ctypes import c_float, c_long, c_ulonglong
-        _lib._sig(L.pafc_residual_dropout, c_int, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                  c_ulonglong, c_ulonglong, c_void_p)         # (the first entry is the return type)
-        _lib._sig(L.pafc_silu_dropout, c_int, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p, c_float, c_ulonglong, c_ulonglong,
-                  c_void_p)
-        L._pafc_te_bound = True
-    return L
-
-
 class _ResidualDropout(torch.autograd.Function):
     """out = x + scale * dropout(y, p): one kernel; backward dx = dout (no kernel), dy = one kernel, mask recomputed."""
 
     @staticmethod
     def forward(ctx, x, y, scale, p):
-        L = _bind_train_elementwise()
+        L = _lib.lib()
         x, y = x.contiguous(), y.contiguous()
         seed, off = _next_dropout_stream(x.device) if p > 0 else (0, 0)
         out = torch.empty_like(x)
@@ -459,7 +406,7 @@ class _ResidualDropout(torch.autograd.Function):
         scale, p, seed, off, ydt = ctx.meta
         dy = None
         if ctx.needs_input_grad[1]:
-            L = _bind_train_elementwise()
+            L = _lib.lib()
             g = g.contiguous()
             dy = torch.empty(g.shape, dtype=ydt, device=g.device)
             _lib.check(L.pafc_residual_dropout(1, _lib.dtype_code(g.dtype), _lib.dtype_code(ydt), g.numel(), _lib.ptr(g), _lib.ptr(None),
@@ -472,7 +419,7 @@ class _SiluDropout(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, p):
-        L = _bind_train_elementwise()
+        L = _lib.lib()
         h = h.contiguous()
         seed, off = _next_dropout_stream(h.device) if p > 0 else (0, 0)
         out = torch.empty_like(h)
@@ -486,7 +433,7 @@ class _SiluDropout(torch.autograd.Function):
     def backward(ctx, g):
         (h,) = ctx.saved_tensors
         p, seed, off = ctx.meta
-        L = _bind_train_elementwise()
+        L = _lib.lib()
         g = g.contiguous()
         dh = torch.empty_like(h)
         _lib.check(L.pafc_silu_dropout(1, _lib.dtype_code(h.dtype), h.numel(), _lib.ptr(h), _lib.ptr(g), _lib.ptr(dh), p, seed, off,
@@ -621,10 +568,7 @@ def _refresh_transposed_shadows() -> None:
         return
     if _tr_table is None:
         _tr_table = {}
-    L = _bind()
-    if not getattr(L, "_pafc_mtr_bound", False):
-        _lib._sig(L.pafc_multi_transpose_bf16, c_int, c_void_p, c_int, c_int, c_void_p)
-        L._pafc_mtr_bound = True
+    L = _lib.lib()
     for dev, live in by_dev.items():
         sig = tuple((p.data_ptr(), sh.data_ptr(), p.dtype) for p, sh in live)
         ent = _tr_table.get(dev)
@@ -684,10 +628,7 @@ def _multi_cast(pairs) -> None:
             torch._foreach_copy_([sh for _, sh in rest], [p.detach() for p, _ in rest])
     if not by_dev:
         return
-    L = _bind()
-    if not getattr(L, "_pafc_mcast_bound", False):
-        _lib._sig(L.pafc_multi_cast_bf16, c_int, c_void_p, c_int, c_int, c_void_p)
-        L._pafc_mcast_bound = True
+    L = _lib.lib()
     for dev, live in by_dev.items():
         sig = tuple((p.data_ptr(), sh.data_ptr(), p.dtype, p.numel()) for p, sh in live)
         ent = _cast_table.get(dev)
@@ -1049,7 +990,7 @@ class _CtcHeadLoss(torch.autograd.Function):
         yl = ylens.to(torch.int32).contiguous()
         ysc = ys.to(torch.int64).contiguous()
         Lmax = ysc.shape[1]
-        L = _bind_ctc_loss()
+        L = _lib.lib()
         nbytes = L.pafc_ctc_loss_workspace_bytes(B, T, Lmax)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         nll = torch.empty(B, dtype=torch.float32, device=x.device)
@@ -1066,7 +1007,7 @@ class _CtcHeadLoss(torch.autograd.Function):
         xb, wb, logits, ws, nll, hl, ysc, yl = ctx.saved_tensors
         B, T, C, V, Vp, Lmax, blank = ctx.dims
         M = B * T
-        L = _bind_ctc_loss()
+        L = _lib.lib()
         dl = torch.empty((M, Vp), dtype=torch.bfloat16, device=xb.device)
         gf = g.detach().to(torch.float32).reshape(1).contiguous()
         _lib.check(L.pafc_ctc_loss_backward(_lib.PAFC_BF16, B, T, V, _lib.ptr(logits), Vp, _lib.ptr(hl), _lib.ptr(ysc), Lmax, _lib.ptr(yl),
@@ -1091,16 +1032,8 @@ class _CtcHeadLoss(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
-def _bind_ctc_loss():
-    L = _bind2()
-    if not getattr(L, "_pafc_ctcloss_bound", False):
-        from ctypes import c_float, c_long, c_size_t
-        P, I, G, Z = c_void_p, c_int, c_long, c_size_t
-        _lib._sig(L.pafc_ctc_loss_workspace_bytes, Z, I, I, I)
-        _lib._sig(L.pafc_ctc_loss_forward, I, I, I, I, I, P, G, P, P, I, P, I, I, P, P, Z, P)
-        _lib._sig(L.pafc_ctc_loss_backward, I, I, I, I, I, P, G, P, P, I, P, I, I, P, P, c_float, P, G, P, Z, P)
-        L._pafc_ctcloss_bound = True
-    return L
+# tests/test_train_loss_kernels_gpu.py calls the CTC loss kernels directly through this name; the signatures are _lib's.
+_bind_ctc_loss = _lib.lib
 
 
 def ctc_head_loss_eligible(x: torch.Tensor, weight: torch.Tensor, ys: torch.Tensor) -> bool:
@@ -1157,7 +1090,7 @@ class _RnntJointLoss(torch.autograd.Function):
         R = row_off[-1]
         Vp = (V + 63) // 64 * 64
         slab_rows = max(max(t * (u + 1) for t, u in zip(Ts, Us)), min(R, RNNT_SLAB_BYTES // (2 * Vp + 4 * J)))
-        L = _bind_rnnt_loss()
+        L = _lib.lib()
         nbytes = L.pafc_rnnt_joint_loss_workspace_bytes(B, J, V, R, 0, None, 0)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
         nll = torch.empty(B, dtype=torch.float32, device=E.device)
@@ -1175,7 +1108,7 @@ class _RnntJointLoss(torch.autograd.Function):
         Eb, Pb, wb, bb, ws, hl, yl, ysc = ctx.saved_tensors
         B, T, Up1, J, V, ldy, blank, R, row_off, slab_rows = ctx.plan
         e_dt, p_dt, w_dt, b_dt = ctx.dtypes
-        L = _bind_rnnt_loss()
+        L = _lib.lib()
         off = (ctypes.c_int64 * (B + 1))(*row_off)
         sbytes = L.pafc_rnnt_joint_loss_workspace_bytes(B, J, V, R, slab_rows, off, 1)
         if sbytes == 0:
@@ -1193,19 +1126,6 @@ class _RnntJointLoss(torch.autograd.Function):
                                                    _lib.ptr(db), _lib.ptr(ws), ws.numel(), _lib.ptr(scratch), sbytes,
                                                    _lib.stream_of(Eb)), "pafc_rnnt_joint_loss_backward")
         return (dE.to(e_dt), dP.to(p_dt), dW.to(w_dt), None if db is None else db.to(b_dt), None, None, None, None)
-
-
-def _bind_rnnt_loss():
-    L = _lib.lib()
-    if not getattr(L, "_pafc_rnntloss_bound", False):
-        from ctypes import c_float, c_long, c_size_t
-        P, I, G, Z = c_void_p, c_int, c_long, c_size_t
-        _lib._sig(L.pafc_rnnt_joint_loss_workspace_bytes, Z, I, I, I, G, G, P, I)
-        _lib._sig(L.pafc_rnnt_joint_loss_forward, I, I, I, I, I, I, P, G, G, P, G, G, P, P, P, P, P, I, I, G, P, P, Z, P)
-        _lib._sig(L.pafc_rnnt_joint_loss_backward, I, I, I, I, I, I, P, G, G, P, G, G, P, P, P, P, P, I, I, G, P, G, P, c_float, I, P,
-                  P, P, P, P, Z, P, Z, P)
-        L._pafc_rnntloss_bound = True
-    return L
 
 
 def rnnt_joint_loss_unmet(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: torch.Tensor) -> Optional[str]:
@@ -1257,19 +1177,6 @@ class _GreedyNet(ctypes.Structure):
                 ("join_dim", c_int), ("vocab", c_int), ("embed_rows", c_int), ("embed", c_void_p), ("w_ih", _PP), ("w_hh", _PP),
                 ("b_ih", _PP), ("b_hh", _PP), ("proj_w", c_void_p), ("proj_b", c_void_p), ("pred_ffn_w", c_void_p),
                 ("pred_ffn_b", c_void_p), ("out_w", c_void_p), ("out_b", c_void_p)]
-
-
-def _bind_rnnt_greedy():
-    L = _lib.lib()
-    if not getattr(L, "_pafc_rnntgreedy_bound", False):
-        from ctypes import c_size_t
-        P, I, Z = c_void_p, c_int, c_size_t
-        _lib._sig(L.pafc_rnnt_greedy_workspace_bytes, Z, P, I, I, I)
-        _lib._sig(L.pafc_rnnt_greedy_init, I, P, I, I, I, I, P, P, Z, P)
-        _lib._sig(L.pafc_rnnt_greedy_step, I, P, I, I, I, I, P, P, Z, P, P)
-        _lib._sig(L.pafc_rnnt_greedy_finish, I, P, I, I, I, P, Z, I, P, P, P, P, P, P)
-        L._pafc_rnntgreedy_bound = True
-    return L
 
 
 def _greedy_net(predictor, joint):
@@ -1375,7 +1282,7 @@ def rnnt_greedy_search(predictor, joint, encoder_out: torch.Tensor, encoder_out_
     lens = encoder_out_lens.detach().to(device=dev, dtype=torch.int64).contiguous()
     if lens.shape != (B,):
         raise _lib.PafcError("rnnt_greedy_search: encoder_out_lens must be (B,)")
-    L = _bind_rnnt_greedy()
+    L = _lib.lib()
     net, keep = _greedy_net(predictor, joint)
     pnet = ctypes.byref(net)
     nbytes = L.pafc_rnnt_greedy_workspace_bytes(pnet, B, T, n_steps)
@@ -1412,19 +1319,6 @@ def rnnt_greedy_search(predictor, joint, encoder_out: torch.Tensor, encoder_out_
     t_h = h[B * 12:B * 12 + B * ld * 4].view(torch.int32).view(B, ld)
     f_h = h[B * 12 + B * ld * 4:].view(torch.int32).view(B, ld)
     return ([t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)], s_h)
-
-
-def _bind_rnnt_greedy_stream():
-    L = _bind_rnnt_greedy()
-    if not getattr(L, "_pafc_rnntgreedy_stream_bound", False):
-        from ctypes import c_size_t
-        P, I, Z = c_void_p, c_int, c_size_t
-        _lib._sig(L.pafc_rnnt_greedy_stream_workspace_bytes, Z, P, I, I, I)
-        _lib._sig(L.pafc_rnnt_greedy_stream_reset, I, P, I, I, I, I, P, P, Z, P)
-        _lib._sig(L.pafc_rnnt_greedy_stream_feed, I, P, I, I, I, I, P, P, Z, P, P)
-        _lib._sig(L.pafc_rnnt_greedy_stream_drain, I, P, I, I, I, P, Z, I, P, P, P, P, P, P)
-        L._pafc_rnntgreedy_stream_bound = True
-    return L
 
 
 def rnnt_greedy_stream_unmet(predictor, joint, B: int, Tmax: int, D: int, device, n_steps: int = 64) -> Optional[str]:
@@ -1471,7 +1365,7 @@ class RnntGreedyStream:
         self._w = ef.weight.detach().contiguous()
         self._b = None if ef.bias is None else ef.bias.detach().contiguous()
         J = joint.ffn_out.in_features
-        self._L = _bind_rnnt_greedy_stream()
+        self._L = _lib.lib()
         self._net, self._keep = _greedy_net(predictor, joint)
         self._pnet = ctypes.byref(self._net)
         self._nbytes = self._L.pafc_rnnt_greedy_stream_workspace_bytes(self._pnet, B, Tmax, n_steps)
@@ -1603,25 +1497,6 @@ class RnntGreedyStream:
         return list(self._score)
 
 
-def _bind2():
-    L = _bind()
-    if getattr(L, "_pafc_glue_bound", False):
-        return L
-    from ctypes import c_float, c_long
-    P, I = c_void_p, c_int
-    _lib._sig(L.pafc_add_layernorm, I, I, I, I, I, P, P, c_float, P, I, I, P, P, P, P, c_long, I, I, P, P, P, c_long,
-              c_float, P)
-    # (first entry = return type; the argument lists are checked against include/*.h by tests/test_abi.py)
-    _lib._sig(L.pafc_tmix_shift_mix, I, I, I, I, I, I, I, P, P, P, P, P)
-    _lib._sig(L.pafc_tmix_mix4, I, I, I, I, I, I, I, P, P, P, P, P)
-    _lib._sig(L.pafc_tmix_lora_mix4_bf16, I, I, I, I, I, I, P, P, P, P, P, P)
-    _lib._sig(L.pafc_tmix_shift_mix_prev, I, I, I, I, I, I, I, P, P, P, P, P, P)
-    _lib._sig(L.pafc_tmix_lora_mix4_bf16_prev, I, I, I, I, I, I, P, P, P, P, P, P, P)
-    _lib._sig(L.pafc_tmix_lora_down_bf16_prev, I, I, I, I, I, I, I, P, P, P, P, P, P)
-    L._pafc_glue_bound = True
-    return L
-
-
 PAFC_SPLIT_BF16 = 2      # output form: an fp32 value as bf16 planes [hi | lo] (include/pafc_wkv6.h)
 
 
@@ -1660,13 +1535,7 @@ def add_layernorm(x: torch.Tensor, y: Optional[torch.Tensor], alpha: float, gamm
     o2 = None
     if gamma2 is not None:
         o2 = planes() if s2 else torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    L = _bind2()
-    if not getattr(L, "_pafc_lnex_bound", False):
-        from ctypes import c_float, c_long
-        P, I = c_void_p, c_int
-        _lib._sig(L.pafc_add_layernorm_ex, I, I, I, I, I, I, P, P, c_float, P, I, I, P, P, P, P, c_long, I, I, P, P, P, c_long,
-                  c_float, P, P, P)
-        L._pafc_lnex_bound = True
+    L = _lib.lib()
     code = _lib.dtype_code(out_dtype)
     rc = L.pafc_add_layernorm_ex(
         _lib.dtype_code(x.dtype), PAFC_SPLIT_BF16 if split1 else code, PAFC_SPLIT_BF16 if s2 else code, rows, C, _lib.ptr(x),
@@ -1695,12 +1564,7 @@ def gemm_bf16_ln(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
         raise _lib.PafcError("gemm_bf16_ln: stats is a contiguous float32 (M, 8, 2) buffer")
     if out is None:
         out = torch.empty((M, No), dtype=a.dtype, device=a.device)
-    L = _bind2()
-    if not getattr(L, "_pafc_gemmln_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_gemm_bf16_ph_ln, I, G, I, I, P, G, P, G, P, P, G, P, G, c_float, I, I, P, P, I, c_float, I, P)
-        L._pafc_gemmln_bound = True
+    L = _lib.lib()
     from .profiling import op_timer
     with op_timer("gemm_%dx%d" % (K, N), sample=12, flops=2.0 * M * N * K):
         rc = L.pafc_gemm_bf16_ph_ln(M, N, K, _lib.ptr(a), a.stride(0), _lib.ptr(w), w.stride(0), _lib.ptr(bias), _lib.ptr(residual),
@@ -1721,11 +1585,7 @@ def split_planes(x: torch.Tensor, triple: bool = False) -> torch.Tensor:
     K = x.shape[-1]
     rows = x.numel() // K
     out = torch.empty(x.shape[:-1] + ((3 if triple else 2) * K,), dtype=torch.bfloat16, device=x.device)
-    L = _bind2()
-    if not getattr(L, "_pafc_split_planes_bound", False):
-        from ctypes import c_long
-        _lib._sig(L.pafc_split_planes, c_int, c_long, c_int, c_void_p, c_long, c_void_p, c_long, c_long, c_int, c_void_p)
-        L._pafc_split_planes_bound = True
+    L = _lib.lib()
     _lib.check(L.pafc_split_planes(rows, K, _lib.ptr(x), K, _lib.ptr(out), out.shape[-1], K, int(triple), _lib.stream_of(x)),
                "pafc_split_planes")
     return out
@@ -1780,15 +1640,7 @@ def gemm_ph_ex(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
             raise _lib.PafcError("gemm_ph_ex: residual (M, N) in the output dtype (bf16 / fp32), not with planes")
     if bias is not None and (bias.dtype != (torch.bfloat16 if ok == 0 else torch.float32) or bias.numel() != N):
         raise _lib.PafcError("gemm_ph_ex: bias (N) bf16 for a bf16 output, fp32 otherwise")
-    L = _bind2()
-    if not getattr(L, "_pafc_gemmex_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_gemm_ph_ex2, I, G, I, I, I, P, G, G, I, I, P, G, G, P, G, P, I, G, G, P, I, G, G, G, c_float, I, I, P)
-        from ctypes import c_size_t
-        _lib._sig(L.pafc_gemm_bf16_f32out_pb, I, G, I, I, P, G, I, I, P, G, P, P, G, P, I, G, G, c_float, I, P, c_size_t, P)
-        _lib._sig(L.pafc_gemm_bf16_f32out_workspace_bytes, c_size_t, G, I, I, I)
-        L._pafc_gemmex_bound = True
+    L = _lib.lib()
     from .profiling import op_timer
     pb_ok = not a_plane_block or (a_split and a_plane_block >= 64 and a_plane_block & (a_plane_block - 1) == 0 and K % a_plane_block == 0)
     if (M <= _SPLIT_SMALL_MAX_ROWS and M * N <= _SPLIT_SMALL_MAX_OUT and ok != 0 and act in ("none", "silu", "tanh", "relu")
@@ -1837,8 +1689,8 @@ def tmix_shift_mix(x: torch.Tensor, maa_x0: torch.Tensor, maa_x1: Optional[torch
     B, T, C = x.shape
     ndir = 2 if maa_x1 is not None else 1
     out = torch.empty((ndir, B, T, C), dtype=x.dtype, device=x.device)
-    rc = _bind2().pafc_tmix_shift_mix_prev(_lib.dtype_code(x.dtype), B, T, C, ndir, int(reverse0), _lib.ptr(x),
-                                           _lib.ptr(maa_x0), _lib.ptr(maa_x1), _lib.ptr(prev), _lib.ptr(out), _lib.stream_of(x))
+    rc = _lib.lib().pafc_tmix_shift_mix_prev(_lib.dtype_code(x.dtype), B, T, C, ndir, int(reverse0), _lib.ptr(x),
+                                             _lib.ptr(maa_x0), _lib.ptr(maa_x1), _lib.ptr(prev), _lib.ptr(out), _lib.stream_of(x))
     _lib.check(rc, "pafc_tmix_shift_mix")
     return out
 
@@ -1851,24 +1703,10 @@ def tmix_mix4(x: torch.Tensor, m: torch.Tensor, maa: torch.Tensor, reverse0: boo
     if m.dtype != x.dtype or maa.dtype != x.dtype:
         raise _lib.PafcError("tmix_mix4: x, m and maa must share one dtype")
     z = torch.empty((4, ndir, B * T, C), dtype=x.dtype, device=x.device)
-    rc = _bind2().pafc_tmix_mix4(_lib.dtype_code(x.dtype), B, T, C, ndir, int(reverse0), _lib.ptr(x), _lib.ptr(m),
-                                 _lib.ptr(maa), _lib.ptr(z), _lib.stream_of(x))
+    rc = _lib.lib().pafc_tmix_mix4(_lib.dtype_code(x.dtype), B, T, C, ndir, int(reverse0), _lib.ptr(x), _lib.ptr(m),
+                                   _lib.ptr(maa), _lib.ptr(z), _lib.stream_of(x))
     _lib.check(rc, "pafc_tmix_mix4")
     return z
-
-
-def _bind_tmix_bwd():
-    L = _bind2()
-    if not getattr(L, "_pafc_tmixbwd_bound", False):
-        from ctypes import c_long, c_size_t
-        P, I = c_void_p, c_int
-        L.pafc_tmix_bwd_workspace_bytes.restype = c_size_t
-        L.pafc_tmix_bwd_workspace_bytes.argtypes = [c_long, c_int]
-        _lib._sig(L.pafc_tmix_shift_mix_bwd, I, I, I, I, I, I, P, P, P, P, P, P, c_size_t, P)
-        _lib._sig(L.pafc_tmix_mix4_bwd, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P)
-        _lib._sig(L.pafc_tmix_mix4_bwd_rows, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P)
-        L._pafc_tmixbwd_bound = True
-    return L
 
 
 class _ShiftMixTrain(torch.autograd.Function):
@@ -1886,7 +1724,7 @@ class _ShiftMixTrain(torch.autograd.Function):
     def backward(ctx, dxxx):
         x, mx = ctx.saved_tensors
         B, T, C = x.shape
-        L = _bind_tmix_bwd()
+        L = _lib.lib()
         nbytes = L.pafc_tmix_bwd_workspace_bytes(B * T, C)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         dx = torch.empty_like(x)
@@ -1918,7 +1756,7 @@ class _Mix4Train(torch.autograd.Function):
         x, mm, a4 = ctx.saved_tensors
         B, T, C = x.shape
         dz = [(torch.zeros_like(x) if g is None else g.contiguous()) for g in dz]
-        L = _bind_tmix_bwd()
+        L = _lib.lib()
         nbytes = L.pafc_tmix_bwd_workspace_bytes(B * T, C)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         dx = torch.empty_like(x)
@@ -1979,7 +1817,7 @@ class _LoraMix4Train(torch.autograd.Function):
         B, T, C = x.shape
         M, R = B * T, w2b.shape[1]
         dz = [(torch.zeros_like(x) if g is None else g.contiguous()) for g in dz]
-        L = _bind_tmix_bwd()
+        L = _lib.lib()
         nbytes = L.pafc_tmix_bwd_workspace_bytes(M, C)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         dx = torch.empty_like(x)
@@ -2035,6 +1873,42 @@ def mix4_train(x: torch.Tensor, m: torch.Tensor, maa4: torch.Tensor, reverse: bo
     return _Mix4Train.apply(x.contiguous(), m, maa4, reverse)
 
 
+def _gemm_operands(op: str, dtype: torch.dtype, a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
+                   residual: Optional[torch.Tensor], out: Optional[torch.Tensor], act: str):
+    """The operand checks of the dense GEMM front ends (gemm_f32, gemm_bf16, gemm_skinny, gemm_bf16_ph): a (M, K) x w (N, K), or
+    both with a leading batch Z, in `dtype` with unit stride in the last dimension; bias (N) or (Z, N); residual / out (M, N_out)
+    per batch entry, N_out = N / 2 for act "glu".  Allocates `out` when it is None.  Returns (Z, M, N, K, out, the 18 leading
+    arguments of the kernels: M, N, K, Z, then pointer, row stride and batch stride of a, w, residual and out, and of bias
+    pointer and batch stride)."""
+    _lib.require_gpu(bias)
+    for t in (a, w, residual, out):
+        if t is not None and (not t.is_cuda or t.dtype != dtype or t.stride(-1) != 1):
+            raise _lib.PafcError(f"{op}: {_DT_NAMES[dtype]} GPU tensors with unit stride in the last dimension")
+    batched = a.dim() == 3
+    Z = a.shape[0] if batched else 1
+    M, K = a.shape[-2], a.shape[-1]
+    N = w.shape[-2]
+    if w.shape[-1] != K or (batched and (w.dim() != 3 or w.shape[0] != Z)) or (not batched and (a.dim() != 2 or w.dim() != 2)):
+        raise _lib.PafcError(f"{op}: a (M, K) x w (N, K), or both with a leading batch")
+    No = N // 2 if act == "glu" else N
+    shape = (Z, M, No) if batched else (M, No)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=a.device)
+    for t in (residual, out):
+        if t is not None and tuple(t.shape) != shape:
+            raise _lib.PafcError(f"{op}: residual / out must be (M, N) per batch entry")
+    if bias is not None and (bias.dtype != dtype or bias.shape[-1] != N):
+        raise _lib.PafcError(f"{op}: bias must be (N) or (Z, N) {_DT_NAMES[dtype]}")
+    bs = lambda t: t.stride(0) if batched and t is not None else 0
+    return Z, M, N, K, out, (M, N, K, Z, _lib.ptr(a), a.stride(-2), bs(a), _lib.ptr(w), w.stride(-2), bs(w), _lib.ptr(bias),
+                             bias.stride(0) if (bias is not None and bias.dim() == 2) else 0, _lib.ptr(residual),
+                             residual.stride(-2) if residual is not None else 0, bs(residual), _lib.ptr(out), out.stride(-2),
+                             bs(out))
+
+
+_DT_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16"}
+
+
 def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: str = "none", alpha: float = 1.0,
              residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Hand-written fp32 GEMM with a fused epilogue on the fp32 matrix cores (include/pafc_encoder_ops.h: pafc_gemm_f32; exact
@@ -2042,39 +1916,12 @@ def gemm_f32(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = No
     nn.Linear layout; bias (N) or (Z, N); residual / out (M, N) or (Z, M, N), `out` may be `residual`.  Rows and batch entries
     may be strided views (unit stride in the last dimension; K and the strides of a and w multiples of 4).  act: none / silu /
     tanh / relu.  No workspace, no plan objects: safe to issue from several streams at once."""
-    _lib.require_gpu(bias)
-    for t in (a, w, bias, residual, out):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.stride(-1) != 1):
-            raise _lib.PafcError("gemm_f32: fp32 GPU tensors with unit stride in the last dimension")
-    L = _bind2()
-    if not getattr(L, "_pafc_gemmf32_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_gemm_f32, I, G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, c_float, I, P)
-        L._pafc_gemmf32_bound = True
-    batched = a.dim() == 3
-    Z = a.shape[0] if batched else 1
-    M, K = a.shape[-2], a.shape[-1]
-    N = w.shape[-2]
-    if w.shape[-1] != K or (batched and (w.dim() != 3 or w.shape[0] != Z)) or (not batched and (a.dim() != 2 or w.dim() != 2)):
-        raise _lib.PafcError("gemm_f32: a (M, K) x w (N, K), or both with a leading batch")
     if act not in ("none", "silu", "tanh", "relu"):
         raise _lib.PafcError("gemm_f32: act is none / silu / tanh / relu")
-    if out is None:
-        out = torch.empty((Z, M, N) if batched else (M, N), dtype=a.dtype, device=a.device)
-    for t in (residual, out):
-        if t is not None and tuple(t.shape) != ((Z, M, N) if batched else (M, N)):
-            raise _lib.PafcError("gemm_f32: residual / out must be (M, N) per batch entry")
-    if bias is not None and bias.shape[-1] != N:
-        raise _lib.PafcError("gemm_f32: bias must be (N) or (Z, N)")
-    sb = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    bs = lambda t: t.stride(0) if batched else 0
+    Z, M, N, K, out, args = _gemm_operands("gemm_f32", torch.float32, a, w, bias, residual, out, act)
     from .profiling import op_timer
-    with op_timer("gemmf32_%dx%d%s" % (K, N, "x%d" % Z if batched else ""), sample=12, flops=2.0 * Z * M * N * K):
-        rc = L.pafc_gemm_f32(M, N, K, Z, _lib.ptr(a), a.stride(-2), bs(a), _lib.ptr(w), w.stride(-2), bs(w),
-                             _lib.ptr(bias), sb, _lib.ptr(residual), residual.stride(-2) if residual is not None else 0,
-                             bs(residual) if residual is not None else 0, _lib.ptr(out), out.stride(-2), bs(out),
-                             float(alpha), _ACTS[act], _lib.stream_of(a))
+    with op_timer("gemmf32_%dx%d%s" % (K, N, "x%d" % Z if a.dim() == 3 else ""), sample=12, flops=2.0 * Z * M * N * K):
+        rc = _lib.lib().pafc_gemm_f32(*args, float(alpha), _ACTS[act], _lib.stream_of(a))
     _lib.check(rc, "pafc_gemm_f32")
     return out
 
@@ -2245,8 +2092,8 @@ def tmix_lora_mix4(x: torch.Tensor, t: torch.Tensor, w2t: torch.Tensor, maa: tor
     if x.dtype != torch.bfloat16 or t.shape != (ndir, B * T, 128) or w2t.shape != (ndir, 4, C, 32):
         raise _lib.PafcError("tmix_lora_mix4: bf16 only, t (ndir, B*T, 128), w2t (ndir, 4, C, 32)")
     z = torch.empty((4, ndir, B * T, C), dtype=x.dtype, device=x.device)
-    rc = _bind2().pafc_tmix_lora_mix4_bf16_prev(B, T, C, ndir, int(reverse0), _lib.ptr(x), _lib.ptr(t), _lib.ptr(w2t),
-                                                _lib.ptr(maa), _lib.ptr(prev), _lib.ptr(z), _lib.stream_of(x))
+    rc = _lib.lib().pafc_tmix_lora_mix4_bf16_prev(B, T, C, ndir, int(reverse0), _lib.ptr(x), _lib.ptr(t), _lib.ptr(w2t),
+                                                  _lib.ptr(maa), _lib.ptr(prev), _lib.ptr(z), _lib.stream_of(x))
     _lib.check(rc, "pafc_tmix_lora_mix4_bf16")
     return z
 
@@ -2264,7 +2111,7 @@ def tmix_lora_down(x: torch.Tensor, maa_x: torch.Tensor, w1n: torch.Tensor, reve
     a GEMM with the same roundings."""
     _lib.require_gpu(x, maa_x, w1n, prev)
     _check_prev(prev, x)
-    L = _bind2()
+    L = _lib.lib()
     B, T, C = x.shape
     ndir, N = w1n.shape[0], w1n.shape[1]
     if x.dtype != torch.bfloat16 or w1n.shape != (ndir, N, C) or maa_x.shape != (ndir, C):
@@ -2295,11 +2142,7 @@ def decay_lora(zw: torch.Tensor, d1n: torch.Tensor, d2n: torch.Tensor, bias: Opt
     bias (ndir, C) or None -> (ndir, rows, C).  C = 512, H = 64 run the fused kernel (weights resident in LDS); other sizes
     take two GEMMs with the same roundings."""
     _lib.require_gpu(zw, d1n, d2n, bias)
-    L = _bind2()
-    if not getattr(L, "_pafc_decay_bound", False):
-        _lib._sig(L.pafc_decay_lora_bf16, c_int, ctypes.c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                  c_void_p, c_void_p)
-        L._pafc_decay_bound = True
+    L = _lib.lib()
     ndir, rows, C = zw.shape
     H = d1n.shape[1]
     if zw.dtype != torch.bfloat16 or d1n.shape != (ndir, H, C) or d2n.shape != (ndir, C, H) or \
@@ -2323,11 +2166,7 @@ def decay_lora(zw: torch.Tensor, d1n: torch.Tensor, d2n: torch.Tensor, bias: Opt
 def conv3x3s2_nhwc(x: torch.Tensor, w_tap_co_ci: torch.Tensor, bias: Optional[torch.Tensor], relu: bool = True):
     """x (B, T1, F1, Ci) bf16 NHWC, w (9, Co, Ci) -> (B, T2, F2, Co) = relu(conv3x3 stride 2 + bias)."""
     _lib.require_gpu(x, w_tap_co_ci, bias)
-    L = _bind2()
-    if not getattr(L, "_pafc_conv_bound", False):
-        _lib._sig(L.pafc_conv3x3s2_nhwc_bf16, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                  c_void_p, c_int, c_void_p)
-        L._pafc_conv_bound = True
+    L = _lib.lib()
     B, T1, F1, Ci = x.shape
     Co = w_tap_co_ci.shape[1]
     if x.dtype != torch.bfloat16 or w_tap_co_ci.shape != (9, Co, Ci) or w_tap_co_ci.dtype != x.dtype:
@@ -2346,11 +2185,7 @@ def conv3x3s2_nhwc_ph(x: torch.Tensor, w_tap_co_ci: torch.Tensor, bias: Optional
     """The phase-pipelined implicit GEMM (csrc/gemm_ph.hip) by itself -- same arguments as conv3x3s2_nhwc, which picks it
     for the long-form shapes."""
     _lib.require_gpu(x, w_tap_co_ci, bias)
-    L = _bind2()
-    if not getattr(L, "_pafc_convph_bound", False):
-        _lib._sig(L.pafc_conv3x3s2_nhwc_bf16_ph, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                  c_void_p, c_int, c_int, c_void_p)
-        L._pafc_convph_bound = True
+    L = _lib.lib()
     B, T1, F1, Ci = x.shape
     Co = w_tap_co_ci.shape[1]
     if x.dtype != torch.bfloat16 or w_tap_co_ci.shape != (9, Co, Ci) or w_tap_co_ci.dtype != x.dtype:
@@ -2367,7 +2202,7 @@ def ctc_greedy(scores: torch.Tensor, lens: Optional[torch.Tensor], blank_id: int
     _lib.require_gpu(scores, lens)
     if scores.dim() != 3:
         raise _lib.PafcError("ctc_greedy wants (B, T, V) scores")
-    L = _bind()
+    L = _lib.lib()
     B, T, V = scores.shape
     lens64 = None if lens is None else lens.to(torch.int64).contiguous()
     best = torch.empty(B, T, dtype=torch.int32, device=scores.device)
@@ -2390,38 +2225,10 @@ def gemm_bf16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = N
     (M, N) or (Z, M, N), ``out`` may be ``residual``.  Rows may be strided views (unit stride in the last dim).
     act "glu": w / bias rows come in blocks of 128 = 64 value rows + the 64 gate rows of the same channels
     (``glu_interleave``); out is (M, N / 2)."""
-    _lib.require_gpu(bias)
-    for t in (a, w, residual, out):
-        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1):
-            raise _lib.PafcError("gemm_bf16: bf16 GPU tensors with unit stride in the last dimension")
-    L = _bind2()
-    if not getattr(L, "_pafc_gemm2_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_gemm_bf16, I, G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, c_float, I, P)
-        L._pafc_gemm2_bound = True
-    batched = a.dim() == 3
-    Z = a.shape[0] if batched else 1
-    M, K = a.shape[-2], a.shape[-1]
-    N = w.shape[-2]
-    if w.shape[-1] != K or (batched and (w.dim() != 3 or w.shape[0] != Z)) or (not batched and (a.dim() != 2 or w.dim() != 2)):
-        raise _lib.PafcError("gemm_bf16: a (M, K) x w (N, K), or both with a leading batch")
-    No = N // 2 if act == "glu" else N
-    if out is None:
-        out = torch.empty((Z, M, No) if batched else (M, No), dtype=a.dtype, device=a.device)
-    for t in (residual, out):
-        if t is not None and tuple(t.shape) != ((Z, M, No) if batched else (M, No)):
-            raise _lib.PafcError("gemm_bf16: residual / out must be (M, N) per batch entry")
-    if bias is not None and (bias.dtype != a.dtype or bias.shape[-1] != N):
-        raise _lib.PafcError("gemm_bf16: bias must be (N) or (Z, N) bf16")
-    sb = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    bs = lambda t: t.stride(0) if batched else 0
+    Z, M, N, K, out, args = _gemm_operands("gemm_bf16", torch.bfloat16, a, w, bias, residual, out, act)
     from .profiling import op_timer
-    with op_timer("gemm_%dx%d%s" % (K, N, "x%d" % Z if batched else ""), sample=12, flops=2.0 * Z * M * N * K):
-        rc = L.pafc_gemm_bf16(M, N, K, Z, _lib.ptr(a), a.stride(-2), bs(a), _lib.ptr(w), w.stride(-2), bs(w),
-                              _lib.ptr(bias), sb, _lib.ptr(residual), residual.stride(-2) if residual is not None else 0,
-                              bs(residual) if residual is not None else 0, _lib.ptr(out), out.stride(-2), bs(out),
-                              float(alpha), _ACTS[act], _lib.stream_of(a))
+    with op_timer("gemm_%dx%d%s" % (K, N, "x%d" % Z if a.dim() == 3 else ""), sample=12, flops=2.0 * Z * M * N * K):
+        rc = _lib.lib().pafc_gemm_bf16(*args, float(alpha), _ACTS[act], _lib.stream_of(a))
     _lib.check(rc, "pafc_gemm_bf16")
     return out
 
@@ -2461,11 +2268,7 @@ def decay_lora_skinny(x: torch.Tensor, d1n: torch.Tensor, d2n: torch.Tensor, bia
     if x.dtype != torch.bfloat16 or x.stride(1) != 1 or d1n.shape != (H, C) or d2n.shape != (C, H) or \
             not (d1n.is_contiguous() and d2n.is_contiguous()) or (bias is not None and (bias.numel() != C or not bias.is_contiguous())):
         raise _lib.PafcError("decay_lora_skinny: x (M, C) bf16 rows, d1n (H, C), d2n (C, H), bias (C), contiguous weights")
-    L = _bind2()
-    if not getattr(L, "_pafc_dls_bound", False):
-        _lib._sig(L.pafc_decay_lora_skinny_bf16, c_int, ctypes.c_long, c_int, c_int, c_void_p, ctypes.c_long, c_void_p, c_void_p, c_void_p,
-                  c_void_p, ctypes.c_long, c_void_p)
-        L._pafc_dls_bound = True
+    L = _lib.lib()
     out = torch.empty((M, C), dtype=x.dtype, device=x.device)
     rc = L.pafc_decay_lora_skinny_bf16(M, C, H, _lib.ptr(x), x.stride(0), _lib.ptr(d1n), _lib.ptr(d2n), _lib.ptr(bias), _lib.ptr(out), C,
                                        _lib.stream_of(x))
@@ -2486,32 +2289,9 @@ def gemm_skinny(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     mix_maa (K) [+ mix_prev (B, K)], mix_T: a = x of B sequences of mix_T rows, the operand is x + (x_prev - x) * maa;
     norm_silu = (gamma (K), beta (K), eps): the operand is silu(LayerNorm(a)), each rounded to bf16."""
     ng, nb, neps = norm_silu if norm_silu is not None else (None, None, 0.0)
-    _lib.require_gpu(bias, ln_stats, ln_csum, stats_out, mix_maa, mix_prev, ng, nb)
-    for t in (a, w, residual, out):
-        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1):
-            raise _lib.PafcError("gemm_skinny: bf16 GPU tensors with unit stride in the last dimension")
-    L = _bind2()
-    if not getattr(L, "_pafc_skinny_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_gemm_skinny_bf16_ex, I, G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, c_float, I, I, P, I, I, P,
-                  c_float, P, P, P, I, P, P, c_float, P)
-        L._pafc_skinny_bound = True
+    _lib.require_gpu(ln_stats, ln_csum, stats_out, mix_maa, mix_prev, ng, nb)
+    Z, M, N, K, out, args = _gemm_operands("gemm_skinny", torch.bfloat16, a, w, bias, residual, out, act)
     batched = a.dim() == 3
-    Z = a.shape[0] if batched else 1
-    M, K = a.shape[-2], a.shape[-1]
-    N = w.shape[-2]
-    if w.shape[-1] != K or (batched and (w.dim() != 3 or w.shape[0] != Z)) or (not batched and (a.dim() != 2 or w.dim() != 2)):
-        raise _lib.PafcError("gemm_skinny: a (M, K) x w (N, K), or both with a leading batch")
-    No = N // 2 if act == "glu" else N
-    shape = (Z, M, No) if batched else (M, No)
-    if out is None:
-        out = torch.empty(shape, dtype=a.dtype, device=a.device)
-    for t in (residual, out):
-        if t is not None and tuple(t.shape) != shape:
-            raise _lib.PafcError("gemm_skinny: residual / out must be (M, N) per batch entry")
-    if bias is not None and (bias.dtype != a.dtype or bias.shape[-1] != N):
-        raise _lib.PafcError("gemm_skinny: bias must be (N) or (Z, N) bf16")
     parts = 0
     if ln_stats is not None or ln_self:
         if ln_csum is None or batched or ln_csum.dtype != torch.float32 or ln_csum.numel() != N or (ln_stats is not None and ln_self):
@@ -2522,7 +2302,7 @@ def gemm_skinny(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
             parts = ln_stats.shape[1]
     elif ln_csum is not None:
         raise _lib.PafcError("gemm_skinny: ln_csum without ln_stats / ln_self")
-    if stats_out is not None and (stats_out.dtype != torch.float32 or stats_out.numel() != Z * M * (No // 16) * 2):
+    if stats_out is not None and (stats_out.dtype != torch.float32 or stats_out.numel() != Z * M * (out.shape[-1] // 16) * 2):
         raise _lib.PafcError("gemm_skinny: stats_out must be fp32 (M, N_out / 16, 2) per batch entry")
     if mix_maa is not None:
         if (batched or mix_T <= 0 or M % mix_T or mix_maa.dtype != a.dtype or mix_maa.numel() != K or not a.is_contiguous()
@@ -2532,14 +2312,9 @@ def gemm_skinny(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
         raise _lib.PafcError("gemm_skinny: mix_prev without mix_maa")
     if ng is not None and (batched or ng.dtype != a.dtype or nb.dtype != a.dtype or ng.numel() != K or nb.numel() != K):
         raise _lib.PafcError("gemm_skinny: norm_silu wants gamma, beta (K) of a's dtype, unbatched")
-    sb = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    bs = lambda t: t.stride(0) if batched else 0
-    rc = L.pafc_gemm_skinny_bf16_ex(M, N, K, Z, _lib.ptr(a), a.stride(-2), bs(a), _lib.ptr(w), w.stride(-2), bs(w), _lib.ptr(bias),
-                                    sb, _lib.ptr(residual), residual.stride(-2) if residual is not None else 0,
-                                    bs(residual) if residual is not None else 0, _lib.ptr(out), out.stride(-2), bs(out),
-                                    float(alpha), _ACTS[act], int(round_first), _lib.ptr(ln_stats), parts, int(ln_self),
-                                    _lib.ptr(ln_csum), float(ln_eps), _lib.ptr(stats_out), _lib.ptr(mix_maa), _lib.ptr(mix_prev),
-                                    int(mix_T), _lib.ptr(ng), _lib.ptr(nb), float(neps), _lib.stream_of(a))
+    rc = _lib.lib().pafc_gemm_skinny_bf16_ex(*args, float(alpha), _ACTS[act], int(round_first), _lib.ptr(ln_stats), parts,
+                                             int(ln_self), _lib.ptr(ln_csum), float(ln_eps), _lib.ptr(stats_out), _lib.ptr(mix_maa),
+                                             _lib.ptr(mix_prev), int(mix_T), _lib.ptr(ng), _lib.ptr(nb), float(neps), _lib.stream_of(a))
     _lib.check(rc, "pafc_gemm_skinny_bf16")
     return out
 
@@ -2549,53 +2324,21 @@ def gemm_bf16_ph(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
                  tile_n: int = 256, tile_m: int = 256):
     """The phase-pipelined tile_m x tile_n kernel (csrc/gemm_ph.hip) by itself -- same arguments as gemm_bf16, which picks
     it for the long-form shapes; act "glu" wants glu_interleave(w, tile_n // 8)."""
-    _lib.require_gpu(bias)
-    for t in (a, w, residual, out):
-        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(-1) != 1):
-            raise _lib.PafcError("gemm_bf16_ph: bf16 GPU tensors with unit stride in the last dimension")
-    L = _bind2()
-    if not getattr(L, "_pafc_gemm_ph_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_gemm_bf16_ph, I, G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, c_float, I, I, I, P)
-        L._pafc_gemm_ph_bound = True
-    batched = a.dim() == 3
-    Z = a.shape[0] if batched else 1
-    M, K = a.shape[-2], a.shape[-1]
-    N = w.shape[-2]
-    if w.shape[-1] != K or (batched and (w.dim() != 3 or w.shape[0] != Z)) or (not batched and (a.dim() != 2 or w.dim() != 2)):
-        raise _lib.PafcError("gemm_bf16_ph: a (M, K) x w (N, K), or both with a leading batch")
-    No = N // 2 if act == "glu" else N
-    if out is None:
-        out = torch.empty((Z, M, No) if batched else (M, No), dtype=a.dtype, device=a.device)
-    sb = bias.stride(0) if (bias is not None and bias.dim() == 2) else 0
-    bs = lambda t: t.stride(0) if batched else 0
-    rc = L.pafc_gemm_bf16_ph(M, N, K, Z, _lib.ptr(a), a.stride(-2), bs(a), _lib.ptr(w), w.stride(-2), bs(w),
-                             _lib.ptr(bias), sb, _lib.ptr(residual), residual.stride(-2) if residual is not None else 0,
-                             bs(residual) if residual is not None else 0, _lib.ptr(out), out.stride(-2), bs(out),
-                             float(alpha), _ACTS[act], int(tile_n), int(tile_m), _lib.stream_of(a))
+    _, _, _, _, out, args = _gemm_operands("gemm_bf16_ph", torch.bfloat16, a, w, bias, residual, out, act)
+    rc = _lib.lib().pafc_gemm_bf16_ph(*args, float(alpha), _ACTS[act], int(tile_n), int(tile_m), _lib.stream_of(a))
     _lib.check(rc, "pafc_gemm_bf16_ph")
     return out
 
 
 def gemm_glu_half(M: int, N: int, K: int, batch: int = 1) -> int:
     """Row-block half size (64 or 32) pafc_gemm_bf16 wants for act "glu" on this problem (it depends on the kernel chosen)."""
-    L = _bind2()
-    if not getattr(L, "_pafc_gluhalf_bound", False):
-        from ctypes import c_long
-        _lib._sig(L.pafc_gemm_bf16_glu_half, c_int, c_long, c_int, c_int, c_int)
-        L._pafc_gluhalf_bound = True
-    return int(L.pafc_gemm_bf16_glu_half(M, N, K, batch))
+    return int(_lib.lib().pafc_gemm_bf16_glu_half(M, N, K, batch))
 
 
 def log_softmax_rows(x: torch.Tensor, inplace: bool = False) -> torch.Tensor:
     """log_softmax over the last dimension in one pass over HBM (include/pafc_search.h: pafc_log_softmax_rows)."""
     _lib.require_gpu(x)
-    L = _bind()
-    if not getattr(L, "_pafc_lsm_bound", False):
-        from ctypes import c_long
-        _lib._sig(L.pafc_log_softmax_rows, c_int, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p)
-        L._pafc_lsm_bound = True
+    L = _lib.lib()
     V = x.shape[-1]
     out = x if inplace else torch.empty_like(x)
     _lib.check(L.pafc_log_softmax_rows(_lib.dtype_code(x.dtype), x.numel() // V, V, _lib.ptr(x), _lib.ptr(out),
@@ -2621,11 +2364,7 @@ def conv3x3s2_c1_nhwc(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     _lib.require_gpu(x, weight, bias)
     if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16 or x.dim() != 3 or weight.shape[1:] != (1, 3, 3):
         raise _lib.PafcError("conv3x3s2_c1_nhwc: bf16 x (B, T, F) and weight (C, 1, 3, 3)")
-    L = _bind()
-    if not getattr(L, "_pafc_c1_bound", False):
-        _lib._sig(L.pafc_conv3x3s2_c1_nhwc_bf16, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                  c_int, c_void_p)
-        L._pafc_c1_bound = True
+    L = _lib.lib()
     B, T, Fd = x.shape
     C = weight.shape[0]
     out = torch.empty((B, (T - 3) // 2 + 1, (Fd - 3) // 2 + 1, C), dtype=x.dtype, device=x.device)
@@ -2640,14 +2379,7 @@ def conv3x3s2_c1_wgrad(x: torch.Tensor, act: torch.Tensor, dact: torch.Tensor) -
     then db; the partial sums are added in a fixed order."""
     B, T, Fd = x.shape
     C = act.shape[-1]
-    L = _bind()
-    if not getattr(L, "_pafc_c1w_bound", False):
-        from ctypes import c_size_t
-        L.pafc_conv3x3s2_c1_wgrad_workspace_bytes.restype = c_size_t
-        L.pafc_conv3x3s2_c1_wgrad_workspace_bytes.argtypes = [c_int, c_int, c_int]
-        _lib._sig(L.pafc_conv3x3s2_c1_wgrad_bf16, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                  c_void_p, c_void_p, c_size_t, c_void_p)
-        L._pafc_c1w_bound = True
+    L = _lib.lib()
     nbytes = L.pafc_conv3x3s2_c1_wgrad_workspace_bytes(B, T, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     out = torch.empty(10, C, dtype=torch.float32, device=x.device)
@@ -2727,13 +2459,7 @@ def ctc_prefix_beam(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optiona
     context biasing, or None.  Returns (tokens (B, beam, T) int32, lengths (B, beam) int32 [-1 = unused],
     scores (B, beam) float64, times (B, beam, T) int32 [frames of each prefix's tokens, then -1] or None), best first."""
     _lib.require_gpu(top_logp, top_idx, lens)
-    from ctypes import c_size_t
-    L = _bind()
-    if not getattr(L, "_pafc_beam_ex_bound", False):
-        P, I = c_void_p, c_int
-        _lib._sig(L.pafc_ctc_prefix_beam_ex_workspace_bytes, c_size_t, I, I, I)
-        _lib._sig(L.pafc_ctc_prefix_beam_search_ex, I, I, I, I, P, P, P, I, I, P, P, P, P, P, P, c_size_t, P)
-        L._pafc_beam_ex_bound = True
+    L = _lib.lib()
     if top_logp.dtype != torch.float32 or top_logp.shape != top_idx.shape or top_logp.dim() != 3:
         raise _lib.PafcError("ctc_prefix_beam: top_logp float32 (B, T, K) and top_idx of the same shape")
     B, T, K = top_logp.shape
@@ -2770,15 +2496,7 @@ class RnntBeamState:
     """Device-side beams of the CTC-fused RNN-T prefix beam search (include/pafc_search.h: pafc_rnnt_beam_*)."""
 
     def __init__(self, B: int, T: int, beam: int, blank: int, device):
-        from ctypes import c_size_t
-        L = _bind()
-        if not getattr(L, "_pafc_rnnt_bound", False):
-            P, I = c_void_p, c_int
-            _lib._sig(L.pafc_rnnt_beam_workspace_bytes, c_size_t, I, I, I)
-            _lib._sig(L.pafc_rnnt_beam_init, I, I, I, I, I, P, c_size_t, P, P, P)
-            _lib._sig(L.pafc_rnnt_beam_step, I, I, I, I, I, I, P, P, P, P, P, c_size_t, P, P, P)
-            _lib._sig(L.pafc_rnnt_beam_finish, I, I, I, I, P, c_size_t, P, P, P, P)
-            L._pafc_rnnt_bound = True
+        L = _lib.lib()
         self.L, self.B, self.T, self.beam, self.blank = L, B, T, beam, blank
         self.nws = L.pafc_rnnt_beam_workspace_bytes(B, T, beam)
         if self.nws == 0:
@@ -2826,12 +2544,7 @@ def conv_sub_f32split(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tens
     _lib.require_gpu(x, w1, b1, w2_hi, w2_lo, b2)
     if x.dtype != torch.float32 or w1.dtype != torch.float32 or w2_hi.dtype != torch.bfloat16 or x.dim() != 3:
         raise _lib.PafcError("conv_sub_f32split: fp32 x (B, T, F) / w1, bf16 split planes for w2")
-    L = _bind()
-    if not getattr(L, "_pafc_split_bound", False):
-        P, I = c_void_p, c_int
-        _lib._sig(L.pafc_conv3x3s2_c1_nhwc_f32split, I, I, I, I, I, P, P, P, P, P, I, P)
-        _lib._sig(L.pafc_conv3x3s2_nhwc_f32split, I, I, I, I, I, I, P, P, P, P, P, P, I, P)
-        L._pafc_split_bound = True
+    L = _lib.lib()
     B, T, Fd = x.shape
     C = w1.shape[0]
     T1, F1 = (T - 3) // 2 + 1, (Fd - 3) // 2 + 1
@@ -2858,13 +2571,7 @@ def conv_sub_f32split_planes(x: torch.Tensor, w1: torch.Tensor, b1: Optional[tor
     C = w1.shape[0]
     if x.dtype != torch.float32 or w1.dtype != torch.float32 or w2_3.dtype != torch.bfloat16 or tuple(w2_3.shape) != (9, C, 3 * C):
         raise _lib.PafcError("conv_sub_f32split_planes: fp32 x (B, T, F) / w1, w2 as (9, C, 3C) bf16 planes")
-    L = _bind()
-    if not getattr(L, "_pafc_splitph_bound", False):
-        from ctypes import c_long
-        P, I = c_void_p, c_int
-        _lib._sig(L.pafc_conv3x3s2_c1_nhwc_f32split_ps, I, I, I, I, I, P, P, P, P, P, c_long, I, P)
-        _lib._sig(L.pafc_conv3x3s2_nhwc_split_ph, I, I, I, I, I, I, P, P, P, P, I, I, P)
-        L._pafc_splitph_bound = True
+    L = _lib.lib()
     T1, F1 = (T - 3) // 2 + 1, (Fd - 3) // 2 + 1
     T2, F2 = (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1
     y1 = torch.empty((B, T1, F1, 2 * C), dtype=torch.bfloat16, device=x.device)
@@ -2881,24 +2588,6 @@ def conv_sub_f32split_planes(x: torch.Tensor, w1: torch.Tensor, b1: Optional[tor
     return out
 
 
-def _bind_mamba():
-    L = _bind()
-    if not getattr(L, "_pafc_mamba_bound", False):
-        from ctypes import c_float, c_long
-        P, I, G = c_void_p, c_int, c_long
-        _lib._sig(L.pafc_dwconv1d_cl_ex, I, I, I, I, I, I, I, I, P, G, P, P, P, I, P, P)
-        _lib._sig(L.pafc_mamba2_prep, I, I, I, I, I, P, P, G, P, P, P, P, P, P, P, P, P)
-        _lib._sig(L.pafc_mamba2_finish, I, I, I, I, I, P, P, P, P, G, P, G, P, P, P, c_float, I, P, P)
-        from ctypes import c_size_t
-        _lib._sig(L.pafc_mamba2_scan_workspace_bytes, c_size_t, I, I, I, I)
-        _lib._sig(L.pafc_mamba2_scan, I, I, I, I, P, G, P, P, P, I, P, c_size_t, P)
-        _lib._sig(L.pafc_mamba2_scan_dir, I, I, I, I, P, G, P, P, P, I, I, P, c_size_t, P)
-        _lib._sig(L.pafc_mamba2_scan_skip_bf16, I, I, I, I, P, G, P, P, P, P, I, I, P, c_size_t, P)
-        _lib._sig(L.pafc_mamba2_gate_norm, I, I, G, I, P, P, G, P, c_float, P, P)
-        L._pafc_mamba_bound = True
-    return L
-
-
 def causal_conv_silu_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], reverse: bool = False
                         ) -> torch.Tensor:
     """SiLU(causal depthwise conv1d) in channels-last layout: x (B, L, C) -- may be a column slice of a wider tensor --
@@ -2913,9 +2602,9 @@ def causal_conv_silu_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     y = torch.empty((B, Lq, C), dtype=x.dtype, device=x.device)
     if reverse:
         weight = weight.flip(-1).contiguous()
-    rc = _bind_mamba().pafc_dwconv1d_cl_ex(_lib.dtype_code(x.dtype), B, Lq, C, K, 0 if reverse else K - 1, Lq, _lib.ptr(x),
-                                           x.stride(1), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), 2, None,
-                                           _lib.stream_of(x))
+    rc = _lib.lib().pafc_dwconv1d_cl_ex(_lib.dtype_code(x.dtype), B, Lq, C, K, 0 if reverse else K - 1, Lq, _lib.ptr(x),
+                                        x.stride(1), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), 2, None,
+                                        _lib.stream_of(x))
     _lib.check(rc, "pafc_dwconv1d_cl_ex")
     return y
 
@@ -2925,9 +2614,9 @@ def mamba2_prep(xbc: torch.Tensor, dt_raw: torch.Tensor, dt_bias: torch.Tensor, 
     _lib.require_gpu(xbc, dt_bias, A_log)
     B, Lq, _ = xbc.shape
     planes = [torch.empty((B, Lq, d_inner), dtype=torch.float32, device=xbc.device) for _ in range(6)]
-    rc = _bind_mamba().pafc_mamba2_prep(_lib.dtype_code(xbc.dtype), B, Lq, d_inner, _lib.ptr(xbc), _lib.ptr(dt_raw),
-                                        dt_raw.stride(1), _lib.ptr(dt_bias), _lib.ptr(A_log), *[_lib.ptr(t) for t in planes],
-                                        _lib.stream_of(xbc))
+    rc = _lib.lib().pafc_mamba2_prep(_lib.dtype_code(xbc.dtype), B, Lq, d_inner, _lib.ptr(xbc), _lib.ptr(dt_raw),
+                                     dt_raw.stride(1), _lib.ptr(dt_bias), _lib.ptr(A_log), *[_lib.ptr(t) for t in planes],
+                                     _lib.stream_of(xbc))
     _lib.check(rc, "pafc_mamba2_prep")
     return planes
 
@@ -2941,7 +2630,7 @@ def mamba2_scan(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, H: int
     if xbc.dtype != torch.bfloat16 or dt.dtype != torch.float32 or log_a.dtype != torch.float32:
         raise _lib.PafcError("mamba2_scan: bf16 xbc, fp32 dt / log_a")
     B, Lq, ldx = xbc.shape
-    Lb = _bind_mamba()
+    Lb = _lib.lib()
     nws = Lb.pafc_mamba2_scan_workspace_bytes(B, Lq, H, 0)
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=xbc.device)
     if D is not None:
@@ -2968,8 +2657,8 @@ def mamba2_gate_norm(y: torch.Tensor, z: torch.Tensor, norm_weight: torch.Tensor
     if z.dtype != y.dtype or norm_weight.dtype != y.dtype or z.stride(-1) != 1 or z.shape != y.shape or not z.is_cuda:
         raise _lib.PafcError("mamba2_gate_norm: y, z, norm_weight in one dtype; z shaped like y with unit channel stride")
     out = torch.empty_like(y)
-    rc = _bind_mamba().pafc_mamba2_gate_norm(_lib.dtype_code(y.dtype), rows, d, _lib.ptr(y), _lib.ptr(z), z.stride(-2),
-                                             _lib.ptr(norm_weight), float(eps), _lib.ptr(out), _lib.stream_of(y))
+    rc = _lib.lib().pafc_mamba2_gate_norm(_lib.dtype_code(y.dtype), rows, d, _lib.ptr(y), _lib.ptr(z), z.stride(-2),
+                                          _lib.ptr(norm_weight), float(eps), _lib.ptr(out), _lib.stream_of(y))
     _lib.check(rc, "pafc_mamba2_gate_norm")
     return out
 
@@ -2979,9 +2668,9 @@ def mamba2_finish(y0, y1, xbc, dt_raw, z, dt_bias, D, norm_weight, eps: float, d
     _lib.require_gpu(y0, y1, xbc, dt_bias, D, norm_weight)
     B, Lq, _ = xbc.shape
     out = torch.empty((B, Lq, d_inner), dtype=xbc.dtype, device=xbc.device)
-    rc = _bind_mamba().pafc_mamba2_finish(_lib.dtype_code(xbc.dtype), B, Lq, d_inner, _lib.ptr(y0), _lib.ptr(y1), _lib.ptr(xbc),
-                                          _lib.ptr(dt_raw), dt_raw.stride(1), _lib.ptr(z), z.stride(1), _lib.ptr(dt_bias),
-                                          _lib.ptr(D), _lib.ptr(norm_weight), float(eps), int(diag), _lib.ptr(out),
-                                          _lib.stream_of(xbc))
+    rc = _lib.lib().pafc_mamba2_finish(_lib.dtype_code(xbc.dtype), B, Lq, d_inner, _lib.ptr(y0), _lib.ptr(y1), _lib.ptr(xbc),
+                                       _lib.ptr(dt_raw), dt_raw.stride(1), _lib.ptr(z), z.stride(1), _lib.ptr(dt_bias),
+                                       _lib.ptr(D), _lib.ptr(norm_weight), float(eps), int(diag), _lib.ptr(out),
+                                       _lib.stream_of(xbc))
     _lib.check(rc, "pafc_mamba2_finish")
     return out

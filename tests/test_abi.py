@@ -143,24 +143,62 @@ def test_torch_ops_wkv6_schema_matches_the_reference_binding(so_path):
         torch.ops.wkv6.forward_fp32(1, 4, 64, 1, t, t, t, t, torch.zeros(1, 64), torch.empty(1, 4, 64))
 
 
-def test_ctypes_signatures_have_the_arity_of_the_header_prototypes():
-    """Every `_lib._sig(L.pafc_x, restype, *argtypes)` in the package declares exactly as many arguments as the prototype of
-    pafc_x in include/*.h has (a short list lets ctypes pass the tail by its default rules: a Python int as a 32-bit C int --
-    a truncated pointer or stream handle)."""
-    import glob
-    import re
-    hdr = "".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "include", "*.h")))
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "int64_t": ctypes.c_long, "size_t": ctypes.c_size_t,
+           "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong, "uint64_t": ctypes.c_ulonglong,
+           "pafc_stream_t": ctypes.c_void_p}
+
+
+def _header_prototypes():
+    """{symbol: (return type, [(C type, parameter name)])} of every prototype in include/*.h; pointers are "*"."""
     protos = {}
-    for m in re.finditer(r"\b(?:int|size_t|void|long)\s+(pafc_\w+)\s*\(([^;{]*?)\)\s*;", hdr, flags=re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ("", "void") else len(args.split(","))
-    src = "".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "paper_accurate_fast_cheap_amd", "**", "*.py"), recursive=True))
-    seen = 0
-    for m in re.finditer(r"_sig\(\s*\w+\.(pafc_\w+)\s*,(.*?)\)\n", src, flags=re.S):
-        name, rest = m.group(1), m.group(2)
-        n = len([a for a in rest.replace("\n", " ").split(",") if a.strip()]) - 1          # minus the return type
-        assert name in protos, f"{name}: bound but not declared in include/*.h"
-        assert protos[name] == n, f"{name}: header has {protos[name]} arguments, the binding declares {n}"
-        seen += 1
-    assert seen >= 40
+    for h in glob.glob(os.path.join(ROOT, "include", "*.h")):
+        text = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+        for m in re.finditer(r"\b(int|size_t|void|long)\s+(pafc_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+            args = m.group(3).strip()
+            params = []
+            for a in ([] if args in ("", "void") else args.split(",")):
+                a = " ".join(a.split())
+                ctype, _, name = a.replace("*", " * ").rpartition(" ")
+                params.append(("*" if "*" in ctype else " ".join(ctype.replace("const", "").split()), name))
+            protos[m.group(2)] = (m.group(1), params)
+    return protos
+
+
+def test_signature_table_matches_the_header_prototypes():
+    """_lib.SIGNATURES -- the one place product code declares how a kernel is called -- holds every prototype of include/*.h
+    with its return and argument types mapped as the table's comment says (a wrong type is not caught at the call: ctypes
+    passes a long declared c_int truncated, a stream handle cut to 32 bits).  Reads the headers only: no library needed."""
+    from paper_accurate_fast_cheap_amd import _lib
+    protos = _header_prototypes()
+    table = _lib.SIGNATURES
+    assert len(protos) >= 100
+    assert set(table) == set(protos), (f"missing from the table: {sorted(set(protos) - set(table))}, "
+                                       f"not in include/*.h: {sorted(set(table) - set(protos))}")
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        assert restype is _CTYPES[ret], f"{name}: returns {ret}, the table says {restype.__name__}"
+        assert len(argtypes) == len(params), f"{name}: header has {len(params)} arguments, the table {len(argtypes)}"
+        for i, ((ctype, pname), got) in enumerate(zip(params, argtypes)):
+            want = ctypes.c_void_p if ctype == "*" else _CTYPES.get(ctype)
+            assert want is not None, f"{name}: argument {i} ({pname}) has C type {ctype}, which the mapping lacks"
+            assert got is want, f"{name}: argument {i} ({pname}, {ctype}) wants {want.__name__}, the table says {got.__name__}"
+
+
+def test_a_symbol_missing_from_the_library_fails_loudly():
+    from paper_accurate_fast_cheap_amd import _lib
+
+    class Stale:                  # a library built before the headers gained a prototype
+        _name = "stale.so"
+    with pytest.raises(_lib.PafcError, match=r"pafc_\w+ is declared in include/\*\.h but missing from stale\.so"):
+        _lib._bind(Stale())
+
+
+def test_signatures_are_declared_in_one_place():
+    """No module of the package but _lib.py sets restype / argtypes, so that scattered binding cannot grow back."""
+    pkg = os.path.join(ROOT, "paper_accurate_fast_cheap_amd")
+    for path in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
+        if os.path.basename(path) == "_lib.py":
+            continue
+        src = open(path).read()
+        for word in ("_sig(", ".argtypes", ".restype"):
+            assert word not in src, f"{os.path.relpath(path, ROOT)} declares a signature ({word}): add it to _lib.SIGNATURES"

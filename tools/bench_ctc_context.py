@@ -6,7 +6,7 @@
 each from the same top-k tensors (the topk itself is not timed), plus the whole ctc_prefix_beam_search call with the
 1 000-phrase graph.  Synthetic posteriors with phrases planted just below a decoy, so the graph changes the beams.
 Prints one JSON line.  Kernel-only times: run under rocprofv3 --kernel-trace --stats."""
-import argparse, ctypes, json, os, random, sys, tempfile
+import argparse, json, os, random, sys, tempfile
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -95,11 +95,6 @@ def main(argv=None):
     idx32, lens64 = top_i.to(torch.int32), lens.to(torch.int64)
 
     L = _lib.lib()
-    P, I, Z = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    L.pafc_ctc_prefix_beam_workspace_bytes.restype = Z
-    L.pafc_ctc_prefix_beam_workspace_bytes.argtypes = [I, I, I]
-    L.pafc_ctc_prefix_beam_search.restype = I
-    L.pafc_ctc_prefix_beam_search.argtypes = [I, I, I, P, P, P, I, I, P, P, P, P, Z, P]
     nws = L.pafc_ctc_prefix_beam_workspace_bytes(B, T, beam)
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
     toks = torch.empty(B, beam, T, dtype=torch.int32, device=dev)
