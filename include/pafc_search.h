@@ -67,6 +67,54 @@ int pafc_ctc_prefix_beam_search_ex(int B, int T, int K, const float *top_logp, c
                                    int32_t *out_tokens, int32_t *out_len, double *out_score, int32_t *out_times,
                                    void *workspace, size_t workspace_bytes, pafc_stream_t stream);
 
+/* CTC prefix beam search chunk by chunk (pafc_ctc_beam_stream_*): the search of pafc_ctc_prefix_beam_search_ex with the
+ * beam carried from one chunk to the next in `workspace`.  After any cut of a row's frames into feeds, the n-best token
+ * lists, frame lists and float64 scores are those of the offline search of the concatenated frames, bit for bit: a feed
+ * loads the beam, runs the offline kernel's per-frame arithmetic and stores the beam back.  Nothing reads the host or
+ * allocates, so a feed can be captured in a graph.  beam <= 16, K <= 16, max_total_frames * beam < 2^31 - 1.
+ * max_total_frames: the most frames a row may consume between two resets; it sizes the row's node pools, which keep the
+ *   offline numbering by absolute frame (node 1 + t * beam + rank).  Memory per stream: 1240 bytes of beam state plus
+ *   (1 + max_total_frames * beam) nodes of 8 bytes, or 16 bytes with_times (beam 8, 4000 frames = 160 s: 500 kB).  The
+ *   pools are not compacted: reset a row at an endpoint.
+ * with_times: the workspace also holds the frame lists (DecodeResult.times); the same value in every call on a workspace.
+ * reset: rows with row_mask[b] != 0 (device int32 (B), or NULL = every row) start again from the empty prefix at absolute
+ *   frame 0, overflow flag cleared.  Call it on every row before the first feed.
+ * feed: row b consumes its first clamp(nframes[b], 0, Tmax) frames of top_logp / top_idx ((B, Tmax, K), as in
+ *   pafc_ctc_prefix_beam_search; nframes: device int64 (B)).  A row with 0 frames is untouched.  A feed that would take a
+ *   row past max_total_frames consumes nothing for that row and sets its overflow flag, which stays until the reset (2: the
+ *   row was never reset).  graph: NULL or the context graph, the same for every feed of a stream.
+ * drain: the n-best of every row as if its stream ended here; the carried state is not changed.  from: device int32 (B)
+ *   or NULL (= 0): tokens [from[b], from[b] + ld) of each list go to out_tokens (B, beam, ld); pass the committed count of
+ *   an earlier drain, and the walk and the copy are bounded by the tail that is not final yet.  out_len (B, beam): the
+ *   TOTAL token count of each entry, -1 for unused entries; out_score (B, beam) float64, with a graph score + the
+ *   finalize() bonus of the entry's state; out_count (B): entries in use; out_committed (B): the length of the longest
+ *   common prefix of the row's token lists -- every later hypothesis extends one of them, so these tokens are final
+ *   (looked for at or above from[b]: a `from` beyond it is the caller's error); out_overflow (B): the row's flag.
+ *   out_ntimes (B, beam) / out_times (B, beam, ld_times), or NULL (need with_times): the length of each entry's frame
+ *   list and its first ld_times frames (ld_times 0: lengths only).  Frame lists are per entry and final only at the end. */
+size_t pafc_ctc_beam_stream_workspace_bytes(int B, int max_total_frames, int beam, int with_times);
+int pafc_ctc_beam_stream_reset(int B, int max_total_frames, int beam, int with_times, const int32_t *row_mask,
+                               void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+int pafc_ctc_beam_stream_feed(int B, int Tmax, int K, const float *top_logp, const int32_t *top_idx, const int64_t *nframes,
+                              int max_total_frames, int beam, int blank_id, const pafc_ctc_context_graph *graph,
+                              int with_times, void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+int pafc_ctc_beam_stream_drain(int B, int max_total_frames, int beam, const pafc_ctc_context_graph *graph, int with_times,
+                               const void *workspace, size_t workspace_bytes, const int32_t *from, int ld,
+                               int32_t *out_tokens, int32_t *out_len, double *out_score, int32_t *out_count,
+                               int32_t *out_committed, int32_t *out_overflow, int ld_times, int32_t *out_times,
+                               int32_t *out_ntimes, pafc_stream_t stream);
+
+/* CTC greedy search chunk by chunk: pafc_ctc_greedy over the first clamp(nframes[b], 0, Tmax) frames of scores
+ * (B, Tmax, V), with two values carried per row in `workspace` (pafc_ctc_greedy_stream_workspace_bytes(B) = 16 B bytes):
+ * the previous frame's argmax, so a run of equal ids that crosses a chunk boundary collapses once, and the frames consumed
+ * so far, so `frames` ((B, Tmax) int64, or NULL) are absolute.  Frames beyond nframes[b] are ignored (not blank).  tokens /
+ * ntok: the tokens this chunk adds.  reset: rows with row_mask[b] != 0 (NULL = all) start a new stream. */
+size_t pafc_ctc_greedy_stream_workspace_bytes(int B);
+int pafc_ctc_greedy_stream_reset(int B, const int32_t *row_mask, void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+int pafc_ctc_greedy_stream(int dtype, int B, int Tmax, int V, const void *scores, const int64_t *nframes, int blank_id,
+                           void *workspace, size_t workspace_bytes, int32_t *best, int32_t *tokens, int32_t *ntok,
+                           int64_t *frames, pafc_stream_t stream);
+
 /* CTC-fused RNN-T prefix beam search (PrefixBeamSearch.prefix_beam_search_decode_batch,
  * wenet/transducer/search/prefix_beam_search.py:428-574): the per-frame candidate walk on the device.  The caller keeps
  * B x beam fixed slots; per frame it runs predictor step + joint + log-softmax + fusion + top-`beam` for all slots with

@@ -141,6 +141,13 @@ SIGNATURES = {
     "pafc_ctc_prefix_beam_search": (I, [I, I, I, P, P, P, I, I, P, P, P, P, Z, P]),
     "pafc_ctc_prefix_beam_ex_workspace_bytes": (Z, [I, I, I]),
     "pafc_ctc_prefix_beam_search_ex": (I, [I, I, I, P, P, P, I, I, P, P, P, P, P, P, Z, P]),
+    "pafc_ctc_beam_stream_workspace_bytes": (Z, [I, I, I, I]),
+    "pafc_ctc_beam_stream_reset": (I, [I, I, I, I, P, P, Z, P]),
+    "pafc_ctc_beam_stream_feed": (I, [I, I, I, P, P, P, I, I, I, P, I, P, Z, P]),
+    "pafc_ctc_beam_stream_drain": (I, [I, I, I, P, I, P, Z, P, I, P, P, P, P, P, P, I, P, P, P]),
+    "pafc_ctc_greedy_stream_workspace_bytes": (Z, [I]),
+    "pafc_ctc_greedy_stream_reset": (I, [I, P, P, Z, P]),
+    "pafc_ctc_greedy_stream": (I, [I, I, I, I, P, P, I, P, Z, P, P, P, P, P]),
     "pafc_rnnt_beam_workspace_bytes": (Z, [I, I, I]),
     "pafc_rnnt_beam_init": (I, [I, I, I, I, P, Z, P, P, P]),
     "pafc_rnnt_beam_step": (I, [I, I, I, I, I, P, P, P, P, P, Z, P, P, P]),

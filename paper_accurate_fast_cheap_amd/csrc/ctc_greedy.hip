@@ -90,6 +90,64 @@ __global__ __launch_bounds__(256) void ctc_collapse_kernel(int T, int blank, con
     if (tid == 0) ntok[b] = s_base;
 }
 
+// Streaming collapse: the collapse kernel over the first n = clamp(nframes[b], 0, Tmax) frames of a chunk, with the two
+// values a row carries from chunk to chunk -- the previous frame's argmax (a run of equal ids that crosses the chunk
+// boundary collapses once) and the number of frames before this chunk (frames are absolute).
+struct GreedyRow {
+    int64_t base;
+    int32_t prev, pad;
+};
+
+__global__ void ctc_greedy_stream_reset_kernel(int B, const int32_t *row_mask, GreedyRow *state) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || (row_mask && row_mask[b] == 0)) return;
+    state[b].base = 0; state[b].prev = -1; state[b].pad = 0;
+}
+
+__global__ __launch_bounds__(256) void ctc_collapse_stream_kernel(int Tmax, int blank, const int64_t *nframes, GreedyRow *state,
+                                                                  const int32_t *best, int32_t *tokens, int32_t *ntok,
+                                                                  int64_t *frames) {
+    __shared__ int s_wave[4];
+    __shared__ int s_base;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t nf = nframes[b];
+    const int T = (int)(nf < 0 ? 0 : (nf > Tmax ? Tmax : nf));
+    const int32_t *ids = best + (long)b * Tmax;
+    int32_t *out = tokens + (long)b * Tmax;
+    int64_t *fout = frames ? frames + (long)b * Tmax : nullptr;
+    const int64_t base = state[b].base;
+    const int carried = state[b].prev;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < T; t0 += 256) {
+        const int t = t0 + tid;
+        int id = blank, prev = blank;
+        bool keep = false;
+        if (t < T) {
+            id = ids[t];
+            prev = t > 0 ? ids[t - 1] : carried;
+            keep = id != blank && id != prev;
+        }
+        const unsigned long long m = __ballot(keep);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int off = s_base;
+        for (int w = 0; w < wave; ++w) off += s_wave[w];
+        if (keep) {
+            out[off + before] = id;
+            if (fout) fout[off + before] = base + t;
+        }
+        __syncthreads();
+        if (tid == 0) s_base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ntok[b] = s_base;
+        if (T > 0) { state[b].prev = ids[T - 1]; state[b].base = base + T; }
+    }
+}
+
 // log-softmax of one row per wave.  RC 16-byte chunks per lane live in registers between the reduction and the write
 // (one read of HBM); rows longer than 64 * RC chunks (or not 16-byte aligned) take the three-sweep path, whose second
 // and third sweeps hit the cache.
@@ -185,6 +243,43 @@ extern "C" int pafc_ctc_greedy(int dtype, int B, int T, int V, const void *score
         hipLaunchKernelGGL((pafc::ctc_argmax_kernel<float>), dim3((unsigned)nblk), dim3(256), 0, s, rows, T, V,
                            (const float *)scores, lens, blank_id, best);
     hipLaunchKernelGGL(pafc::ctc_collapse_kernel, dim3(B), dim3(256), 0, s, T, blank_id, best, tokens, ntok, frames);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+extern "C" size_t pafc_ctc_greedy_stream_workspace_bytes(int B) {
+    return B <= 0 ? 0 : (size_t)B * sizeof(pafc::GreedyRow);
+}
+
+extern "C" int pafc_ctc_greedy_stream_reset(int B, const int32_t *row_mask, void *workspace, size_t workspace_bytes,
+                                            pafc_stream_t stream) {
+    if (!workspace) return PAFC_ERR_NULL_POINTER;
+    if (B <= 0) return PAFC_ERR_BAD_DIMS;
+    if (workspace_bytes < pafc_ctc_greedy_stream_workspace_bytes(B)) return PAFC_ERR_WORKSPACE;
+    hipLaunchKernelGGL(pafc::ctc_greedy_stream_reset_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, row_mask,
+                       (pafc::GreedyRow *)workspace);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+extern "C" int pafc_ctc_greedy_stream(int dtype, int B, int Tmax, int V, const void *scores, const int64_t *nframes, int blank_id,
+                                      void *workspace, size_t workspace_bytes, int32_t *best, int32_t *tokens, int32_t *ntok,
+                                      int64_t *frames, pafc_stream_t stream) {
+    if (!scores || !nframes || !workspace || !best || !tokens || !ntok) return PAFC_ERR_NULL_POINTER;
+    if (B <= 0 || Tmax <= 0 || V <= 0 || blank_id < 0 || blank_id >= V) return PAFC_ERR_BAD_DIMS;
+    if (dtype != PAFC_F32 && dtype != PAFC_BF16) return PAFC_ERR_DTYPE;
+    if (workspace_bytes < pafc_ctc_greedy_stream_workspace_bytes(B)) return PAFC_ERR_WORKSPACE;
+    const long rows = (long)B * Tmax;
+    const long nblk = (rows + 3) / 4;
+    if (nblk > 0x7fffffffL) return PAFC_ERR_BAD_DIMS;
+    hipStream_t s = (hipStream_t)stream;
+    // the offline argmax kernel, the chunk's frame counts as lengths: rows beyond them are not read
+    if (dtype == PAFC_BF16)
+        hipLaunchKernelGGL((pafc::ctc_argmax_kernel<pafc::bf16_t>), dim3((unsigned)nblk), dim3(256), 0, s, rows, Tmax, V,
+                           (const pafc::bf16_t *)scores, nframes, blank_id, best);
+    else
+        hipLaunchKernelGGL((pafc::ctc_argmax_kernel<float>), dim3((unsigned)nblk), dim3(256), 0, s, rows, Tmax, V,
+                           (const float *)scores, nframes, blank_id, best);
+    hipLaunchKernelGGL(pafc::ctc_collapse_stream_kernel, dim3(B), dim3(256), 0, s, Tmax, blank_id, nframes,
+                       (pafc::GreedyRow *)workspace, best, tokens, ntok, frames);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 

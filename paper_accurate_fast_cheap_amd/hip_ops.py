@@ -2452,6 +2452,17 @@ class _CtxGraph(ctypes.Structure):
                 ("fail", c_void_p), ("token_score", c_void_p), ("node_score", c_void_p), ("output_score", c_void_p)]
 
 
+def _ctx_graph(g: dict, dev, who: str) -> _CtxGraph:
+    """The C struct over ContextGraph.device_tables(dev); the tables must outlive it."""
+    for k, dt in (("child_begin", torch.int32), ("child_token", torch.int32), ("child_node", torch.int32),
+                  ("fail", torch.int32), ("token_score", torch.float64), ("node_score", torch.float64),
+                  ("output_score", torch.float64)):
+        if g[k].dtype != dt or g[k].device != dev or not g[k].is_contiguous():
+            raise _lib.PafcError(f"{who}: graph table {k} must be contiguous {dt} on {dev}")
+    return _CtxGraph(int(g["fail"].numel()), *[_lib.ptr(g[k]) for k in ("child_begin", "child_token", "child_node", "fail",
+                                                                        "token_score", "node_score", "output_score")])
+
+
 def ctc_prefix_beam(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optional[torch.Tensor], beam: int,
                     blank_id: int = 0, graph_tables: Optional[dict] = None, want_times: bool = True):
     """GPU-resident CTC prefix beam search (include/pafc_search.h: pafc_ctc_prefix_beam_search_ex).  top_logp (B, T, K)
@@ -2466,17 +2477,7 @@ def ctc_prefix_beam(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optiona
     idx32 = top_idx.to(torch.int32).contiguous()
     lens64 = None if lens is None else lens.to(torch.int64).contiguous()
     dev = top_logp.device
-    graph = None
-    if graph_tables is not None:
-        g = graph_tables
-        for k, dt in (("child_begin", torch.int32), ("child_token", torch.int32), ("child_node", torch.int32),
-                      ("fail", torch.int32), ("token_score", torch.float64), ("node_score", torch.float64),
-                      ("output_score", torch.float64)):
-            if g[k].dtype != dt or g[k].device != dev or not g[k].is_contiguous():
-                raise _lib.PafcError(f"ctc_prefix_beam: graph table {k} must be contiguous {dt} on {dev}")
-        graph = _CtxGraph(int(g["fail"].numel()), *[_lib.ptr(g[k]) for k in ("child_begin", "child_token", "child_node",
-                                                                              "fail", "token_score", "node_score",
-                                                                              "output_score")])
+    graph = None if graph_tables is None else _ctx_graph(graph_tables, dev, "ctc_prefix_beam")
     nws = L.pafc_ctc_prefix_beam_ex_workspace_bytes(B, T, beam)
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
     tokens = torch.empty(B, beam, T, dtype=torch.int32, device=dev)
@@ -2490,6 +2491,203 @@ def ctc_prefix_beam(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optiona
                                                 _lib.ptr(ws), nws, _lib.stream_of(top_logp)),
                "pafc_ctc_prefix_beam_search_ex")
     return tokens, lengths, scores, times
+
+
+class CtcBeamStream:
+    """CTC prefix beam search of B streams chunk by chunk (include/pafc_search.h: pafc_ctc_beam_stream_*,
+    csrc/ctc_beam_stream.hip): the beam of every stream lives in the workspace between feeds, and the n-best lists over a
+    stream equal ctc_prefix_beam on the concatenated frames bit for bit.  The object owns the workspace, the fixed
+    (B, Tmax, K) top-k buffers, the frame counts and the `from` offsets.
+
+    feed(top_logp (B, n <= Tmax, K), top_idx, nframes=None) copies the chunk into the fixed buffers and launches the feed
+    kernel; launch_feed() is that launch alone, on whatever the buffers hold -- nothing but the package's kernel, so it
+    can be captured in a graph.  drain(counts, ld) returns host lists: the one read of a feed.  A row that would pass
+    max_total_frames consumes nothing and is reported by drain's `overflow`; reset(rows) starts rows again."""
+
+    def __init__(self, B: int, Tmax: int, K: int, beam: int, device, blank_id: int = 0, graph_tables: Optional[dict] = None,
+                 max_total_frames: int = 4096, want_times: bool = True):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.PafcError(f"CtcBeamStream runs on the MI355X only (device {dev}); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if B < 1 or Tmax < 1 or max_total_frames < 1:
+            raise _lib.PafcError(f"CtcBeamStream: B {B}, Tmax {Tmax}, max_total_frames {max_total_frames} must be >= 1")
+        if not 1 <= beam <= 16 or not 1 <= K <= 16:
+            raise _lib.PafcError(f"CtcBeamStream: beam {beam} and K {K} must be in 1 .. 16")
+        self.B, self.Tmax, self.K, self.beam, self.blank, self.device = B, Tmax, K, beam, int(blank_id), dev
+        self.max_total, self.times = int(max_total_frames), int(bool(want_times))
+        self._L = _lib.lib()
+        self._tables = graph_tables
+        self._graph = None if graph_tables is None else _ctx_graph(graph_tables, dev, "CtcBeamStream")
+        self._pgraph = None if self._graph is None else ctypes.addressof(self._graph)
+        self._nbytes = self._L.pafc_ctc_beam_stream_workspace_bytes(B, self.max_total, beam, self.times)
+        if self._nbytes == 0:
+            raise _lib.PafcError("pafc_ctc_beam_stream_workspace_bytes: unsupported dimensions (max_total_frames * beam < 2^31)")
+        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self._top_p = torch.zeros(B, Tmax, K, dtype=torch.float32, device=dev)
+        self._top_i = torch.zeros(B, Tmax, K, dtype=torch.int32, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._from = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._from_h = [0] * B
+        self.last_read_bytes = 0
+        self.reset()
+
+    def reset(self, rows=None):
+        """Restart the given rows (all when None) from the empty prefix at frame 0; other rows are untouched."""
+        mask = None
+        if rows is not None:
+            m = torch.zeros(self.B, dtype=torch.int32)
+            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
+            self._mask.copy_(m)
+            mask = _lib.ptr(self._mask)
+        _lib.check(self._L.pafc_ctc_beam_stream_reset(self.B, self.max_total, self.beam, self.times, mask, _lib.ptr(self._ws),
+                                                       self._nbytes, _lib.stream_of(self._ws)), "pafc_ctc_beam_stream_reset")
+
+    def launch_feed(self):
+        """The feed kernel on the fixed buffers (top-k, frame counts): reads nothing from the host, allocates nothing."""
+        _lib.check(self._L.pafc_ctc_beam_stream_feed(self.B, self.Tmax, self.K, _lib.ptr(self._top_p), _lib.ptr(self._top_i),
+                                                      _lib.ptr(self._nf), self.max_total, self.beam, self.blank, self._pgraph,
+                                                      self.times, _lib.ptr(self._ws), self._nbytes, _lib.stream_of(self._ws)),
+                   "pafc_ctc_beam_stream_feed")
+
+    def load(self, top_logp: torch.Tensor, top_idx: torch.Tensor, nframes=None):
+        """Copy a chunk's top-k (B, n <= Tmax, K) and its frame counts (default n for every row) into the fixed buffers."""
+        B, Tmax, K = self.B, self.Tmax, self.K
+        if top_logp.dim() != 3 or top_logp.shape != top_idx.shape or top_logp.shape[0] != B or top_logp.shape[2] != K:
+            raise _lib.PafcError(f"CtcBeamStream.feed: top_logp and top_idx must be ({B}, n, {K})")
+        n = top_logp.shape[1]
+        if n > Tmax:
+            raise _lib.PafcError(f"CtcBeamStream.feed: {n} frames, at most Tmax = {Tmax}")
+        if top_logp.device != self.device or top_idx.device != self.device or top_logp.dtype != torch.float32:
+            raise _lib.PafcError(f"CtcBeamStream.feed: top_logp float32 and top_idx on {self.device}")
+        if n:
+            self._top_p[:, :n].copy_(top_logp)
+            self._top_i[:, :n].copy_(top_idx)
+        if nframes is None:
+            self._nf.fill_(n)
+        else:
+            nf = torch.as_tensor(nframes, dtype=torch.int64)
+            if nf.shape != (B,):
+                raise _lib.PafcError(f"CtcBeamStream.feed: nframes must be ({B},)")
+            self._nf.copy_(nf.clamp(0, n))
+
+    def feed(self, top_logp: torch.Tensor, top_idx: torch.Tensor, nframes=None):
+        self.load(top_logp, top_idx, nframes)
+        self.launch_feed()
+
+    def drain(self, counts=None, ld: int = 1, want_times: bool = False):
+        """The n-best of every row as if its stream ended here.  counts: per row the tokens the caller already holds as
+        final (an earlier drain's `committed`), default 0.  Returns a dict of host lists: count (B), committed (B),
+        overflow (B), len (B, beam: total token counts, -1 unused), score (B, beam), tokens (B, beam: the tokens from
+        counts[b] on, at most ld of them) and, with want_times, times (B, beam: the whole frame list)."""
+        B, beam = self.B, self.beam
+        counts = [0] * B if counts is None else [int(c) for c in counts]
+        if counts != self._from_h:
+            self._from.copy_(torch.tensor(counts, dtype=torch.int32))
+            self._from_h = counts
+        if want_times and not self.times:
+            raise _lib.PafcError("CtcBeamStream.drain: the stream was made with want_times=False")
+        ld = max(1, int(ld))
+        # one buffer, one read: score (B, beam) f64 | len (B, beam) | count | committed | overflow (B) | tokens (B, beam, ld) i32
+        nb = B * beam
+        o = [0, nb * 8]
+        for words in (nb, B, B, B, nb * ld):
+            o.append(o[-1] + 4 * words)
+        out = torch.empty(o[-1], dtype=torch.uint8, device=self.device)
+        ntim = tim = None
+        if want_times:               # the frame lists' lengths first: they size the second call's copy
+            ntim = torch.empty(B, beam, dtype=torch.int32, device=self.device)
+            self._drain(out, o, ld, 0, None, ntim)
+            ldt = max(1, int(ntim.max()))
+            tim = torch.empty(B, beam, ldt, dtype=torch.int32, device=self.device)
+            self._drain(out, o, ld, ldt, tim, ntim)
+        else:
+            self._drain(out, o, ld, 0, None, None)
+        h = out.cpu()                                  # the read
+        self.last_read_bytes = o[-1]
+        i32 = lambda k, *shape: h[o[k]:o[k + 1]].view(torch.int32).view(*shape)
+        lens = i32(1, B, beam).tolist()
+        toks = i32(5, B, beam, ld).tolist()
+        res = {"score": h[:o[1]].view(torch.float64).view(B, beam).tolist(), "len": lens, "count": i32(2, B).tolist(),
+               "committed": i32(3, B).tolist(), "overflow": i32(4, B).tolist(),
+               "tokens": [[toks[b][n][:max(0, min(ld, lens[b][n] - counts[b]))] for n in range(beam)] for b in range(B)]}
+        if want_times:
+            nt_h, tm_h = ntim.tolist(), tim.tolist()
+            res["times"] = [[tm_h[b][n][:nt_h[b][n]] for n in range(beam)] for b in range(B)]
+        return res
+
+    def _drain(self, out, o, ld, ldt, tim, ntim):
+        p = lambda k: _lib.ptr(out[o[k]:o[k + 1]])
+        _lib.check(self._L.pafc_ctc_beam_stream_drain(self.B, self.max_total, self.beam, self._pgraph, self.times,
+                                                       _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._from), ld, p(5), p(1),
+                                                       p(0), p(2), p(3), p(4), ldt, _lib.ptr(tim), _lib.ptr(ntim),
+                                                       _lib.stream_of(self._ws)), "pafc_ctc_beam_stream_drain")
+
+
+class CtcGreedyStream:
+    """CTC greedy search of B streams chunk by chunk (pafc_ctc_greedy_stream, csrc/ctc_greedy.hip): the offline argmax
+    kernel on the chunk and a collapse that carries the previous frame's argmax and the frame base per row, so the tokens
+    and absolute frames over a stream equal ctc_greedy(want_frames=True) on the concatenated frames."""
+
+    def __init__(self, B: int, Tmax: int, device, blank_id: int = 0):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.PafcError(f"CtcGreedyStream runs on the MI355X only (device {dev}); there is no CPU fallback")
+        if B < 1 or Tmax < 1:
+            raise _lib.PafcError(f"CtcGreedyStream: B {B} and Tmax {Tmax} must be >= 1")
+        self.B, self.Tmax, self.blank, self.device = B, Tmax, int(blank_id), dev
+        self._L = _lib.lib()
+        self._nbytes = self._L.pafc_ctc_greedy_stream_workspace_bytes(B)
+        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self._best = torch.empty(B, Tmax, dtype=torch.int32, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
+        # one buffer, one read: frames (B, Tmax) i64 | ntok (B) i32 | tokens (B, Tmax) i32
+        self._o = (B * Tmax * 8, B * Tmax * 8 + B * 4)
+        self._out = torch.empty(self._o[1] + B * Tmax * 4, dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def reset(self, rows=None):
+        mask = None
+        if rows is not None:
+            m = torch.zeros(self.B, dtype=torch.int32)
+            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
+            self._mask.copy_(m)
+            mask = _lib.ptr(self._mask)
+        _lib.check(self._L.pafc_ctc_greedy_stream_reset(self.B, mask, _lib.ptr(self._ws), self._nbytes, _lib.stream_of(self._ws)),
+                   "pafc_ctc_greedy_stream_reset")
+
+    def feed(self, scores: torch.Tensor, nframes=None):
+        """scores (B, n <= Tmax, V) float32 / bfloat16.  Returns (tokens, frames): per row what this chunk adds."""
+        B, Tmax = self.B, self.Tmax
+        if scores.dim() != 3 or scores.shape[0] != B or scores.shape[1] > Tmax:
+            raise _lib.PafcError(f"CtcGreedyStream.feed: the chunk must be ({B}, n <= {Tmax}, V)")
+        if scores.device != self.device:
+            raise _lib.PafcError(f"CtcGreedyStream.feed: the chunk is not on {self.device}")
+        n, V = scores.shape[1], scores.shape[2]
+        if n == 0:
+            return [[] for _ in range(B)], [[] for _ in range(B)]
+        scores = scores.contiguous()
+        if nframes is None:
+            self._nf.fill_(n)
+        else:
+            nf = torch.as_tensor(nframes, dtype=torch.int64)
+            if nf.shape != (B,):
+                raise _lib.PafcError(f"CtcGreedyStream.feed: nframes must be ({B},)")
+            self._nf.copy_(nf.clamp(0, n))
+        o1, o2 = self._o
+        out = self._out                                    # rows of n: the chunk's own frame count is the row stride
+        _lib.check(self._L.pafc_ctc_greedy_stream(_lib.dtype_code(scores.dtype), B, n, V, _lib.ptr(scores), _lib.ptr(self._nf),
+                                                   self.blank, _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._best),
+                                                   _lib.ptr(out[o2:]), _lib.ptr(out[o1:o2]), _lib.ptr(out[:o1]),
+                                                   _lib.stream_of(scores)), "pafc_ctc_greedy_stream")
+        h = out.cpu()
+        cnt = h[o1:o2].view(torch.int32).tolist()
+        fr = h[:B * n * 8].view(torch.int64).view(B, n)
+        tk = h[o2:o2 + B * n * 4].view(torch.int32).view(B, n)
+        return [tk[b, :cnt[b]].tolist() for b in range(B)], [fr[b, :cnt[b]].tolist() for b in range(B)]
 
 
 class RnntBeamState:

@@ -130,33 +130,13 @@ class Transducer(ASRModel):
     @torch.no_grad()
     def stream_greedy_search(self, speech: torch.Tensor, decoding_chunk_size: int, n_steps: int = 64,
                              on_tokens: Optional[Callable[[int, List[List[int]]], None]] = None) -> List[DecodeResult]:
-        """Streaming greedy search of B equal-length streams (B, T, F), the contract of encoder.stream_chunks: the windows of
-        forward_chunk_by_chunk through the encoder with carried state -- forward_chunk_carry for a causal conv module (or
-        none), forward_chunk_lookahead for the shipped non-causal one, drained with final=True after the last window --
-        and each window's output frames into one GreedyStreamer.  on_tokens(window_index, new_tokens_per_row) is called
-        after every window.  Returns per stream the tokens, their absolute frames and the path score.  Over the stream the
+        """Streaming greedy search of B equal-length streams (B, T, F): the window walk of ASRModel._stream_windows (the
+        encoder with carried state, drained after the last window) and each window's output frames into one
+        GreedyStreamer.  on_tokens(window_index, new_tokens_per_row) is called after every window.  Returns per stream the tokens, their absolute frames and the path score.  Over the stream the
         decisions equal batch_greedy_search of the concatenated encoder outputs of the same steps."""
-        if decoding_chunk_size <= 0:
-            raise ValueError("stream_greedy_search: decoding_chunk_size must be > 0 (a chunked stream)")
-        from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
-        enc = self.encoder
-        layers = list(getattr(enc, "encoders", []))
-        if not layers or any(type(l.self_attn) is not RWKV_TmixWrapper for l in layers) or not enc.normalize_before:
-            raise ValueError("stream_greedy_search: the encoder must be a pre-norm uni-directional model (rwkv_tmix60 slot); "
-                             "a bidirectional encoder needs the whole utterance")
-        lookahead = any(l.conv_module is not None and l.conv_module.lorder == 0 for l in layers)
-        sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
-        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
-        T = speech.size(1)
-        starts = list(range(0, T - ctx + 1, stride))
+        windows = self._stream_windows(speech, decoding_chunk_size, "stream_greedy_search")
         streamer = GreedyStreamer(self, speech.size(0), decoding_chunk_size, n_steps)
-        state = None
-        for i, c in enumerate(starts):
-            xs = speech[:, c:min(c + window, T)]
-            if lookahead:
-                y, state = enc.forward_chunk_lookahead(xs, state, final=(i == len(starts) - 1))
-            else:
-                y, state = enc.forward_chunk_carry(xs, 0, state)
+        for i, y in windows:
             new: List[List[int]] = [[] for _ in range(speech.size(0))]
             for a in range(0, y.size(1), decoding_chunk_size):      # (the final drain of the look-ahead emits more frames)
                 for b, tk in enumerate(streamer.feed(y[:, a:a + decoding_chunk_size])):

@@ -2,7 +2,7 @@
 `.encoder`, `.ctc`, `_forward_encoder` (asr_model.py:294-321), `ctc_logprobs` (:324-335) and `decode` for the
 CTC modes (:337-440).  The attention decoder, RNN-T predictor/joint and their losses are containers around the
 path, not the path; transducer decoding joins in paper_accurate_fast_cheap_amd/transducer."""
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, Iterator, List, Optional, Tuple
 
 import torch
 
@@ -70,3 +70,58 @@ class ASRModel(torch.nn.Module):
             else:
                 raise NotImplementedError(f"decode mode {m!r} is outside the accelerated path")
         return results
+
+    def _stream_windows(self, speech: torch.Tensor, decoding_chunk_size: int, who: str) -> Iterator[Tuple[int, torch.Tensor]]:
+        """The window walk of a chunked stream, the contract of encoder.stream_chunks: the windows of forward_chunk_by_chunk
+        through the encoder with carried state -- forward_chunk_carry for a causal conv module (or none),
+        forward_chunk_lookahead for the shipped non-causal one, drained with final=True after the last window.  Yields
+        (window index, the window's output frames (B, n, D)); the final drain of the look-ahead emits more frames than
+        decoding_chunk_size."""
+        if decoding_chunk_size <= 0:
+            raise ValueError(f"{who}: decoding_chunk_size must be > 0 (a chunked stream)")
+        from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
+        enc = self.encoder
+        layers = list(getattr(enc, "encoders", []))
+        if not layers or any(type(l.self_attn) is not RWKV_TmixWrapper for l in layers) or not enc.normalize_before:
+            raise ValueError(f"{who}: the encoder must be a pre-norm uni-directional model (rwkv_tmix60 slot); "
+                             "a bidirectional encoder needs the whole utterance")
+        lookahead = any(l.conv_module is not None and l.conv_module.lorder == 0 for l in layers)
+        sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
+        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
+        T = speech.size(1)
+        starts = list(range(0, T - ctx + 1, stride))
+
+        def walk():
+            state = None
+            for i, c in enumerate(starts):
+                xs = speech[:, c:min(c + window, T)]
+                if lookahead:
+                    y, state = enc.forward_chunk_lookahead(xs, state, final=(i == len(starts) - 1))
+                else:
+                    y, state = enc.forward_chunk_carry(xs, 0, state)
+                yield i, y
+        return walk()
+
+    @torch.no_grad()
+    def stream_ctc_search(self, speech: torch.Tensor, decoding_chunk_size: int, mode: str = "ctc_prefix_beam_search",
+                          beam_size: int = 10, context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0,
+                          on_partial: Optional[Callable[[int, List[DecodeResult], List[List[int]]], None]] = None,
+                          max_total_frames: Optional[int] = None) -> List[DecodeResult]:
+        """Streaming CTC search (mode: ctc_prefix_beam_search or ctc_greedy_search) of B equal-length streams (B, T, F):
+        the window walk of _stream_windows, each window's frames through ctc_logprobs into one search.CtcStreamer.
+        on_partial(window_index, partial_results, committed_tokens_per_row) is called once per window.  Returns per
+        stream the full DecodeResult (times included).  Over the stream the result equals the offline search of
+        ctc_logprobs of the concatenated encoder outputs of the same steps.  max_total_frames (default: what the speech
+        can produce) sizes the beam search's pools."""
+        from .search import CtcStreamer
+        windows = self._stream_windows(speech, decoding_chunk_size, "stream_ctc_search")
+        if max_total_frames is None:
+            max_total_frames = speech.size(1) // self.encoder.embed.subsampling_rate + decoding_chunk_size
+        streamer = CtcStreamer(speech.size(0), decoding_chunk_size, mode, beam_size, context_graph, blank_id, max_total_frames)
+        for i, y in windows:
+            partial = None                                      # (a window may come without output frames)
+            for a in range(0, y.size(1), decoding_chunk_size):
+                partial = streamer.feed(self.ctc_logprobs(y[:, a:a + decoding_chunk_size], blank_penalty, blank_id))
+            if on_partial is not None:
+                on_partial(i, partial if partial is not None else streamer.partials(), [list(c) for c in streamer.committed])
+        return streamer.results()

@@ -116,6 +116,87 @@ class _PrefixScore:
         self.context_state = state
 
 
+class _BeamRow:
+    """The host loop's variables for one stream, kept between calls of _prefix_beam_resume: the current beam (prefix,
+    score) best first, and the number of frames consumed."""
+    __slots__ = ("cur", "base")
+
+    def __init__(self, graph):
+        self.cur = [(tuple(), _PrefixScore(s=0.0, ns=-float("inf"), v_s=0.0, v_ns=0.0,
+                                           context_state=None if graph is None else graph.root, context_score=0.0))]
+        self.base = 0
+
+
+def _prefix_beam_resume(r: _BeamRow, top_p, top_i, nframes: int, beam_size: int, graph, blank_id: int):
+    """The reference's loop (search.py:150-222) over frames [0, nframes) of one utterance's top-k lists, resumed from r and left
+    in r; the frame lists record r.base + j.  One call over all frames is the offline search; calls over consecutive
+    pieces do the same arithmetic in the same order, since nothing but the beam lives from one frame to the next."""
+    cur = r.cur
+    for j in range(nframes):
+        t = r.base + j
+        nxt = defaultdict(_PrefixScore)
+        for prob, u in zip(top_p[j], top_i[j]):
+            for prefix, ps in cur:
+                last = prefix[-1] if len(prefix) > 0 else None
+                if u == blank_id:
+                    n = nxt[prefix]
+                    n.s = log_add([n.s, ps.score() + prob])
+                    n.v_s = ps.viterbi_score() + prob
+                    n.times_s = ps.times().copy()
+                    if graph is not None and not n.has_context:
+                        n.copy_context(ps)
+                        n.has_context = True
+                elif u == last:
+                    n1 = nxt[prefix]                       # *uu -> *u
+                    n1.ns = log_add([n1.ns, ps.ns + prob])
+                    # the reference assigns a misspelt attribute here (search.py:186), so v_ns stays as it is
+                    if n1.v_ns < ps.v_ns + prob and n1.cur_token_prob < prob:
+                        n1.cur_token_prob = prob
+                        n1.times_ns = ps.times_ns.copy()
+                        n1.times_ns[-1] = t
+                    if graph is not None and not n1.has_context:
+                        n1.copy_context(ps)
+                        n1.has_context = True
+                    n2 = nxt[prefix + (u,)]                # *u-u -> *uu
+                    n2.ns = log_add([n2.ns, ps.s + prob])
+                    if n2.v_ns < ps.v_s + prob:
+                        n2.v_ns = ps.v_s + prob
+                        n2.cur_token_prob = prob
+                        n2.times_ns = ps.times_s.copy()
+                        n2.times_ns.append(t)
+                    if graph is not None and not n2.has_context:
+                        n2.update_context(graph, ps, u)
+                        n2.has_context = True
+                else:
+                    n = nxt[prefix + (u,)]
+                    n.ns = log_add([n.ns, ps.score() + prob])
+                    if n.v_ns < ps.viterbi_score() + prob:
+                        n.v_ns = ps.viterbi_score() + prob
+                        n.cur_token_prob = prob
+                        n.times_ns = ps.times().copy()
+                        n.times_ns.append(t)
+                    if graph is not None and not n.has_context:
+                        n.update_context(graph, ps, u)
+                        n.has_context = True
+        cur = sorted(nxt.items(), key=lambda x: x[1].total_score(), reverse=True)[:beam_size]
+    r.cur = cur
+    r.base += nframes
+
+
+def _prefix_beam_result(r: _BeamRow, graph) -> DecodeResult:
+    """The n-best of a stream that ends here.  With a graph each survivor's bonus is replaced by its finalize() value
+    (partial matches are backed off; the order is NOT revisited, search.py:224-231) -- on a copy, r goes on unchanged."""
+    cur = r.cur
+    nbest = [tuple(y[0]) for y in cur]
+    if graph is not None:
+        nbest_scores = [y[1].score() + graph.finalize(y[1].context_state)[0] for y in cur]
+    else:
+        nbest_scores = [y[1].total_score() for y in cur]
+    nbest_times = [list(y[1].times()) for y in cur]
+    return DecodeResult(tokens=nbest[0], score=nbest_scores[0], times=nbest_times[0], nbest=nbest,
+                        nbest_scores=nbest_scores, nbest_times=nbest_times)
+
+
 def ctc_prefix_beam_search(ctc_probs: torch.Tensor, ctc_lens: torch.Tensor, beam_size: int, context_graph=None,
                            blank_id: int = 0) -> List[DecodeResult]:
     """search.py:124-248.  The per-frame top-`beam` tokens of the WHOLE batch are taken in one device op and
@@ -152,63 +233,205 @@ def ctc_prefix_beam_search(ctc_probs: torch.Tensor, ctc_lens: torch.Tensor, beam
                                         nbest_times=ntimes))
         return results
     top_p, top_i, lens = top_p.cpu().tolist(), top_i.cpu().tolist(), [int(v) for v in ctc_lens.tolist()]
-    graph = context_graph
     results = []
     for b in range(B):
-        cur = [(tuple(), _PrefixScore(s=0.0, ns=-float("inf"), v_s=0.0, v_ns=0.0,
-                                      context_state=None if graph is None else graph.root, context_score=0.0))]
-        for t in range(lens[b]):
-            nxt = defaultdict(_PrefixScore)
-            for prob, u in zip(top_p[b][t], top_i[b][t]):
-                for prefix, ps in cur:
-                    last = prefix[-1] if len(prefix) > 0 else None
-                    if u == blank_id:
-                        n = nxt[prefix]
-                        n.s = log_add([n.s, ps.score() + prob])
-                        n.v_s = ps.viterbi_score() + prob
-                        n.times_s = ps.times().copy()
-                        if graph is not None and not n.has_context:
-                            n.copy_context(ps)
-                            n.has_context = True
-                    elif u == last:
-                        n1 = nxt[prefix]                       # *uu -> *u
-                        n1.ns = log_add([n1.ns, ps.ns + prob])
-                        # the reference assigns a misspelt attribute here (search.py:186), so v_ns stays as it is
-                        if n1.v_ns < ps.v_ns + prob and n1.cur_token_prob < prob:
-                            n1.cur_token_prob = prob
-                            n1.times_ns = ps.times_ns.copy()
-                            n1.times_ns[-1] = t
-                        if graph is not None and not n1.has_context:
-                            n1.copy_context(ps)
-                            n1.has_context = True
-                        n2 = nxt[prefix + (u,)]                # *u-u -> *uu
-                        n2.ns = log_add([n2.ns, ps.s + prob])
-                        if n2.v_ns < ps.v_s + prob:
-                            n2.v_ns = ps.v_s + prob
-                            n2.cur_token_prob = prob
-                            n2.times_ns = ps.times_s.copy()
-                            n2.times_ns.append(t)
-                        if graph is not None and not n2.has_context:
-                            n2.update_context(graph, ps, u)
-                            n2.has_context = True
-                    else:
-                        n = nxt[prefix + (u,)]
-                        n.ns = log_add([n.ns, ps.score() + prob])
-                        if n.v_ns < ps.viterbi_score() + prob:
-                            n.v_ns = ps.viterbi_score() + prob
-                            n.cur_token_prob = prob
-                            n.times_ns = ps.times().copy()
-                            n.times_ns.append(t)
-                        if graph is not None and not n.has_context:
-                            n.update_context(graph, ps, u)
-                            n.has_context = True
-            cur = sorted(nxt.items(), key=lambda x: x[1].total_score(), reverse=True)[:beam_size]
-        if graph is not None:            # back off partial matches; the order is NOT revisited (search.py:224-231)
-            for _, ps in cur:
-                ps.context_score, ps.context_state = graph.finalize(ps.context_state)
-        nbest = [tuple(y[0]) for y in cur]
-        nbest_scores = [y[1].total_score() for y in cur]
-        nbest_times = [y[1].times() for y in cur]
-        results.append(DecodeResult(tokens=nbest[0], score=nbest_scores[0], times=nbest_times[0], nbest=nbest,
-                                    nbest_scores=nbest_scores, nbest_times=nbest_times))
+        r = _BeamRow(context_graph)
+        _prefix_beam_resume(r, top_p[b], top_i[b], lens[b], beam_size, context_graph, blank_id)
+        results.append(_prefix_beam_result(r, context_graph))
     return results
+
+
+def _common_prefix_len(lists) -> int:
+    n = min(len(x) for x in lists)
+    for i in range(n):
+        if any(x[i] != lists[0][i] for x in lists[1:]):
+            return i
+    return n
+
+
+STREAM_MODES = ("ctc_prefix_beam_search", "ctc_greedy_search")
+
+
+class CtcStreamer:
+    """CTC greedy or prefix beam search of `batch_size` streams fed chunk by chunk.  Over a stream, for any cut of its
+    frames into chunks, the result equals the offline function on the concatenated frames: tokens and times exactly, and
+    scores bit for bit where both sides run the same arithmetic (host loop against host loop, kernel against kernel).
+
+    feed(ctc_logp_chunk (B, n <= max_frames, V), nframes=None): row b consumes its first nframes[b] frames (default n;
+    0 = the row sits the chunk out).  The chunk's top-k is taken exactly as the offline function takes it.  Returns per row
+    a partial DecodeResult -- the 1-best and n-best tokens and scores if the stream ended here (with a context graph the
+    finalize value is applied to a copy; greedy: the tokens and frames so far) -- without times.  `.committed` holds per
+    row the tokens that can no longer change: the common prefix of the row's n-best.  Every later hypothesis extends a
+    member of the beam, so a committed token is final; the list only grows.
+    reset(rows=None) restarts rows (all when None) from their next chunk on.
+    results(): per row the full DecodeResult, times / nbest_times included.
+    max_total_frames: the most frames a row may take between resets (the beam search's node pools are sized by it and are
+    not compacted: reset a row at an endpoint).  A feed that would pass it leaves that row as it was -- the row takes no
+    more frames until its reset --, serves the other rows, and raises PafcError naming the rows.
+    GPU tensors run on hip_ops.CtcBeamStream / CtcGreedyStream (PafcError otherwise, never a fallback); CPU tensors, and
+    beam_size > 16 as in the offline function, run the host loop (_prefix_beam_resume, the function the offline host
+    path calls once per utterance)."""
+
+    def __init__(self, batch_size: int, max_frames: int, mode: str = "ctc_prefix_beam_search", beam_size: int = 10,
+                 context_graph=None, blank_id: int = 0, max_total_frames: int = 4096):
+        if mode not in STREAM_MODES:
+            raise ValueError(f"CtcStreamer: mode must be one of {STREAM_MODES}, got {mode!r}")
+        if batch_size < 1 or max_frames < 1 or max_total_frames < 1 or beam_size < 1:
+            raise ValueError("CtcStreamer: batch_size, max_frames, max_total_frames and beam_size must be >= 1")
+        self.B, self.Tmax, self.mode, self.beam, self.graph = batch_size, max_frames, mode, beam_size, context_graph
+        self.blank, self.max_total = blank_id, max_total_frames
+        self.greedy = mode == "ctc_greedy_search"
+        self._gpu = None                                   # made by the first feed of a GPU tensor
+        self._device = None
+        self.committed: List[List[int]] = [[] for _ in range(batch_size)]
+        self._rows: List[Optional[_BeamRow]] = [None] * batch_size
+        self._frames = [0] * batch_size                    # frames consumed per row
+        self._maxlen = [0] * batch_size                    # the longest token list of a row's beam
+        self._times: List[List[int]] = [[] for _ in range(batch_size)]      # greedy: frames of the committed tokens
+        self._prev = [-1] * batch_size                     # greedy on the host: the previous frame's argmax
+        self._full = [False] * batch_size                  # the row was refused frames: it takes no more until its reset
+        self.last_read_bytes = 0
+        self.reset()
+
+    def reset(self, rows=None):
+        rows = list(range(self.B)) if rows is None else [int(b) for b in rows]
+        for b in rows:
+            self.committed[b], self._times[b] = [], []
+            self._frames[b], self._maxlen[b], self._prev[b], self._full[b] = 0, 0, -1, False
+            self._rows[b] = None if self.greedy else _BeamRow(self.graph)
+        if self._gpu is not None:
+            self._gpu.reset(None if len(rows) == self.B else rows)
+
+    def _make_gpu(self, chunk: torch.Tensor):
+        from .. import hip_ops
+        if self.greedy:
+            return hip_ops.CtcGreedyStream(self.B, self.Tmax, chunk.device, self.blank)
+        tables = None if self.graph is None else self.graph.device_tables(chunk.device)
+        return hip_ops.CtcBeamStream(self.B, self.Tmax, min(self.beam, chunk.shape[-1]), self.beam, chunk.device, self.blank,
+                                     tables, self.max_total)
+
+    def feed(self, ctc_logp_chunk: torch.Tensor, nframes=None) -> List[DecodeResult]:
+        B = self.B
+        if ctc_logp_chunk.dim() != 3 or ctc_logp_chunk.shape[0] != B or ctc_logp_chunk.shape[1] > self.Tmax:
+            raise ValueError(f"CtcStreamer.feed: the chunk must be ({B}, n <= {self.Tmax}, V)")
+        n = ctc_logp_chunk.shape[1]
+        nf = [n] * B if nframes is None else [max(0, min(n, int(v))) for v in torch.as_tensor(nframes).tolist()]
+        if len(nf) != B:
+            raise ValueError(f"CtcStreamer.feed: nframes must be ({B},)")
+        on_gpu = ctc_logp_chunk.is_cuda and (self.greedy or self.beam <= 16)
+        if self._device is None:
+            self._device = ctc_logp_chunk.device
+            if on_gpu:
+                self._gpu = self._make_gpu(ctc_logp_chunk)
+        elif ctc_logp_chunk.device != self._device:
+            raise ValueError(f"CtcStreamer.feed: the stream began on {self._device}, this chunk is on {ctc_logp_chunk.device}")
+        over = [] if self.greedy else [b for b in range(B)      # (the greedy search keeps no pool)
+                                      if nf[b] > 0 and (self._full[b] or self._frames[b] + nf[b] > self.max_total)]
+        for b in over:
+            self._full[b] = True
+        if self.greedy:
+            out = self._feed_greedy(ctc_logp_chunk, nf, over)
+        elif self._gpu is not None:
+            out = self._feed_beam_gpu(ctc_logp_chunk, nf, over)
+        else:
+            out = self._feed_beam_host(ctc_logp_chunk, nf, over)
+        if over:
+            from .._lib import PafcError
+            raise PafcError(f"CtcStreamer.feed: rows {over} would pass max_total_frames = {self.max_total} and took no frames; "
+                            "reset them (the other rows were served)")
+        return out
+
+    # ---- greedy ------------------------------------------------------------------------------------------------
+    def _feed_greedy(self, chunk, nf, over):
+        nf = [0 if b in over else v for b, v in enumerate(nf)]
+        if self._gpu is not None:
+            toks, frames = self._gpu.feed(chunk, nf)
+        else:
+            best = chunk.argmax(dim=2).tolist()            # == topk(1), as in ctc_greedy_search
+            toks, frames = [], []
+            for b in range(self.B):
+                tk, fr, prev = [], [], self._prev[b]
+                for t in range(nf[b]):
+                    u = best[b][t]
+                    if u != self.blank and u != prev:
+                        tk.append(u)
+                        fr.append(self._frames[b] + t)
+                    prev = u
+                self._prev[b] = prev
+                toks.append(tk)
+                frames.append(fr)
+        for b in range(self.B):
+            self.committed[b] += toks[b]
+            self._times[b] += frames[b]
+            self._frames[b] += nf[b]
+        return self.partials()
+
+    # ---- prefix beam search ------------------------------------------------------------------------------------
+    def _feed_beam_host(self, chunk, nf, over):
+        k = min(self.beam, chunk.shape[-1])
+        top_p, top_i = chunk.float().topk(k, dim=-1)
+        top_p, top_i = top_p.cpu().tolist(), top_i.cpu().tolist()
+        for b in range(self.B):
+            if nf[b] and b not in over:
+                _prefix_beam_resume(self._rows[b], top_p[b], top_i[b], nf[b], self.beam, self.graph, self.blank)
+                self._frames[b] += nf[b]
+        return self.partials()
+
+    def _drain_gpu(self, ld: int, want_times: bool):
+        """One drain from the committed counts on; full token lists are the committed tokens + the returned tails."""
+        B = self.B
+        d = self._gpu.drain([len(c) for c in self.committed], ld, want_times)
+        self.last_read_bytes = self._gpu.last_read_bytes
+        out = []
+        for b in range(B):
+            live = range(d["count"][b])
+            head = tuple(self.committed[b])
+            nbest = [head + tuple(d["tokens"][b][n]) for n in live]
+            nsc = [d["score"][b][n] for n in live]
+            new = d["committed"][b] - len(head)
+            if new > 0:
+                self.committed[b] += d["tokens"][b][0][:new]
+            self._maxlen[b] = max(d["len"][b][n] for n in live)
+            ntimes = [d["times"][b][n] for n in live] if want_times else None
+            out.append(DecodeResult(tokens=nbest[0], score=nsc[0], times=ntimes[0] if want_times else None, nbest=nbest,
+                                    nbest_scores=nsc, nbest_times=ntimes))
+        return out, d["overflow"]
+
+    def _feed_beam_gpu(self, chunk, nf, over):
+        k = min(self.beam, chunk.shape[-1])
+        top_p, top_i = chunk.float().topk(k, dim=-1)
+        self._gpu.feed(top_p, top_i, nf)                    # (a row in `over` is refused by the kernel itself)
+        for b in range(self.B):
+            if b not in over:
+                self._frames[b] += nf[b]
+        # a list grows by at most one token per frame: the tails fit in the longest tail so far + n
+        out, flags = self._drain_gpu(self._tail() + chunk.shape[1], False)
+        for b in range(self.B):                             # the kernel's own flags say the same
+            if flags[b] and nf[b] > 0 and b not in over:
+                over.append(b)
+        return out
+
+    def _tail(self) -> int:
+        """The longest uncommitted tail of any row's token lists as of the last drain."""
+        return max(self._maxlen[b] - len(self.committed[b]) for b in range(self.B))
+
+    def partials(self) -> List[DecodeResult]:
+        """What the last feed returned: per row the result if the stream ended here, without times."""
+        if self.greedy:
+            return [DecodeResult(list(self.committed[b])) for b in range(self.B)]
+        if self._gpu is not None:
+            return self._drain_gpu(self._tail(), False)[0]
+        out = []
+        for b in range(self.B):
+            r = _prefix_beam_result(self._rows[b], self.graph)
+            self.committed[b] = list(r.nbest[0][:_common_prefix_len(r.nbest)])
+            r.times = r.nbest_times = None
+            out.append(r)
+        return out
+
+    def results(self) -> List[DecodeResult]:
+        if self.greedy:
+            return [DecodeResult(list(self.committed[b]), times=list(self._times[b])) for b in range(self.B)]
+        if self._gpu is not None:
+            return self._drain_gpu(self._tail(), True)[0]
+        return [_prefix_beam_result(r, self.graph) for r in self._rows]

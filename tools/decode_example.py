@@ -5,6 +5,12 @@ chain and its interfaces -- pass --checkpoint / --config of a real GigaSpeech mo
 
   python tools/decode_example.py [--config conf.yaml --checkpoint model.pt --bpe_model spm.model --units units.txt]
                                  [--mode ctc_prefix_beam_search --context_list_path hotwords.txt --context_graph_score 3.0]
+                                 [--stream 16]
+
+--stream CHUNK decodes one utterance as a stream instead (ASRModel.stream_ctc_search): the default model becomes the
+uni-directional encoder with a causal conv module, the encoder runs window by window with carried state, every CHUNK
+output frames go through the streaming CTC search, and the committed text -- the tokens that can no longer change --
+is printed as it grows, followed by the final result.
 """
 import argparse, io, os, sys
 import torch
@@ -28,6 +34,7 @@ def main(argv=None):
     ap.add_argument("--beam_size", type=int, default=8)
     ap.add_argument("--context_list_path", default="", help="hotword list, one phrase per line (prefix beam search)")
     ap.add_argument("--context_graph_score", type=float, default=0.0, help="bonus per matched hotword token")
+    ap.add_argument("--stream", type=int, default=0, metavar="CHUNK", help="stream one utterance in chunks of CHUNK encoder frames")
     args = ap.parse_args(argv)
     dev = torch.device("cuda")
     tok = RevBpeTokenizer(args.bpe_model, args.units, None)
@@ -35,7 +42,10 @@ def main(argv=None):
         import yaml
         configs = yaml.safe_load(open(args.config))
     else:   # the paper's encoder shape with a vocabulary that matches the tiny tokenizer fixture
-        configs = dict(encoder="conformer", encoder_conf=B.encoder_conf(), input_dim=80, output_dim=tok.vocab_size(),
+        conf = B.encoder_conf()
+        if args.stream:      # a stream needs the uni-directional encoder; a causal conv module needs no look-ahead
+            conf.update(selfattention_layer_type="rwkv_tmix60", rnn_att_direction="uni", causal=True, cnn_module_kernel=15)
+        configs = dict(encoder="conformer", encoder_conf=conf, input_dim=80, output_dim=tok.vocab_size(),
                        ctc="ctc", ctc_conf={"ctc_blank_id": 0}, model_conf={}, dataset_conf={})
 
     class A:
@@ -57,6 +67,8 @@ def main(argv=None):
     if args.context_list_path:
         from paper_accurate_fast_cheap_amd.utils.context_graph import ContextGraph
         context_graph = ContextGraph(args.context_list_path, tok.symbol_table, args.bpe_model, args.context_graph_score)
+    if args.stream:
+        return stream_one(model, tok, batch[1:2, :int(lens[1])], args, context_graph)
     with torch.no_grad():
         results = model.decode([args.mode], batch, lens, beam_size=args.beam_size,
                                context_graph=context_graph)[args.mode]
@@ -71,6 +83,25 @@ def main(argv=None):
     tot = scorer.overall()
     out.write("Overall -> %4.2f %% %s\n" % (tot.wer, tot.line()))
     print(out.getvalue(), end="")
+    return results
+
+
+def stream_one(model, tok, speech, args, context_graph):
+    shown = [0]
+
+    def on_partial(i, partial, committed):
+        if len(committed[0]) > shown[0]:
+            shown[0] = len(committed[0])
+            print(f"window {i:3d}: committed {shown[0]:3d} tokens -> {tok.detokenize(committed[0])[0][-60:]!r}"
+                  f"   (1-best now {len(partial[0].tokens)} tokens)")
+
+    with torch.no_grad():
+        results = model.stream_ctc_search(speech, args.stream, mode=args.mode, beam_size=args.beam_size,
+                                          context_graph=context_graph, on_partial=on_partial)
+    r = results[0]
+    print(f"final: {len(r.tokens)} tokens -> {tok.detokenize(list(r.tokens))[0][:60]!r}")
+    if r.times is not None:
+        print("  frames: " + " ".join(f"{t}:{f}" for t, f in zip(r.tokens, r.times)))
     return results
 
 
