@@ -419,6 +419,18 @@ int pafc_mamba2_scan_skip_bf16(int B, int L, int H, const void *xbc, long ldx, c
 int pafc_mamba2_gate_norm(int dtype, long rows, int d_inner, const void *y, const void *z, long ld_z,
                           const void *norm_weight, float eps, void *out, pafc_stream_t stream);
 
+/* The scan from an initial state and handing back the final one: what a streaming step of the uni-directional block needs
+ * (a chunk fed in pieces, state carried, computes what the whole chunk computes).  s_in / s_out: fp32 (B, H, 128, 64),
+ * [state dim n][head channel p] = h of the recurrence above; either may be NULL (zero state / not wanted), s_out may be
+ * s_in (updated where it lies); both 16-byte aligned.  s_out = h after the call's last step (with reverse != 0: after time
+ * index 0).  Output: exactly one of y_f32 (the raw scan, as pafc_mamba2_scan_dir; D ignored) and y_bf16 (+ D: bf16(scan +
+ * D[h] x), as pafc_mamba2_scan_skip_bf16).  One chunk (L <= chunk_len, or no workspace): each (batch, head) wave loads its
+ * state, walks the steps and stores it.  Several chunks: the scan over chunks starts from s_in and the wave of the last
+ * chunk stores s_out. */
+int pafc_mamba2_scan_state(int B, int L, int H, const void *xbc, long ldx, const float *dt, const float *log_a, const float *D,
+                           float *y_f32, void *y_bf16, const float *s_in, float *s_out, int reverse, int chunk_len,
+                           void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+
 /* Hand-written bf16 GEMM with fused epilogue, batched (csrc/gemm_bf16.hip: 128 x 128 tiles, two blocks per CU;
  * csrc/gemm_ph.hip: persistent 256-wide phase-pipelined tiles for problems that fill the chip with them -- the entry point
  * picks):

@@ -62,9 +62,15 @@ struct SsdParams {
     int reverse;           // 1: step s of the recurrence is time index L - 1 - s (the right-to-left direction, un-flipped I/O)
     float *ws_state;       // [B][H][NC][128][64]
     float *ws_decay;       // [B][H][NC]
+    const float *s_in;     // [B][H][128][64] state entering step 0 of the call, or null = zero   (pafc_mamba2_scan_state only)
+    float *s_out;          // [B][H][128][64] state after the call's last step, or null; may be s_in
 };
 
-template <bool WRITE_Y, bool Y16 = false>
+// STATE (pafc_mamba2_scan_state): a one-chunk call starts from p.s_in instead of zero, and the wave that walks the call's last
+// chunk leaves its accumulators in p.s_out.  Each wave reads its own (b, h) tile before its first step and writes it after
+// its last, so s_out may be s_in.  With STATE = false nothing of it is compiled in: the three stateless instantiations are
+// the code they were.
+template <bool WRITE_Y, bool Y16 = false, bool STATE = false>
 __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
     const int c = blockIdx.x;
     const int b = blockIdx.y / p.H, h = blockIdx.y % p.H;
@@ -89,6 +95,9 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
     sf32x4 S[8][4];
     {
         const float *src = (WRITE_Y && p.NC > 1) ? p.ws_state + (seq * p.NC + c) * (size_t)(SN * SP) : nullptr;
+        if constexpr (STATE) {
+            if (p.NC == 1 && p.s_in) src = p.s_in + seq * (size_t)(SN * SP);
+        }
 #pragma unroll
         for (int jm = 0; jm < 8; ++jm)
 #pragma unroll
@@ -249,6 +258,18 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
         }
     }
 
+    if constexpr (STATE) {
+        if (p.s_out && c == p.NC - 1) {      // (wave-uniform) same tile pattern as pass A's store: 64-byte segments per 16 lanes
+            float *so = p.s_out + seq * (size_t)(SN * SP);
+#pragma unroll
+            for (int jm = 0; jm < 8; ++jm)
+#pragma unroll
+                for (int in = 0; in < 4; ++in)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) so[(16 * jm + 4 * q + g) * SP + 16 * in + t16] = S[jm][in][g];
+        }
+    }
+
     if constexpr (!WRITE_Y) {
         float *ws = p.ws_state + (seq * p.NC + c) * (size_t)(SN * SP);
 #pragma unroll
@@ -268,6 +289,21 @@ __global__ __launch_bounds__(256) void mamba2_ssd_scan_kernel(const SsdParams p)
     float *ws = p.ws_state + seq * p.NC * (size_t)(SN * SP) + e;
     const float *wd = p.ws_decay + seq * p.NC;
     float run = 0.f;
+    for (int c = 0; c < p.nc_local; ++c) {
+        const float loc = ws[(size_t)c * (SN * SP)];
+        ws[(size_t)c * (SN * SP)] = run;
+        run = fmaf(run, wd[c], loc);
+    }
+    if (p.nc_local < p.NC) ws[(size_t)(p.NC - 1) * (SN * SP)] = run;
+}
+
+// pass B of pafc_mamba2_scan_state: the same exclusive scan with the running value seeded from the carried state
+__global__ __launch_bounds__(256) void mamba2_ssd_scan_state_kernel(const SsdParams p) {
+    const size_t seq = blockIdx.y;
+    const int e = blockIdx.x * 256 + threadIdx.x;     // 0 .. 8191
+    float *ws = p.ws_state + seq * p.NC * (size_t)(SN * SP) + e;
+    const float *wd = p.ws_decay + seq * p.NC;
+    float run = p.s_in ? p.s_in[seq * (size_t)(SN * SP) + e] : 0.f;
     for (int c = 0; c < p.nc_local; ++c) {
         const float loc = ws[(size_t)c * (SN * SP)];
         ws[(size_t)c * (SN * SP)] = run;
@@ -304,11 +340,14 @@ extern "C" int pafc_mamba2_scan(int B, int L, int H, const void *xbc, long ldx, 
 
 namespace pafc {
 namespace {
+template <bool STATE = false>
 int ssd_launch(int B, int L, int H, const void *xbc, long ldx, const float *dt, const float *log_a, float *y, bf16_t *y16,
-               const float *Dskip, int reverse, int chunk_len, void *workspace, size_t workspace_bytes, hipStream_t s) {
+               const float *Dskip, int reverse, int chunk_len, void *workspace, size_t workspace_bytes, hipStream_t s,
+               const float *s_in = nullptr, float *s_out = nullptr) {
     if (!xbc || !dt || !log_a || (!y && !y16) || (y16 && !Dskip)) return PAFC_ERR_NULL_POINTER;
     if (B <= 0 || L <= 0 || H <= 0 || (long)B * H > 65535 || ldx < (long)H * 64 + 256 || (ldx % 4)) return PAFC_ERR_BAD_DIMS;
     if (((uintptr_t)xbc & 7) || ((uintptr_t)y & 15) || ((uintptr_t)y16 & 7)) return PAFC_ERR_ALIGNMENT;
+    if (((uintptr_t)s_in & 15) || ((uintptr_t)s_out & 15)) return PAFC_ERR_ALIGNMENT;   // (room for 16-byte accesses of the tile)
     int Lc = chunk_len > 0 ? chunk_len : pafc_mamba2_scan_chunk_len(B, L, H);
     if (!workspace) Lc = L;
     if (Lc < L) Lc = (Lc + 15) / 16 * 16;
@@ -318,15 +357,18 @@ int ssd_launch(int B, int L, int H, const void *xbc, long ldx, const float *dt, 
     p.B = B; p.L = L; p.H = H; p.d_inner = H * 64; p.Lc = Lc; p.reverse = reverse ? 1 : 0;
     p.NC = (L + Lc - 1) / Lc;
     p.nc_local = p.NC - 1;
+    p.s_in = s_in; p.s_out = s_out;
     if (p.NC > 1) {
         if (workspace_bytes < pafc_mamba2_scan_workspace_bytes(B, L, H, Lc)) return PAFC_ERR_WORKSPACE;
         p.ws_state = (float *)workspace;
         p.ws_decay = p.ws_state + (size_t)B * H * p.NC * (SN * SP);
         hipLaunchKernelGGL((mamba2_ssd_kernel<false, false>), dim3(p.nc_local, B * H), dim3(64), 0, s, p);
-        hipLaunchKernelGGL(mamba2_ssd_scan_kernel, dim3(SN * SP / 256, B * H), dim3(256), 0, s, p);
+        // (chunk-local end states start from zero whatever the carried state is: the recurrence is linear, s_in enters in pass B)
+        if constexpr (STATE) hipLaunchKernelGGL(mamba2_ssd_scan_state_kernel, dim3(SN * SP / 256, B * H), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(mamba2_ssd_scan_kernel, dim3(SN * SP / 256, B * H), dim3(256), 0, s, p);
     }
-    if (y16) hipLaunchKernelGGL((mamba2_ssd_kernel<true, true>), dim3(p.NC, B * H), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL((mamba2_ssd_kernel<true, false>), dim3(p.NC, B * H), dim3(64), 0, s, p);
+    if (y16) hipLaunchKernelGGL((mamba2_ssd_kernel<true, true, STATE>), dim3(p.NC, B * H), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((mamba2_ssd_kernel<true, false, STATE>), dim3(p.NC, B * H), dim3(64), 0, s, p);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 }  // namespace
@@ -344,4 +386,12 @@ extern "C" int pafc_mamba2_scan_skip_bf16(int B, int L, int H, const void *xbc, 
                                           size_t workspace_bytes, pafc_stream_t stream) {
     return pafc::ssd_launch(B, L, H, xbc, ldx, dt, log_a, nullptr, (pafc::bf16_t *)y_bf16, D, reverse, chunk_len, workspace,
                             workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int pafc_mamba2_scan_state(int B, int L, int H, const void *xbc, long ldx, const float *dt, const float *log_a,
+                                      const float *D, float *y_f32, void *y_bf16, const float *s_in, float *s_out, int reverse,
+                                      int chunk_len, void *workspace, size_t workspace_bytes, pafc_stream_t stream) {
+    if ((y_f32 != nullptr) == (y_bf16 != nullptr)) return PAFC_ERR_NULL_POINTER;      // exactly one output form
+    return pafc::ssd_launch<true>(B, L, H, xbc, ldx, dt, log_a, y_f32, (pafc::bf16_t *)y_bf16, D, reverse, chunk_len, workspace,
+                                  workspace_bytes, (hipStream_t)stream, s_in, s_out);
 }

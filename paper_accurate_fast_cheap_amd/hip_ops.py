@@ -2807,6 +2807,23 @@ def causal_conv_silu_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     return y
 
 
+def causal_conv_silu_cl_prefix(xp: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """SiLU(causal depthwise conv1d) of a chunk whose left context is laid out in front of it: xp (B, K - 1 + T, C)
+    contiguous = [the K - 1 rows before the chunk | the chunk], weight (C, 1, K) -> (B, T, C).  Three zero rows in front are the
+    module's own causal zero padding (the start of a stream).  pafc_dwconv1d_cl_ex with left_pad 0, T_out = T_in - (K - 1)."""
+    _lib.require_gpu(xp, weight, bias)
+    K = weight.shape[-1]
+    if xp.dim() != 3 or not xp.is_contiguous() or xp.shape[1] < K:
+        raise _lib.PafcError("causal_conv_silu_cl_prefix: contiguous (B, K - 1 + T, C) with T >= 1")
+    B, Tin, C = xp.shape
+    T = Tin - (K - 1)
+    y = torch.empty((B, T, C), dtype=xp.dtype, device=xp.device)
+    rc = _lib.lib().pafc_dwconv1d_cl_ex(_lib.dtype_code(xp.dtype), B, Tin, C, K, 0, T, _lib.ptr(xp), C, _lib.ptr(weight),
+                                        _lib.ptr(bias), _lib.ptr(y), 2, None, _lib.stream_of(xp))
+    _lib.check(rc, "pafc_dwconv1d_cl_ex")
+    return y
+
+
 def mamba2_prep(xbc: torch.Tensor, dt_raw: torch.Tensor, dt_bias: torch.Tensor, A_log: torch.Tensor, d_inner: int):
     """xbc (B, L, d_inner + 256) contiguous, dt_raw (B, L, H) slice -> [r0, r1, k0, k1, v, w] fp32 (B, L, d_inner)."""
     _lib.require_gpu(xbc, dt_bias, A_log)
@@ -2845,6 +2862,40 @@ def mamba2_scan(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, H: int
                                  _lib.ptr(ws) if nws else None, nws, _lib.stream_of(xbc))
     _lib.check(rc, "pafc_mamba2_scan_dir")
     return y
+
+
+def mamba2_scan_state(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, H: int, s_in: Optional[torch.Tensor] = None,
+                      s_out: Optional[torch.Tensor] = None, reverse: bool = False, D: Optional[torch.Tensor] = None,
+                      want_state: bool = True, chunk_len: int = 0):
+    """mamba2_scan from an initial state, returning the final one (include/pafc_encoder_ops.h: pafc_mamba2_scan_state).
+    s_in / s_out: float32 (B, H, 128, 64) [state dim][head channel]; s_in None = zero state; s_out None = allocated here when
+    want_state; s_out may BE s_in (the state is updated where it lies).  -> (y, s_out): y fp32 raw scan, or with D (H) fp32
+    bf16(scan + D x)."""
+    _lib.require_gpu(xbc, dt, log_a, D, s_in, s_out)
+    if xbc.dtype != torch.bfloat16 or dt.dtype != torch.float32 or log_a.dtype != torch.float32:
+        raise _lib.PafcError("mamba2_scan_state: bf16 xbc, fp32 dt / log_a")
+    if xbc.dim() != 3 or not xbc.is_contiguous() or not dt.is_contiguous() or not log_a.is_contiguous():
+        raise _lib.PafcError("mamba2_scan_state: contiguous xbc (B, L, H * 64 + 256), dt / log_a (B, L, H)")
+    B, Lq, ldx = xbc.shape
+    if tuple(dt.shape) != (B, Lq, H) or tuple(log_a.shape) != (B, Lq, H):
+        raise _lib.PafcError("mamba2_scan_state: dt / log_a must be (B, L, H)")
+    for name, s in (("s_in", s_in), ("s_out", s_out)):
+        if s is not None and (s.dtype != torch.float32 or tuple(s.shape) != (B, H, 128, 64) or not s.is_contiguous()):
+            raise _lib.PafcError(f"mamba2_scan_state: {name} must be contiguous float32 (B, H, 128, 64)")
+    if D is not None and (D.dtype != torch.float32 or tuple(D.shape) != (H,)):
+        raise _lib.PafcError("mamba2_scan_state: D must be float32 (H)")
+    if s_out is None and want_state:
+        s_out = torch.empty((B, H, 128, 64), dtype=torch.float32, device=xbc.device)
+    Lb = _lib.lib()
+    nws = Lb.pafc_mamba2_scan_workspace_bytes(B, Lq, H, chunk_len)
+    ws = torch.empty(nws, dtype=torch.uint8, device=xbc.device) if nws else None
+    y = torch.empty((B, Lq, H * 64), dtype=torch.bfloat16 if D is not None else torch.float32, device=xbc.device)
+    rc = Lb.pafc_mamba2_scan_state(B, Lq, H, _lib.ptr(xbc), ldx, _lib.ptr(dt), _lib.ptr(log_a), _lib.ptr(D),
+                                   None if D is not None else _lib.ptr(y), _lib.ptr(y) if D is not None else None,
+                                   _lib.ptr(s_in), _lib.ptr(s_out), int(reverse), chunk_len, _lib.ptr(ws), nws,
+                                   _lib.stream_of(xbc))
+    _lib.check(rc, "pafc_mamba2_scan_state")
+    return y, s_out
 
 
 def mamba2_gate_norm(y: torch.Tensor, z: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> torch.Tensor:

@@ -79,12 +79,12 @@ class ASRModel(torch.nn.Module):
         decoding_chunk_size."""
         if decoding_chunk_size <= 0:
             raise ValueError(f"{who}: decoding_chunk_size must be > 0 (a chunked stream)")
-        from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
+        from .encoder_layer import streamable_slot
         enc = self.encoder
         layers = list(getattr(enc, "encoders", []))
-        if not layers or any(type(l.self_attn) is not RWKV_TmixWrapper for l in layers) or not enc.normalize_before:
-            raise ValueError(f"{who}: the encoder must be a pre-norm uni-directional model (rwkv_tmix60 slot); "
-                             "a bidirectional encoder needs the whole utterance")
+        if not layers or any(not streamable_slot(l.self_attn) for l in layers) or not enc.normalize_before:
+            raise ValueError(f"{who}: the encoder must be a pre-norm uni-directional model (rwkv_tmix60 slot, or mamba_att with "
+                             "rnn_att_direction: uni); a bidirectional encoder needs the whole utterance")
         lookahead = any(l.conv_module is not None and l.conv_module.lorder == 0 for l in layers)
         sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
         stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx

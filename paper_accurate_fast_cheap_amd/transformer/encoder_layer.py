@@ -11,6 +11,33 @@ from torch import nn
 from .layer_norm import LayerNorm
 
 
+def _uni_rwkv(slot: nn.Module) -> bool:
+    from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
+    return type(slot) is RWKV_TmixWrapper
+
+
+def _uni_mamba(slot: nn.Module) -> bool:
+    from .mamba2 import MambaAttWrapper
+    return type(slot) is MambaAttWrapper and slot.streamable
+
+
+def streamable_slot(slot: nn.Module) -> bool:
+    """The slots with a state carry: the left-to-right RWKV-6 time-mix and the left-to-right Mamba-2 block."""
+    return _uni_rwkv(slot) or _uni_mamba(slot)
+
+
+def _slot_state(slot: nn.Module, mamba: bool, h: torch.Tensor, carry: dict) -> Tuple[torch.Tensor, dict]:
+    """The slot on one chunk from its carries -> (output in h's dtype, the slot's new carries)."""
+    if mamba:
+        att, conv, ssm = slot.forward_state(h, carry.get("conv"), carry.get("ssm"))
+        return att, {"conv": conv, "ssm": ssm}
+    qd = h.dtype
+    if slot.do_bfloat16:
+        h = h.to(torch.bfloat16)
+    att, shift, wkv = slot.tmix_block.forward_state(h, carry.get("shift"), carry.get("wkv"))
+    return att.to(qd), {"shift": shift, "wkv": wkv}
+
+
 class ConformerEncoderLayer(nn.Module):
     def __init__(self, size: int, self_attn: nn.Module, feed_forward: Optional[nn.Module] = None,
                  feed_forward_macaron: Optional[nn.Module] = None, conv_module: Optional[nn.Module] = None,
@@ -95,23 +122,22 @@ class ConformerEncoderLayer(nn.Module):
         """One chunk WITH recurrent-state carry (uni-directional slot only): what the reference's forward_chunk
         lacks (its wrappers return `cache` untouched, rwkv_wrapper.py:81).  carry = {"shift": (B,1,C) last
         normalised frame of the previous chunk, "wkv": float32 (B,H,N,N) scan state, "cnn": (B,C,lorder) causal-conv
-        left context} or None at the start of a stream.  With a causal conv module, chunked == full sequence."""
-        from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
+        left context} or None at the start of a stream; a uni-directional Mamba-2 slot carries {"conv": (B, 3, d_inner +
+        2 d_state) last pre-convolution xBC rows, "ssm": float32 (B,H,128,64) scan state} in place of "shift" / "wkv".
+        With a causal conv module, chunked == full sequence."""
         slot = self.self_attn
-        if type(slot) is not RWKV_TmixWrapper:
-            raise NotImplementedError("state carry is defined for the uni-directional slot (rwkv_tmix60)")
+        mamba = _uni_mamba(slot)
+        if not mamba and not _uni_rwkv(slot):
+            raise NotImplementedError("state carry is defined for the uni-directional slot (rwkv_tmix60, or mamba_att with "
+                                      "rnn_att_direction: uni)")
         if not self.normalize_before:
             raise NotImplementedError("state carry is defined for pre-norm layers")
         carry = carry or {}
         if self.feed_forward_macaron is not None:
             x = x + self.ff_scale * self.feed_forward_macaron(self.norm_ff_macaron(x))
         h = self.norm_mha(x)
-        qd = h.dtype
-        if slot.do_bfloat16:
-            h = h.to(torch.bfloat16)
-        att, shift, wkv = slot.tmix_block.forward_state(h, carry.get("shift"), carry.get("wkv"))
-        x = x + att.to(qd)
-        new = {"shift": shift, "wkv": wkv}
+        att, new = _slot_state(slot, mamba, h, carry)
+        x = x + att
         if self.conv_module is not None:
             empty_mask = torch.ones((0, 0, 0), dtype=torch.bool, device=x.device)
             cnn = carry.get("cnn", torch.zeros((0, 0, 0), dtype=x.dtype, device=x.device))
@@ -136,9 +162,9 @@ class ConformerEncoderLayer(nn.Module):
         Returns (the frames finalised by this call (B, v, C), new carry); over a whole stream the concatenated outputs equal
         the layer's whole-sequence forward."""
         from ..hip_ops import depthwise_conv1d_cl, linear
-        from ..rwkv_v6.rwkv_wrapper import RWKV_TmixWrapper
         slot, cm = self.self_attn, self.conv_module
-        if type(slot) is not RWKV_TmixWrapper or not self.normalize_before or cm is None or cm.lorder > 0 or not cm.use_layer_norm:
+        mamba = _uni_mamba(slot)
+        if not (mamba or _uni_rwkv(slot)) or not self.normalize_before or cm is None or cm.lorder > 0 or not cm.use_layer_norm:
             raise NotImplementedError("look-ahead carry: uni-directional slot, pre-norm, non-causal conv module with layer_norm")
         carry = dict(carry or {})
         B, m, C = x.shape
@@ -150,11 +176,9 @@ class ConformerEncoderLayer(nn.Module):
             if self.feed_forward_macaron is not None:
                 x = x + self.ff_scale * self.feed_forward_macaron(self.norm_ff_macaron(x))
             h = self.norm_mha(x)
-            qd = h.dtype
-            if slot.do_bfloat16:
-                h = h.to(torch.bfloat16)
-            att, carry["shift"], carry["wkv"] = slot.tmix_block.forward_state(h.contiguous(), carry.get("shift"), carry.get("wkv"))
-            x2 = x + att.to(qd)
+            att, new = _slot_state(slot, mamba, h.contiguous(), carry)
+            carry.update(new)
+            x2 = x + att
             u = torch.nn.functional.glu(linear(self.norm_conv(x2), cm.pointwise_conv1.weight.squeeze(-1), cm.pointwise_conv1.bias), dim=-1)
             U = torch.cat([carry["cu"], u], dim=1)
             X2 = torch.cat([carry["x2"], x2], dim=1)

@@ -163,7 +163,9 @@ class LayerPlan:
             wp = (wf * g).to(torch.bfloat16).contiguous()
             return wp, bf.to(torch.bfloat16).contiguous(), wp.float().sum(-1).contiguous(), norm.eps
 
-        folds = dict(out=fold(self.Wo, None, self.blocks[0].ln_x), ff=fold(L.feed_forward.w_1.weight, L.feed_forward.w_1.bias, L.norm_ff))
+        folds = dict(ff=fold(L.feed_forward.w_1.weight, L.feed_forward.w_1.bias, L.norm_ff))
+        if self.rwkv:
+            folds["out"] = fold(self.Wo, None, self.blocks[0].ln_x)
         self._carry_folds = (self._stamp, folds, hip_ops.DerivedFill())
         return folds
 
@@ -559,16 +561,28 @@ def layer_forward_split(plan: LayerPlan, x: torch.Tensor, hp: torch.Tensor, lens
     return out, hn
 
 
+def _carry_slot_ok(slot: nn.Module) -> bool:
+    """The slots the fused chunk steps serve: the bf16 left-to-right RWKV-6 time-mix, and the left-to-right Mamba-2 block in
+    bf16 on its SSD scan kernel (called through Mamba2.forward_state inside the re-scheduled layer)."""
+    if type(slot) is RWKV_TmixWrapper:
+        return bool(slot.do_bfloat16)
+    from .mamba2 import MambaAttWrapper
+    if type(slot) is MambaAttWrapper and slot.streamable:
+        m = slot.mamba
+        return bool(m.fused_inference and m.ssd_kernel and m.d_state == 128 and m.d_inner <= 1024
+                    and m.conv1d.weight.dtype == torch.bfloat16 and m.in_proj.weight.dtype == torch.bfloat16)
+    return False
+
+
 def carry_eligible(layer: nn.Module, x: torch.Tensor) -> bool:
     """State-carrying chunk step through the fused kernels: uni-directional bf16 slot, causal conv; B concurrent streams
     of equal chunk length (B = 1 is the reference's forward_chunk contract, B > 1 is B independent streams per step)."""
     cm = layer.conv_module
-    return (cm is not None and type(layer.self_attn) is RWKV_TmixWrapper and layer.normalize_before
+    return (cm is not None and _carry_slot_ok(layer.self_attn) and layer.normalize_before
             and layer.feed_forward_macaron is not None and cm.use_layer_norm and cm.lorder > 0
             and isinstance(cm.activation, nn.SiLU) and isinstance(layer.feed_forward.activation, nn.SiLU)
             and isinstance(layer.feed_forward_macaron.activation, nn.SiLU) and cm.kernel_size <= 31
-            and layer.size % 64 == 0 and layer.size <= 1024 and x.is_cuda and x.dtype == torch.bfloat16
-            and bool(layer.self_attn.do_bfloat16))
+            and layer.size % 64 == 0 and layer.size <= 1024 and x.is_cuda and x.dtype == torch.bfloat16)
 
 
 def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict], h0: Optional[torch.Tensor] = None,
@@ -595,69 +609,89 @@ def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict],
         _, h0, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_ff_macaron.weight, L.norm_ff_macaron.bias, want_x=False, eps=L.norm_ff_macaron.eps)
     x = _ffn_residual(L.feed_forward_macaron, h0, x, L.ff_scale, plan.b2_macaron, inplace=False)
     _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_mha.weight, L.norm_mha.bias, want_x=False, eps=L.norm_mha.eps)
-    shift = carry.get("shift")
-    if shift is None:
-        shift = h.new_zeros(B, 1, C)
-    elif shift.dtype != h.dtype or not shift.is_contiguous():
-        shift = shift.to(h.dtype).contiguous()
     few = True                                           # the chunk step is launch-bound: one kernel each for the two LoRA chains
     sk = h.dtype == torch.bfloat16 and hip_ops.skinny_ok(M, C, C)     # a handful of rows: the few-rows GEMM and its fusions
-    if sk:   # token shift + lerp as the operand producer of the down-projection (one ~5 us launch)
-        t = hip_ops.gemm_skinny(h.view(M, C), plan.W1n[0], None, "tanh", mix_maa=plan.maa_x_n[0], mix_prev=shift, mix_T=T).view(1, M, -1)
-    else:
-        t = hip_ops.tmix_lora_down(h, plan.maa_x_n, plan.W1n, prev=shift, one_pass=few)
-    z = hip_ops.tmix_lora_mix4(h, t, plan.W2t, plan.maa4, prev=shift)                         # (4, 1, M, C)
-    if hip_ops.skinny_ok(M, C, C):
-        rkv = hip_ops.gemm_skinny(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
-    elif M >= _OWN_GEMM_MIN_ROWS:
-        rkv = hip_ops.gemm_bf16(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
-    else:
-        rkv = torch.bmm(z[:3].view(3, M, C), plan.Wrkv).view(3, B, T, C)
-    # (the decay chain and the r / k / v projections are independent, but as two branches of the captured graph -- a second HIP
-    # stream forked and joined by events -- the step got 25 % SLOWER, 1.33 -> 1.66 ms: cross-queue dependencies cost more than
-    # the 5 us they hide; one stream)
-    if sk and plan.D1n.shape[1] == 64:   # one short launch: bf16(tanh(z_w D1)) in LDS, then bf16(. D2) + time_decay, rounded
-        w = hip_ops.decay_lora_skinny(z[3].view(M, C), plan.D1n[0], plan.D2n[0], plan.time_decay.view(C)).view(B, T, C)   # as the op chain rounds
-    elif sk:
-        td = hip_ops.gemm_skinny(z[3].view(M, C), plan.D1n[0], None, "tanh")
-        w = hip_ops.gemm_skinny(td, plan.D2n[0], plan.time_decay.view(C), round_first=True).view(B, T, C)
-    else:
-        w = hip_ops.decay_lora(z[3].view(1, M, C), plan.D1n, plan.D2n, plan.time_decay.view(1, C), one_pass=few).view(B, T, C)
-    s_in = carry.get("wkv")
-    new = carry if in_place else {}
-    if in_place and s_in is not None and hip_ops.wkv6_single_chunk(B, T, C, plan.u[0].shape[0]):
-        y, _ = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, s_out=s_in)      # the state is updated where it lies
-    else:
-        y, s_out = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, want_state=True)
-        if in_place and s_in is not None:
-            s_in.copy_(s_out)
+    att = None                                           # a slot output still to be added to the stream (by the norm_conv pass)
+    if not plan.rwkv:
+        # Mamba-2: the block itself, from and into its carries -- "conv" (B, 3, d_inner + 256) pre-convolution rows, "ssm" float32
+        # (B, H, 128, 64); in_place: the scan writes the state over the carried one, the three rows are refreshed by a small copy
+        conv, s_in = carry.get("conv"), carry.get("ssm")
+        new = carry if in_place else {}
+        att, conv_new, s_new = L.self_attn.forward_state(h, conv, s_in, s_in if (in_place and s_in is not None) else None)
+        if s_new is not s_in:
+            new["ssm"] = s_new
+        if in_place and conv is not None and conv.shape == conv_new.shape and conv.dtype == conv_new.dtype:
+            if pending is not None:
+                pending.append((conv, conv_new))
+            else:
+                conv.copy_(conv_new)
         else:
-            new["wkv"] = s_out
-    if in_place and carry.get("shift") is not None and carry["shift"].dtype == h.dtype:
-        if pending is not None:
-            pending.append((carry["shift"], h[:, -1:]))
+            new["conv"] = conv_new
+    else:
+        shift = carry.get("shift")
+        if shift is None:
+            shift = h.new_zeros(B, 1, C)
+        elif shift.dtype != h.dtype or not shift.is_contiguous():
+            shift = shift.to(h.dtype).contiguous()
+        if sk:   # token shift + lerp as the operand producer of the down-projection (one ~5 us launch)
+            t = hip_ops.gemm_skinny(h.view(M, C), plan.W1n[0], None, "tanh", mix_maa=plan.maa_x_n[0], mix_prev=shift, mix_T=T).view(1, M, -1)
         else:
-            carry["shift"].copy_(h[:, -1:])           # (after the two passes that read the old one)
-    else:
-        new["shift"] = h[:, -1:].contiguous()
-    ln = plan.blocks[0].ln_x
-    if sk:   # ln_x folded into the output projection
-        wo, bo, cso, epo = plan.carry_folds()["out"]
-        x2 = x.view(M, C)
-        x = hip_ops.gemm_skinny(y.view(M, C), wo, bo, residual=x2, out=x2, ln_self=True, ln_csum=cso, ln_eps=epo).view(B, T, C)
-    else:
-        _, yn, _ = hip_ops.add_layernorm(y.view(M, C), None, 1.0, ln.weight, ln.bias, eps=ln.eps, want_x=False)
-        x = proj(yn, plan.Wo, None, "none", residual=x.view(M, C), inplace=True).view(B, T, C)
+            t = hip_ops.tmix_lora_down(h, plan.maa_x_n, plan.W1n, prev=shift, one_pass=few)
+        z = hip_ops.tmix_lora_mix4(h, t, plan.W2t, plan.maa4, prev=shift)                         # (4, 1, M, C)
+        if hip_ops.skinny_ok(M, C, C):
+            rkv = hip_ops.gemm_skinny(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
+        elif M >= _OWN_GEMM_MIN_ROWS:
+            rkv = hip_ops.gemm_bf16(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
+        else:
+            rkv = torch.bmm(z[:3].view(3, M, C), plan.Wrkv).view(3, B, T, C)
+        # (the decay chain and the r / k / v projections are independent, but as two branches of the captured graph -- a second HIP
+        # stream forked and joined by events -- the step got 25 % SLOWER, 1.33 -> 1.66 ms: cross-queue dependencies cost more than
+        # the 5 us they hide; one stream)
+        if sk and plan.D1n.shape[1] == 64:   # one short launch: bf16(tanh(z_w D1)) in LDS, then bf16(. D2) + time_decay, rounded
+            w = hip_ops.decay_lora_skinny(z[3].view(M, C), plan.D1n[0], plan.D2n[0], plan.time_decay.view(C)).view(B, T, C)   # as the op chain rounds
+        elif sk:
+            td = hip_ops.gemm_skinny(z[3].view(M, C), plan.D1n[0], None, "tanh")
+            w = hip_ops.gemm_skinny(td, plan.D2n[0], plan.time_decay.view(C), round_first=True).view(B, T, C)
+        else:
+            w = hip_ops.decay_lora(z[3].view(1, M, C), plan.D1n, plan.D2n, plan.time_decay.view(1, C), one_pass=few).view(B, T, C)
+        s_in = carry.get("wkv")
+        new = carry if in_place else {}
+        if in_place and s_in is not None and hip_ops.wkv6_single_chunk(B, T, C, plan.u[0].shape[0]):
+            y, _ = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, s_out=s_in)      # the state is updated where it lies
+        else:
+            y, s_out = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, want_state=True)
+            if in_place and s_in is not None:
+                s_in.copy_(s_out)
+            else:
+                new["wkv"] = s_out
+        if in_place and carry.get("shift") is not None and carry["shift"].dtype == h.dtype:
+            if pending is not None:
+                pending.append((carry["shift"], h[:, -1:]))
+            else:
+                carry["shift"].copy_(h[:, -1:])           # (after the two passes that read the old one)
+        else:
+            new["shift"] = h[:, -1:].contiguous()
+        ln = plan.blocks[0].ln_x
+        if sk:   # ln_x folded into the output projection
+            wo, bo, cso, epo = plan.carry_folds()["out"]
+            x2 = x.view(M, C)
+            x = hip_ops.gemm_skinny(y.view(M, C), wo, bo, residual=x2, out=x2, ln_self=True, ln_csum=cso, ln_eps=epo).view(B, T, C)
+        else:
+            _, yn, _ = hip_ops.add_layernorm(y.view(M, C), None, 1.0, ln.weight, ln.bias, eps=ln.eps, want_x=False)
+            x = proj(yn, plan.Wo, None, "none", residual=x.view(M, C), inplace=True).view(B, T, C)
     cm = L.conv_module
     cnn = carry.get("cnn")
     cxb = carry.get("cx") if in_place else None
     if cxb is not None and B == 1 and cxb.shape == (1, cm.lorder + T, C) and cxb.dtype == x.dtype and T >= cm.lorder:
         cx = cxb                                      # rows [0, lorder) = the cache, the chunk's rows go behind them
-        hip_ops.add_layernorm(x, None, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=False, eps=L.norm_conv.eps,
-                              out1=cx[0, cm.lorder:])
+        xa, _, _ = hip_ops.add_layernorm(x, att, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=att is not None,
+                                         eps=L.norm_conv.eps, out1=cx[0, cm.lorder:])
+        x = xa if att is not None else x
         cnn = None                                    # ("cnn" is rebuilt from cx by stream_chunks when the captured steps end)
     else:
-        _, hc, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=False, eps=L.norm_conv.eps)
+        xa, hc, _ = hip_ops.add_layernorm(x, att, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=att is not None,
+                                          eps=L.norm_conv.eps)
+        x = xa if att is not None else x
         left = cnn.transpose(1, 2).to(hc.dtype) if cnn is not None and cnn.numel() > 0 else hc.new_zeros(B, cm.lorder, C)
         cx = torch.cat([left, hc], dim=1)                                                     # (B, lorder + T, C)
     pw1 = cm.pointwise_conv1
@@ -711,7 +745,7 @@ def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict],
 def lookahead_eligible(layer: nn.Module, x: torch.Tensor) -> bool:
     """The steady-state look-ahead chunk step (non-causal conv module, the shipped uni YAML) on the fused kernels: one bf16
     stream, uni-directional bf16 slot, pre-norm, layer_norm conv module with an odd kernel <= 31."""
-    cm = layer.conv_module
+    cm = layer.conv_module      # (a Mamba-2 slot takes the module path of forward_lookahead: stream_chunks_lookahead's eager loop)
     return (cm is not None and type(layer.self_attn) is RWKV_TmixWrapper and layer.normalize_before
             and layer.feed_forward_macaron is not None and cm.use_layer_norm and cm.lorder == 0 and cm.kernel_size % 2 == 1
             and isinstance(cm.activation, nn.SiLU) and isinstance(layer.feed_forward.activation, nn.SiLU)

@@ -99,6 +99,66 @@ class Mamba2(nn.Module):
         #  in flight on side streams its fp32 GEMM never finishes -- DESIGN section 4 "the c2 stall"; found by the Mamba-2 sweep)
         return lin(y, self.out_proj)
 
+    def forward_state(self, u: torch.Tensor, conv_in: Optional[torch.Tensor] = None, ssm_in: Optional[torch.Tensor] = None,
+                      ssm_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One chunk of a left-to-right stream WITH the block's two carries (GPU inference only, no fallback):
+            conv_in (B, d_conv - 1, d_inner + 2 d_state): the last pre-convolution xBC rows of the previous chunk (None at the
+                start of a stream = zero rows, the module's own causal padding);
+            ssm_in  float32 (B, H, 128, 64) [state dim][head channel]: h after the previous chunk's last step (None = zero).
+        -> (out (B, T, d_model), conv_out, ssm_out).  Chunk after chunk computes what forward() computes on the whole sequence.
+        ssm_out (bf16 SSD kernel): where the new state goes; it may be ssm_in (updated where it lies, the captured chunk step).
+        fp32 (and bf16 with ssd_kernel off): the two half-state scans run on the WKV-6 kernel, whose state is
+        [value][key] and PRE-DECAYED (S_t = a_t h_{t-1}): the public carry is mapped to and from it by a transpose and a scale by
+        the chunk's first decay per call, so the carry has one layout whatever the precision."""
+        from .. import hip_ops
+        if not (u.is_cuda and u.dim() == 3 and u.size(1) > 0 and self.d_state == 128 and self.d_inner <= 1024
+                and u.dtype in (torch.float32, torch.bfloat16) and self.conv1d.weight.dtype == u.dtype):
+            raise NotImplementedError("Mamba2.forward_state: GPU tensors (B, T > 0, d_model), fp32 or bf16 in the parameters' dtype, "
+                                      "d_state 128, d_inner <= 1024")
+        lin = lambda t, m: hip_ops.linear_fused(t.contiguous(), m.weight, m.bias, "none")
+        Bsz, T, _ = u.shape
+        di, N, H, K = self.d_inner, self.d_state, self.nheads, self.d_conv
+        zxbcdt = lin(u, self.in_proj)
+        z = zxbcdt[..., :di]
+        dt_raw = zxbcdt[..., 2 * di + 2 * N:]
+        if conv_in is None:
+            conv_in = zxbcdt.new_zeros(Bsz, K - 1, di + 2 * N)
+        xp = torch.cat([conv_in.to(zxbcdt.dtype), zxbcdt[..., di:2 * di + 2 * N]], dim=1)       # (B, K - 1 + T, conv_dim)
+        conv_out = xp[:, T:].contiguous()                                                      # its last K - 1 rows
+        xbc = hip_ops.causal_conv_silu_cl_prefix(xp, self.conv1d.weight, self.conv1d.bias)
+        if u.dtype == torch.bfloat16 and self.ssd_kernel:
+            dt = F.softplus(dt_raw.float() + self.dt_bias.float()).contiguous()
+            log_a = (dt * (-torch.exp(self.A_log.float()))).contiguous()
+            if self.scan_bf16_out:
+                y, s_new = hip_ops.mamba2_scan_state(xbc, dt, log_a, H, ssm_in, ssm_out, D=self.D.float())
+                y = hip_ops.mamba2_gate_norm(y, z, self.norm.weight, self.norm.eps)
+            else:
+                y, s_new = hip_ops.mamba2_scan_state(xbc, dt, log_a, H, ssm_in, ssm_out)
+                y = hip_ops.mamba2_finish(y, None, xbc, dt_raw, z, self.dt_bias.float(), self.D.float(), self.norm.weight,
+                                          self.norm.eps, di, diag=False)
+            return lin(y, self.out_proj), conv_out, s_new
+        r0, r1, k0, k1, v, w = hip_ops.mamba2_prep(xbc, dt_raw, self.dt_bias.float(), self.A_log.float(), di)
+        u0 = torch.zeros(H, 64, dtype=torch.float32, device=u.device)
+        s0 = s1 = None
+        if ssm_in is not None:
+            # WKV state entering the chunk = a_0 h^T per 64-wide half of the state dimension
+            a0 = torch.exp(F.softplus(dt_raw[:, 0].float() + self.dt_bias.float()) * (-torch.exp(self.A_log.float())))   # (B, H)
+            sw = (ssm_in * a0.view(Bsz, H, 1, 1)).transpose(2, 3)                                # (B, H, 64, 128) [value][key]
+            s0, s1 = sw[..., :64].contiguous(), sw[..., 64:].contiguous()
+        y0, e0 = wkv6_forward(r0, k0, v, w, u0, s_in=s0, want_state=True)
+        y1, e1 = wkv6_forward(r1, k1, v, w, u0, s_in=s1, want_state=True)
+        # (the prepared decay of the chunk's last step is 1 -- the next chunk's first decay is not known yet -- so the final
+        #  WKV state is h itself, transposed)
+        s_new = torch.cat([e0, e1], dim=3).transpose(2, 3)
+        if ssm_out is not None:
+            ssm_out.copy_(s_new)
+            s_new = ssm_out
+        else:
+            s_new = s_new.contiguous()
+        y = hip_ops.mamba2_finish(y0, y1, xbc, dt_raw, z, self.dt_bias.float(), self.D.float(), self.norm.weight,
+                                  self.norm.eps, di)
+        return lin(y, self.out_proj), conv_out, s_new
+
     def fused_eligible(self, u: torch.Tensor) -> bool:
         return (self.fused_inference and u.is_cuda and not torch.is_grad_enabled() and self.d_state == 128
                 and self.d_inner <= 1024 and u.dtype in (torch.float32, torch.bfloat16)
@@ -175,3 +235,15 @@ class MambaAttWrapper(nn.Module):
     def forward(self, query: torch.Tensor, key=None, value=None, mask=None, pos_emb=None,
                 cache: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         return self.mamba(query), (cache if cache is not None else _EMPTY_CACHE.to(query.device))
+
+    @property
+    def streamable(self) -> bool:
+        """State carry exists for the left-to-right block alone (a bidirectional one needs the whole utterance)."""
+        return type(self.mamba) is Mamba2
+
+    def forward_state(self, query: torch.Tensor, conv_in: Optional[torch.Tensor] = None, ssm_in: Optional[torch.Tensor] = None,
+                      ssm_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Mamba2.forward_state of the uni-directional slot: (out, conv carry, ssm carry)."""
+        if not self.streamable:
+            raise NotImplementedError("state carry is defined for the uni-directional slot (rnn_att_direction: uni)")
+        return self.mamba.forward_state(query, conv_in, ssm_in, ssm_out)
