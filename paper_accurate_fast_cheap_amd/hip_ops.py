@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import c_int, c_void_p
+from .utils import graph_step
 
 
 # ---- dispatch thresholds: ONE table ---------------------------------------------------------------------------------------
@@ -1422,16 +1423,7 @@ class RnntGreedyStream:
         g = self._graphs.get(n, False)
         if g is False and self.use_graph:
             # capture once per n; only a REFUSED capture (nothing ran: the state is as before) finishes eagerly, for good
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    self._fixed(n)
-            except RuntimeError as e:
-                torch.cuda.synchronize(self.device)
-                if isinstance(e, _lib.PafcError) or "captur" not in str(e).lower():
-                    raise
-                g = None
-            self._graphs[n] = g
+            g = self._graphs[n] = graph_step.capture(lambda: self._fixed(n), self.device)[0]
         if g:
             g.replay()
         else:

@@ -17,6 +17,7 @@ from typing import List, Optional
 import torch
 
 from ...transformer.search import DecodeResult, log_add
+from ...utils import graph_step
 
 
 class Sequence:
@@ -171,25 +172,12 @@ class PrefixBeamSearch:
             # body is captured into a hipGraph and replayed for the remaining frames.  MIOpen's RNN call is not
             # capturable (it sizes its workspace inside the call), so the LSTM runs through the framework's own cell.
             with torch.backends.cudnn.flags(enabled=False):
-                side = torch.cuda.Stream(device=device)
-                side.wait_stream(torch.cuda.current_stream(device))
-                with torch.cuda.stream(side):
-                    frame(); frame()
-                torch.cuda.current_stream(device).wait_stream(side)
+                graph_step.on_side_stream(device, lambda: (frame(), frame()))
                 done = 2
-                graph = torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(graph):
-                        frame()
-                except RuntimeError as e:
-                    # only a REFUSED capture (an operation the stream capture does not permit in this build) finishes eagerly --
-                    # nothing ran during the failed capture, so t_dev still stands behind the two warm-up frames; a failing
-                    # launch or a PafcError inside the frame is a real error and surfaces
-                    from ..._lib import PafcError
-                    torch.cuda.synchronize(device)
-                    if isinstance(e, PafcError) or "captur" not in str(e).lower():
-                        raise
-                    graph = None
+                # only a REFUSED capture (an operation the stream capture does not permit in this build) finishes eagerly --
+                # nothing ran during the failed capture, so t_dev still stands behind the two warm-up frames; a failing
+                # launch or a PafcError inside the frame is a real error and surfaces
+                graph = graph_step.capture(frame, device)[0]
                 if graph is not None:          # errors of the replays are genuine kernel / launch errors: not swallowed
                     for _ in range(T - done):
                         graph.replay()

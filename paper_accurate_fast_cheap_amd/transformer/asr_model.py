@@ -6,6 +6,7 @@ from typing import Callable, Dict, Iterator, List, Optional, Tuple
 
 import torch
 
+from ..utils.graph_step import chunk_windows
 from .ctc import CTC
 from .search import DecodeResult, ctc_greedy_search
 
@@ -86,10 +87,8 @@ class ASRModel(torch.nn.Module):
             raise ValueError(f"{who}: the encoder must be a pre-norm uni-directional model (rwkv_tmix60 slot, or mamba_att with "
                              "rnn_att_direction: uni); a bidirectional encoder needs the whole utterance")
         lookahead = any(l.conv_module is not None and l.conv_module.lorder == 0 for l in layers)
-        sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
-        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
         T = speech.size(1)
-        starts = list(range(0, T - ctx + 1, stride))
+        starts, window, _ = chunk_windows(enc.embed, decoding_chunk_size, T)
 
         def walk():
             state = None

@@ -12,6 +12,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from ..utils import graph_step
 from ..utils.class_utils import (WENET_ACTIVATION_CLASSES, WENET_ATTENTION_CLASSES, WENET_EMB_CLASSES,
                                  WENET_SUBSAMPLE_CLASSES)
 from ..utils.mask import add_optional_chunk_mask, make_pad_mask
@@ -28,44 +29,6 @@ def _bump_epoch():
 def _post_load_bump(module, incompatible_keys):
     """load_state_dict post-hook (a module-level function: a lambda would make the module unpicklable)."""
     _bump_epoch()
-
-
-_CAPTURE_STREAMS = {}
-
-
-def _capture_stream(device) -> torch.cuda.Stream:
-    """The side stream this module's graph captures run on (one per device, as torch.cuda.graph keeps one of its own)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if idx not in _CAPTURE_STREAMS:
-        _CAPTURE_STREAMS[idx] = torch.cuda.Stream(device=device)
-    return _CAPTURE_STREAMS[idx]
-
-
-def _abandon_capture(stream: torch.cuda.Stream, device) -> None:
-    """After a capture the runtime refused: let the device drain, taking the runtime's echo of the error here (an invalidated
-    capture reports itself once more through the next synchronising call) rather than in the caller's next unrelated operation.
-    Best effort: on ROCm 7.0's HIP inside torch 2.10 an invalidated capture keeps failing every later call of the process with
-    hipErrorStreamCaptureInvalidated -- ending the capture on its stream by hand (hipStreamEndCapture + hipGetLastError through
-    ctypes) was tried in round 6 and changes nothing, and is not done here: a second copy of the HIP runtime could get loaded for
-    it.  tests/test_encoder_gpu.py::test_refused_capture_is_never_silent_in_a_child_process records which way a runtime
-    behaves; what cannot be cleared surfaces at the caller's next call, naming the capture."""
-    for _ in range(2):
-        try:
-            torch.cuda.synchronize(device)
-            break
-        except RuntimeError as again:
-            if not _capture_refused(again):
-                raise
-
-
-def _capture_refused(e: BaseException) -> bool:
-    """Is this the runtime refusing an operation under stream capture (hipErrorStreamCapture* -- a synchronising call, an
-    allocation the graph pool cannot serve, a capture-unsafe library call), as opposed to an error of the work itself?"""
-    from .._lib import PafcError
-    if isinstance(e, PafcError):
-        return False
-    msg = str(e).lower()
-    return "captur" in msg
 
 
 class BaseEncoder(torch.nn.Module):
@@ -215,21 +178,15 @@ class BaseEncoder(torch.nn.Module):
             self._trim_graphs()
             return None
         if ent == "seen":
-            try:
-                sx, sl = xs.clone(), xs_lens.clone()
-                graph = torch.cuda.CUDAGraph()
-                cap_stream = _capture_stream(xs.device)        # ours, so that a refused capture can be ended by hand (below)
-                with torch.cuda.graph(graph, stream=cap_stream):
-                    oy, om, _ = self.forward_return_layers(sx, sl, all_full=full)
-                ent = self._graphs[key] = (graph, sx, sl, oy, om)
-                self._graphs[key] = self._graphs.pop(key)     # newest last, then drop the oldest graphs beyond the bound
-                self._trim_graphs()
-            except RuntimeError as e:              # a REFUSED capture (an operation the capture mode does not permit): this shape
-                if not _capture_refused(e):        # stays eager; anything else -- a failing launch, a PafcError -- surfaces
-                    raise
-                _abandon_capture(cap_stream, xs.device)
+            sx, sl = xs.clone(), xs_lens.clone()
+            graph, out = graph_step.capture(lambda: self.forward_return_layers(sx, sl, all_full=full), xs.device,
+                                            stream=graph_step.side_stream(xs.device))
+            if graph is None:                      # a REFUSED capture: this shape stays eager (an error of the work surfaced)
                 self._graphs[key] = "eager"
                 return None
+            ent = self._graphs[key] = (graph, sx, sl, out[0], out[1])
+            self._graphs[key] = self._graphs.pop(key)         # newest last, then drop the oldest graphs beyond the bound
+            self._trim_graphs()
         if ent == "eager":
             return None
         graph, sx, sl, oy, om = ent
@@ -333,6 +290,32 @@ class BaseEncoder(torch.nn.Module):
         from . import fused
         return all(fused.carry_eligible(l, xs) for l in self.encoders)
 
+    def _fused_chunk_step(self, xs: torch.Tensor, masks: torch.Tensor, offset: int, state: list, layer_step,
+                          in_place: bool = True) -> torch.Tensor:
+        """The layer loop of a chunk step on the fused kernels, shared by forward_chunk_carry and _lookahead_fused_step: embed,
+        then every layer through layer_step(plan, xs, carry, h, next_norm, pending) -> (xs, h) -- fused.layer_forward_carry or
+        fused.layer_forward_lookahead -- with the next layer's first norm (or after_norm) folded into this one's tail.
+        `pending` is this loop's own list: the layers of an in-place step put their carries' small refreshes there and the
+        loop issues them as ONE multi-tensor copy at the end (None when not in place).  xs: the window after the CMVN."""
+        from . import fused
+        from .. import hip_ops
+        pending = [] if in_place else None
+        with hip_ops.chunk_step():          # few rows: the launch-bound regime (csrc/gemm_skinny.hip)
+            xs, _, _ = self.embed(xs, masks, offset)
+            if getattr(self, "_carry_plans", None) is None:
+                self._carry_plans = [fused.LayerPlan(l) for l in self.encoders]
+            plans = self._carry_plans
+            n = len(plans)
+            tail = self.after_norm if self.normalize_before else None
+            h = None
+            for i, carry in enumerate(state):
+                plans[i].refresh()
+                nxt = plans[i + 1].layer.norm_ff_macaron if i + 1 < n else tail
+                xs, h = layer_step(plans[i], xs, carry, h, nxt, pending)
+            if pending:
+                torch._foreach_copy_([d for d, _ in pending], [s_ for _, s_ in pending])
+        return h if tail is not None else xs
+
     @torch.no_grad()
     def forward_chunk_carry(self, xs: torch.Tensor, offset: int = 0, state: Optional[list] = None, in_place: bool = False
                             ) -> Tuple[torch.Tensor, list]:
@@ -351,27 +334,14 @@ class BaseEncoder(torch.nn.Module):
         self._carry_last_fused = self._carry_step_is_fused(xs)      # (after the CMVN: its output dtype is what the layers see)
         if self._carry_last_fused:                  # bf16 streams, causal conv: fused kernels
             from . import fused
-            from .. import hip_ops
-            with hip_ops.chunk_step():      # few rows: the launch-bound regime (csrc/gemm_skinny.hip)
-                xs, _, _ = self.embed(xs, masks, offset)
-                if getattr(self, "_carry_plans", None) is None:
-                    self._carry_plans = [fused.LayerPlan(l) for l in self.encoders]
-                plans = self._carry_plans
-                n = len(plans)
-                tail = self.after_norm if self.normalize_before else None
-                h = None
-                pending = [] if in_place else None     # the carries' small refreshes: one multi-tensor copy at the end
-                for i, carry in enumerate(state):
-                    plans[i].refresh()
-                    nxt = plans[i + 1].layer.norm_ff_macaron if i + 1 < n else tail
-                    xs, c, h = fused.layer_forward_carry(plans[i], xs, carry, h0=h, next_norm=nxt,
-                                                         in_place=in_place and carry is not None, pending=pending)
-                    new_state.append(c)
-                if pending:
-                    torch._foreach_copy_([d for d, _ in pending], [s_ for _, s_ in pending])
-                return (h if tail is not None else xs), new_state
-        else:
-            xs, _, _ = self.embed(xs, masks, offset)
+
+            def layer_step(plan, x, carry, h, nxt, pending):
+                x, c, h = fused.layer_forward_carry(plan, x, carry, h0=h, next_norm=nxt,
+                                                    in_place=in_place and carry is not None, pending=pending)
+                new_state.append(c)
+                return x, h
+            return self._fused_chunk_step(xs, masks, offset, state, layer_step, in_place), new_state
+        xs, _, _ = self.embed(xs, masks, offset)
         for layer, carry in zip(self.encoders, state):
             xs, c = layer.forward_carry(xs, carry)
             new_state.append(c)
@@ -387,10 +357,8 @@ class BaseEncoder(torch.nn.Module):
         a hipGraph over fixed input / state / output buffers and replayed per window; the first windows (which also
         let the causal-conv cache reach its final length) and a shorter last window run eagerly."""
         assert decoding_chunk_size > 0
-        sub, ctx = self.embed.subsampling_rate, self.embed.right_context + 1
-        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
         T = xs.size(1)
-        starts = list(range(0, T - ctx + 1, stride))
+        starts, window, _ = graph_step.chunk_windows(self.embed, decoding_chunk_size, T)
         full = [c for c in starts if c + window <= T]
         outs: List[torch.Tensor] = []
         state: Optional[list] = None
@@ -404,12 +372,10 @@ class BaseEncoder(torch.nn.Module):
         warm = max(2, -(-lorder // decoding_chunk_size) + 1)
         done = 0
         if use_graph and xs.is_cuda and len(full) >= warm + 4:
-            side = torch.cuda.Stream(device=xs.device)
-            side.wait_stream(torch.cuda.current_stream(xs.device))
-            with torch.cuda.stream(side):
+            def warm_up():
                 for c in full[:warm]:
                     eager(c)
-            torch.cuda.current_stream(xs.device).wait_stream(side)
+            graph_step.on_side_stream(xs.device, warm_up)
             done = warm
             static_in = xs[:, full[warm]:full[warm] + window].clone()
             static_state = [{k: v.clone() for k, v in st.items()} for st in state]
@@ -422,22 +388,16 @@ class BaseEncoder(torch.nn.Module):
                         cx = cnn.new_zeros(1, cnn.size(2) + decoding_chunk_size, cnn.size(1))
                         cx[:, :cnn.size(2)] = cnn.transpose(1, 2)
                         st["cx"] = cx
-            graph = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(graph):
-                    y_static, new_state = self.forward_chunk_carry(static_in, 0, static_state, in_place=True)
-                    for st, nw in zip(static_state, new_state):
-                        if nw is not st:            # (the fused step updates its carries where they lie)
-                            for k in st:
-                                st[k].copy_(nw[k])
-            except RuntimeError as e:
-                # only "this step cannot be captured here" (an operation the stream capture refuses) falls back to the eager
-                # loop -- nothing ran during the failed capture, so `state` is still the state after the warm-up windows;
-                # any other error is a real one and is raised
-                torch.cuda.synchronize(xs.device)
-                if "captur" not in str(e).lower():
-                    raise
-                graph = None
+
+            def step():
+                y, new_state = self.forward_chunk_carry(static_in, 0, static_state, in_place=True)
+                for st, nw in zip(static_state, new_state):
+                    if nw is not st:                # (the fused step updates its carries where they lie)
+                        for k in st:
+                            st[k].copy_(nw[k])
+                return y
+            # nothing runs during a refused capture: `state` is still the state after the warm-up windows, for the eager loop
+            graph, y_static = graph_step.capture(step, xs.device)
             if graph is not None:                   # errors from here on are genuine kernel / launch errors: not swallowed
                 for c in full[warm:]:
                     static_in.copy_(xs[:, c:c + window])
@@ -488,24 +448,10 @@ class BaseEncoder(torch.nn.Module):
         T frames and emits T frames, the carries are the fixed buffers "U" / "X2" / "shift" / "wkv" updated where they lie
         (the form a captured hipGraph needs).  xs: (1, window, F) input window; returns the (1, T, D) frames finalised."""
         from . import fused
-        from .. import hip_ops
         masks = torch.ones(1, 1, xs.size(1), device=xs.device, dtype=torch.bool)
         if self.global_cmvn is not None:
             xs = self.global_cmvn(xs)
-        with hip_ops.chunk_step():
-            xs, _, _ = self.embed(xs, masks, 0)
-            if getattr(self, "_carry_plans", None) is None:
-                self._carry_plans = [fused.LayerPlan(l) for l in self.encoders]
-            plans = self._carry_plans
-            n = len(plans)
-            tail = self.after_norm if self.normalize_before else None
-            h, pending = None, []
-            for i, carry in enumerate(state):
-                plans[i].refresh()
-                nxt = plans[i + 1].layer.norm_ff_macaron if i + 1 < n else tail
-                xs, h = fused.layer_forward_lookahead(plans[i], xs, carry, h, nxt, pending)
-            torch._foreach_copy_([d for d, _ in pending], [s_ for _, s_ in pending])
-        return h if tail is not None else xs
+        return self._fused_chunk_step(xs, masks, 0, state, fused.layer_forward_lookahead)
 
     @torch.no_grad()
     def stream_chunks_lookahead(self, xs: torch.Tensor, decoding_chunk_size: int, use_graph: bool = True) -> torch.Tensor:
@@ -516,10 +462,8 @@ class BaseEncoder(torch.nn.Module):
         captured hipGraph (as stream_chunks does for the causal model); the windows that fill the pipeline, a shorter last
         window and the final drain take the module path."""
         assert decoding_chunk_size > 0
-        sub, ctx = self.embed.subsampling_rate, self.embed.right_context + 1
-        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
         T = xs.size(1)
-        starts = list(range(0, T - ctx + 1, stride))
+        starts, window, _ = graph_step.chunk_windows(self.embed, decoding_chunk_size, T)
         outs, state = [], None
         i = 0
         n = len(starts)
@@ -545,28 +489,19 @@ class BaseEncoder(torch.nn.Module):
                     X2[:, :hf] = st["x2"]
                     bufs.append({"U": U, "X2": X2, "shift": st["shift"].clone().contiguous(), "wkv": st["wkv"].clone().contiguous()})
                 static_in = xs[:, starts[i]:starts[i] + window].clone()
-                side = torch.cuda.Stream(device=xs.device)               # one eager step on a side stream warms every kernel up
-                side.wait_stream(torch.cuda.current_stream(xs.device))
-                with torch.cuda.stream(side):
-                    outs.append(self._lookahead_fused_step(static_in, bufs).clone())
-                torch.cuda.current_stream(xs.device).wait_stream(side)
+
+                def step():
+                    return self._lookahead_fused_step(static_in, bufs)
+                outs.append(graph_step.on_side_stream(xs.device, lambda: step().clone()))  # one eager step warms every kernel up
                 i += 1
-                graph = torch.cuda.CUDAGraph()
-                try:
-                    with torch.cuda.graph(graph):
-                        y_static = self._lookahead_fused_step(static_in, bufs)
-                except RuntimeError as e:                 # only a refused capture falls back to eager fused steps
-                    torch.cuda.synchronize(xs.device)
-                    if "captur" not in str(e).lower():
-                        raise
-                    graph = None
+                graph, y_static = graph_step.capture(step, xs.device)      # (refused: the fused steps go on eagerly)
                 while i in steady:
                     static_in.copy_(xs[:, starts[i]:starts[i] + window])
                     if graph is not None:
                         graph.replay()
                         outs.append(y_static.clone())
                     else:
-                        outs.append(self._lookahead_fused_step(static_in, bufs).clone())
+                        outs.append(step().clone())
                     i += 1
                 state = [{"cu": b["U"][:, :2 * hf].clone(), "x2": b["X2"][:, :hf].clone(), "shift": b["shift"], "wkv": b["wkv"]}
                          for b, hf in zip(bufs, halves)]
@@ -593,18 +528,16 @@ class BaseEncoder(torch.nn.Module):
     def forward_chunk_by_chunk(self, xs: torch.Tensor, decoding_chunk_size: int, num_decoding_left_chunks: int = -1,
                                cat_embs: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(1, T, F) -> ((1, T', C), all-ones (1, 1, T') mask), the function of encoder.py:341-402: the utterance is cut
-        into overlapping windows of (chunk - 1) * subsampling + right_context + 1 input frames, one every
-        subsampling * chunk frames, each encoded by forward_chunk with the caches of the previous one, outputs joined.
+        into overlapping windows (graph_step.chunk_windows), each encoded by forward_chunk with the caches of the previous
+        one, outputs joined.
 
         With the recurrent slot and the non-causal conv module both caches stay empty, so the windows are independent
         full-context passes: here the equal-length ones go through the layers as ONE batch (B = number of windows; same
         arithmetic per window, no padding, hundreds of launches instead of hundreds per window) and only a shorter
         last window runs alone."""
         assert decoding_chunk_size > 0
-        sub, ctx = self.embed.subsampling_rate, self.embed.right_context + 1
-        stride, window = sub * decoding_chunk_size, (decoding_chunk_size - 1) * sub + ctx
         T = xs.size(1)
-        starts = list(range(0, T - ctx + 1, stride))
+        starts, window, _ = graph_step.chunk_windows(self.embed, decoding_chunk_size, T)
         outputs: List[torch.Tensor] = []
         done = 0
         plan = self._windows_independent(xs) if (xs.size(0) == 1 and cat_embs is None) else None

@@ -58,7 +58,6 @@ def _multi_stream_safe(model) -> bool:
     return bool(fn()) if callable(fn) else False
 
 
-
 def _side_streams(device: torch.device, n: int):
     """The same n side streams for every call on a device: the encoder's graph cache is keyed by (shape, stream), so fresh
     streams per file would mean fresh captures per file."""
@@ -66,6 +65,20 @@ def _side_streams(device: torch.device, n: int):
     while len(have) < n:
         have.append(torch.cuda.Stream(device=device))
     return have[:n]
+
+
+def _in_flight(model, device: torch.device, streams: int, n_batches: int):
+    """(n_side, side streams) for a decode loop over n_batches batches: up to `streams` of them in flight, each on a side stream
+    that waits for the caller's stream first (the batches were cut there).  (1, []) -- every batch on the caller's stream -- when
+    the pass calls the framework's library GEMMs, which must not overlap another pass (_multi_stream_safe)."""
+    n_side = max(1, min(int(streams), n_batches))
+    if n_side > 1 and not _multi_stream_safe(model):
+        n_side = 1
+    side = _side_streams(device, n_side) if n_side > 1 else []
+    main = torch.cuda.current_stream(device)
+    for s_ in side:
+        s_.wait_stream(main)
+    return n_side, side
 
 
 @torch.no_grad()
@@ -81,13 +94,7 @@ def greedy_decode_batches(model, batches, streams: int = 2, blank_id: int = 0, w
     if not batches:
         return ([] if want_tokens else None), None
     device = batches[0][0].device
-    n_side = max(1, min(int(streams), len(batches)))
-    if n_side > 1 and not _multi_stream_safe(model):
-        n_side = 1                   # a pass that calls the framework's library GEMMs must not overlap another one (see there)
-    main = torch.cuda.current_stream(device)
-    side = _side_streams(device, n_side) if n_side > 1 else []
-    for s_ in side:
-        s_.wait_stream(main)
+    n_side, side = _in_flight(model, device, streams, len(batches))
     pending, logp = [], None
     for i, (fb, lens) in enumerate(batches):
         with (torch.cuda.stream(side[i % n_side]) if side else contextlib.nullcontext()):
@@ -96,7 +103,7 @@ def greedy_decode_batches(model, batches, streams: int = 2, blank_id: int = 0, w
             if want_tokens:
                 pending.append(ctc_greedy_search(logp, mask.squeeze(1).sum(1), blank_id, defer=True))
     for s_ in side:
-        main.wait_stream(s_)
+        torch.cuda.current_stream(device).wait_stream(s_)
     return ([f() for f in pending] if want_tokens else None), logp
 
 
@@ -121,13 +128,7 @@ def decode_windows(model, feats: torch.Tensor, chunk_size: int, batch_size: int,
         from ..hip_ops import ctc_greedy
         batch_size = merged_batch_size(chunk_size, batch_size, merge_frames)
         batches = list(feats_batcher(feats, chunk_size, batch_size, feats.device))
-        n_side = max(1, min(int(streams), len(batches)))
-        if n_side > 1 and not _multi_stream_safe(model):
-            n_side = 1               # a pass that calls the framework's library GEMMs must not overlap another one
-        main = torch.cuda.current_stream(feats.device)
-        side = _side_streams(feats.device, n_side) if n_side > 1 else []
-        for s_ in side:
-            s_.wait_stream(main)                   # the batches above were cut on the caller's stream
+        n_side, side = _in_flight(model, feats.device, streams, len(batches))
         enc_mod = getattr(model, "encoder", None)
         if graph_cache and getattr(enc_mod, "graph_cache_size", None) is not None and len(batches) > 1:
             # the window shape recurs batch after batch and file after file: the encoder keeps a graph per (shape, stream).  The
@@ -142,7 +143,7 @@ def decode_windows(model, feats: torch.Tensor, chunk_size: int, batch_size: int,
                 pending.append(ctc_greedy(logp.contiguous(), mask.squeeze(1).sum(1), decode_kw.get("blank_id", 0),
                                           want_frames=True))
         for s_ in side:
-            main.wait_stream(s_)
+            torch.cuda.current_stream(feats.device).wait_stream(s_)
         for tk, nt, fr in pending:
             tk, nt, fr = tk.cpu(), nt.cpu(), fr.cpu()
             for i in range(tk.shape[0]):

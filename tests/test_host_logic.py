@@ -392,3 +392,39 @@ def test_grouped_weights_keep_names_values_checkpoints_and_optimizer_state(tmp_p
     with hip_ops.train_shadows():
         g2 = hip_ops._weight_group(f)
         assert g2.data_ptr() == g.data_ptr() and torch.equal(g2[1], f[1].detach().to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("cls", ["Conv2dSubsampling4", "LinearNoSubsampling"])
+def test_chunk_windows_is_the_window_plan_of_forward_chunk_by_chunk(cls):
+    """graph_step.chunk_windows against the arithmetic of the reference written out (wenet/transformer/encoder.py:377-391:
+    context = right_context + 1, stride = subsampling * chunk, window = (chunk - 1) * subsampling + context, a window at
+    every `stride` from 0 while `context` frames are left), for both subsampling classes, from one frame short of a window's
+    context (no window at all) to a few strides past it."""
+    from paper_accurate_fast_cheap_amd.transformer import subsampling
+    from paper_accurate_fast_cheap_amd.transformer.embedding import RelPositionalEncoding
+    from paper_accurate_fast_cheap_amd.utils.graph_step import chunk_windows
+    embed = getattr(subsampling, cls)(80, 32, 0.0, RelPositionalEncoding(32, 0.0))
+    sub, ctx = {"Conv2dSubsampling4": (4, 7), "LinearNoSubsampling": (1, 1)}[cls]
+    assert (embed.subsampling_rate, embed.right_context + 1) == (sub, ctx)
+    for chunk in (1, 8, 16, 64):
+        stride, window = sub * chunk, (chunk - 1) * sub + ctx
+        for T in range(ctx - 1, ctx + 3 * stride + 2):
+            want, cur = [], 0
+            while cur <= T - ctx:                   # `for cur in range(0, num_frames - context + 1, stride)`, written out
+                want.append(cur)
+                cur += stride
+            assert chunk_windows(embed, chunk, T) == (want, window, stride), (chunk, T)
+            assert (want == []) == (T < ctx)
+            if want:                                # every window starts inside the utterance and the last one reaches its end
+                assert want[-1] + ctx <= T and T - (want[-1] + window) < stride
+
+
+def test_capture_refused_tells_the_runtime_refusing_a_capture_from_an_error_of_the_work():
+    from paper_accurate_fast_cheap_amd._lib import PafcError
+    from paper_accurate_fast_cheap_amd.utils.graph_step import capture_refused
+    assert issubclass(PafcError, RuntimeError)      # (it passes through the same except clause)
+    assert capture_refused(PafcError("pafc_gemm_bf16: PAFC_ERR_LAUNCH during stream capture")) is False
+    assert capture_refused(RuntimeError("HIP error: hipErrorStreamCaptureInvalidated: operation failed due to a previous "
+                                        "error during capture")) is True
+    assert capture_refused(RuntimeError("HIP error: hipErrorStreamCaptureUnsupported")) is True
+    assert capture_refused(RuntimeError("launch failed")) is False

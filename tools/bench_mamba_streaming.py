@@ -5,6 +5,7 @@ model on the whole sequence.  Prints one JSON line.  Launches per step: one run 
 import json, sys, time
 import torch
 import bench as B
+from paper_accurate_fast_cheap_amd.utils.graph_step import chunk_windows
 from paper_accurate_fast_cheap_amd.utils.init_model import init_model
 
 chunk = int(sys.argv[1]) if len(sys.argv) > 1 else 64           # encoder frames per chunk (64 = 2.56 s)
@@ -32,9 +33,7 @@ feats = feats.to(torch.bfloat16)
 if streams > 1:      # every stream its own audio: the same file rotated by 17 s per stream
     feats = torch.cat([torch.roll(feats, 1700 * i, dims=1) for i in range(streams)], dim=0).contiguous()
 T = feats.shape[1]
-sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
-stride, window = sub * chunk, (chunk - 1) * sub + ctx
-starts = list(range(0, T - ctx + 1, stride))
+starts = chunk_windows(enc.embed, chunk, T)[0]
 
 
 def run_stream():

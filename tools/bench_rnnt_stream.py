@@ -87,6 +87,7 @@ def encoder_plus_decoder(lo, seconds, steps):
     """bench_streaming.py's model (12 x 512 uni encoder, causal conv k = 15, bf16), one stream, 16-frame chunks: the
     encoder's forward_chunk_carry per window, its output frames into the streamer."""
     import bench as Bn
+    from paper_accurate_fast_cheap_amd.utils.graph_step import chunk_windows
     from paper_accurate_fast_cheap_amd.utils.init_model import init_model
     torch.manual_seed(777)
     conf = Bn.encoder_conf()
@@ -104,9 +105,7 @@ def encoder_plus_decoder(lo, seconds, steps):
     dec = BG.to(BG.make_model(seed=0, D=enc.output_size()), "cuda", torch.bfloat16)
     st = hip_ops.RnntGreedyStream(dec.predictor, dec.joint, 1, CHUNK)
     T = feats.shape[1]
-    sub, ctx = enc.embed.subsampling_rate, enc.embed.right_context + 1
-    stride, window = sub * CHUNK, (CHUNK - 1) * sub + ctx
-    starts = list(range(0, T - ctx + 1, stride))
+    starts, window, _ = chunk_windows(enc.embed, CHUNK, T)
     res = []
     with torch.no_grad():
         for rep in range(1 + steps):
