@@ -134,6 +134,53 @@ int pafc_rnnt_beam_step(int B, int T, int beam, int blank_id, int t, const int64
 int pafc_rnnt_beam_finish(int B, int T, int beam, void *workspace, size_t workspace_bytes, int32_t *out_tokens,
                           int32_t *out_len, double *out_score, pafc_stream_t stream);
 
+/* The same search chunk by chunk (pafc_rnnt_beam_stream_*), the beams carried from one chunk to the next in `workspace`.
+ * The caller keeps B x beam slots as above and fixed (B, Tmax, ...) staging buffers of the current chunk; per chunk it calls
+ * feed once and then, for j = 0 .. Tmax - 1 (or up to the longest row), its frame body on frame j of the staging buffers
+ * followed by step.  The step kernel includes the per-frame text of pafc_rnnt_beam_step (csrc/rnnt_beam_frame.inc), so after
+ * any cut of a row's frames into chunks the n-best token lists, float64 scores and every frame's next_idx / last_tok are
+ * those of the offline search of the concatenated frames, bit for bit, given the same top_val / top_idx.  Nothing reads the
+ * host or allocates: a feed and its steps can be captured in a graph.
+ * max_total_frames: the most frames a row may consume between two resets; it sizes the row's trie pools of
+ *   1 + max_total_frames * beam nodes of 8 bytes, numbered by absolute frame (node 1 + t_abs * beam + rank).  The workspace
+ *   holds the beam state of pafc_rnnt_beam_* for T = max_total_frames and, per row, the frames consumed since the reset, the
+ *   frames taken in the current chunk, an overflow flag and each member's token count.  beam <= 16 and max_total_frames *
+ *   beam < 2^31 - 1, else PAFC_ERR_UNSUPPORTED (workspace_bytes: 0).
+ * reset: rows with row_mask[b] != 0 (device int32 (B), or NULL = every row) restart: one live beam of score 0 at the root
+ *   node, last_tok = blank and the identity next_idx for the row's slots, consumed frames 0, overflow flag cleared.  Other
+ *   rows are untouched.  Call it on every row before the first feed.  (The LSTM state of the slots is the caller's.)
+ * feed: begins a chunk: row b takes clamp(nframes[b], 0, Tmax) frames (nframes: device int64 (B)).  A feed that would take a
+ *   row past max_total_frames takes nothing for that row and sets its overflow flag, which stays until the reset (2: the row
+ *   was never reset).
+ * step: frame j of the chunk, j read from *j_dev (device int64) when that is given.  A row with j >= its taken count is a
+ *   no-op with the identity next_idx, as a finished utterance is offline; a live row runs the walk at absolute frame
+ *   consumed[b], then consumed[b] advances.  top_val float32 / top_idx int64: (B, beam, beam).
+ * drain: the n-best of every row as if its stream ended here; the state is not changed.  The contract of
+ *   pafc_ctc_beam_stream_drain: from (device int32 (B), or NULL = 0): tokens [from[b], from[b] + ld) of each list go to
+ *   out_tokens (B, beam, ld); out_len (B, beam): TOTAL token counts, -1 for unused entries; out_score (B, beam) float64;
+ *   out_count (B): entries in use; out_committed (B): the length of the longest common prefix of the row's live hypotheses --
+ *   every later hypothesis is a live one, or a live one plus a token, so these tokens are final (looked for at or above
+ *   from[b]); out_overflow (B): the row's flag.  The walk and the copy are bounded by the uncommitted tail. */
+size_t pafc_rnnt_beam_stream_workspace_bytes(int B, int max_total_frames, int beam);
+int pafc_rnnt_beam_stream_reset(int B, int max_total_frames, int beam, int blank_id, const int32_t *row_mask, void *workspace,
+                                size_t workspace_bytes, int64_t *next_idx, int64_t *last_tok, pafc_stream_t stream);
+int pafc_rnnt_beam_stream_feed(int B, int Tmax, int max_total_frames, int beam, const int64_t *nframes, void *workspace,
+                               size_t workspace_bytes, pafc_stream_t stream);
+int pafc_rnnt_beam_stream_step(int B, int Tmax, int max_total_frames, int beam, int blank_id, int j, const int64_t *j_dev,
+                               const float *top_val, const int64_t *top_idx, void *workspace, size_t workspace_bytes,
+                               int64_t *next_idx, int64_t *last_tok, pafc_stream_t stream);
+int pafc_rnnt_beam_stream_drain(int B, int max_total_frames, int beam, const void *workspace, size_t workspace_bytes,
+                                const int32_t *from, int ld, int32_t *out_tokens, int32_t *out_len, double *out_score,
+                                int32_t *out_count, int32_t *out_committed, int32_t *out_overflow, pafc_stream_t stream);
+
+/* The LSTM state of the survivors, in one launch and in place: for h and for c, both (num_layers, n = B * beam, hidden)
+ * contiguous of `dtype`, h[l, i, :] = (next_idx[i] < n ? h : h_new)[l, next_idx[i] mod n, :] -- what
+ * torch.cat([h, h_new], 1).index_select(1, next_idx) copied back into h computes, bit for bit.  A slot only ever references
+ * slots of its own utterance (next_idx of pafc_rnnt_beam_step / _stream_step), and a thread owns the same columns of all the
+ * utterance's slots: it reads every row it needs before it writes any.  An index outside [0, 2 n) keeps the slot as it is. */
+int pafc_rnnt_beam_select_state(int dtype, int num_layers, int B, int beam, int hidden, void *h, void *c, const void *h_new,
+                                const void *c_new, const int64_t *next_idx, pafc_stream_t stream);
+
 /* RNN-T greedy search (basic_greedy_search, wenet/transducer/search/greedy_search.py) for B utterances at once, in lockstep:
  * each pafc_rnnt_greedy_step advances every running utterance by one decision -- the LSTM predictor (only for rows whose
  * last decision was not blank), projection, pred_ffn, the joint reduced to per-slice softmax statistics, argmax (lowest index

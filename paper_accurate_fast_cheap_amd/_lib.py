@@ -153,6 +153,12 @@ SIGNATURES = {
     "pafc_rnnt_beam_init": (I, [I, I, I, I, P, Z, P, P, P]),
     "pafc_rnnt_beam_step": (I, [I, I, I, I, I, P, P, P, P, P, Z, P, P, P]),
     "pafc_rnnt_beam_finish": (I, [I, I, I, P, Z, P, P, P, P]),
+    "pafc_rnnt_beam_stream_workspace_bytes": (Z, [I, I, I]),
+    "pafc_rnnt_beam_stream_reset": (I, [I, I, I, I, P, P, Z, P, P, P]),
+    "pafc_rnnt_beam_stream_feed": (I, [I, I, I, I, P, P, Z, P]),
+    "pafc_rnnt_beam_stream_step": (I, [I, I, I, I, I, I, P, P, P, P, Z, P, P, P]),
+    "pafc_rnnt_beam_stream_drain": (I, [I, I, I, P, Z, P, I, P, P, P, P, P, P, P]),
+    "pafc_rnnt_beam_select_state": (I, [I, I, I, I, I, P, P, P, P, P, P]),
     "pafc_rnnt_greedy_workspace_bytes": (Z, [P, I, I, I]),
     "pafc_rnnt_greedy_init": (I, [P, I, I, I, I, P, P, Z, P]),
     "pafc_rnnt_greedy_step": (I, [P, I, I, I, I, P, P, Z, P, P]),

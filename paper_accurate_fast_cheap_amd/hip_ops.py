@@ -2719,6 +2719,142 @@ class RnntBeamState:
         return tokens, lengths, scores
 
 
+class RnntBeamStream:
+    """Device-side beams of the CTC-fused RNN-T prefix beam search for B streams fed chunk by chunk (include/pafc_search.h:
+    pafc_rnnt_beam_stream_*, csrc/rnnt_beam_stream.hip).  The object owns the workspace, `next_idx` / `last_tok` of the
+    B x beam slots, the frame counts and the `from` offsets; the caller owns the frame body and the LSTM state.  Per chunk:
+    feed(nframes), then for every chunk frame j the caller's body and step(j, top_val, top_idx) (j_dev: the frame from a
+    device int64, for a captured body) and select_state(...); drain() is the one host read.  Given the same top_val /
+    top_idx, every frame's next_idx / last_tok and the drained lists equal RnntBeamState's over the concatenated frames,
+    bit for bit.  A row that would pass max_total_frames takes nothing and is reported by drain's `overflow`."""
+
+    def __init__(self, B: int, Tmax: int, beam: int, blank: int, device, max_total_frames: int = 4096):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.PafcError(f"RnntBeamStream runs on the MI355X only (device {dev}); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if B < 1 or Tmax < 1 or max_total_frames < 1:
+            raise _lib.PafcError(f"RnntBeamStream: B {B}, Tmax {Tmax}, max_total_frames {max_total_frames} must be >= 1")
+        if not 1 <= beam <= 16:
+            raise _lib.PafcError(f"RnntBeamStream: beam {beam} must be in 1 .. 16")
+        self.L = _lib.lib()
+        self.B, self.Tmax, self.beam, self.blank, self.device = B, Tmax, beam, int(blank), dev
+        self.max_total = int(max_total_frames)
+        self.nws = self.L.pafc_rnnt_beam_stream_workspace_bytes(B, self.max_total, beam)
+        if self.nws == 0:
+            raise _lib.PafcError("pafc_rnnt_beam_stream_workspace_bytes: unsupported dimensions (max_total_frames * beam < 2^31)")
+        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev)
+        self.next_idx = torch.empty(B * beam, dtype=torch.int64, device=dev)
+        self.last_tok = torch.empty(B * beam, dtype=torch.int64, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._from = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._from_h = [0] * B
+        self.last_read_bytes = 0
+        self.reset()
+
+    def reset(self, rows=None):
+        """Restart the given rows (all when None): one live beam of score 0, the root node, last_tok = blank, the identity
+        next_idx, no frames consumed, overflow flag cleared; other rows are untouched."""
+        mask = None
+        if rows is not None:
+            m = torch.zeros(self.B, dtype=torch.int32)
+            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
+            self._mask.copy_(m)
+            mask = _lib.ptr(self._mask)
+        _lib.check(self.L.pafc_rnnt_beam_stream_reset(self.B, self.max_total, self.beam, self.blank, mask, _lib.ptr(self.ws),
+                                                      self.nws, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
+                                                      _lib.stream_of(self.ws)), "pafc_rnnt_beam_stream_reset")
+
+    def load(self, nframes, n: Optional[int] = None):
+        """The frame counts of the next chunk into their device buffer (an int: every row; else (B,) counts, clamped to
+        [0, n]; a device int64 tensor stays off the host)."""
+        n = self.Tmax if n is None else n
+        if isinstance(nframes, int):
+            self._nf.fill_(max(0, min(n, nframes)))
+        else:
+            nf = torch.as_tensor(nframes, dtype=torch.int64)
+            if nf.shape != (self.B,):
+                raise _lib.PafcError(f"RnntBeamStream.feed: nframes must be ({self.B},)")
+            nf = nf.clamp(0, n)
+            # host counts go up from pinned memory without a synchronising call (the pinned block is not reused before the copy ran)
+            self._nf.copy_(nf if nf.is_cuda else nf.pin_memory(), non_blocking=True)
+
+    def launch_feed(self):
+        """The feed kernel on the frame-count buffer: reads nothing from the host, allocates nothing."""
+        _lib.check(self.L.pafc_rnnt_beam_stream_feed(self.B, self.Tmax, self.max_total, self.beam, _lib.ptr(self._nf),
+                                                     _lib.ptr(self.ws), self.nws, _lib.stream_of(self.ws)),
+                   "pafc_rnnt_beam_stream_feed")
+
+    def feed(self, nframes, n: Optional[int] = None):
+        """Begin a chunk: row b takes clamp(nframes[b], 0, min(n, Tmax)) frames."""
+        self.load(nframes, n)
+        self.launch_feed()
+
+    def step(self, j: int, top_val: torch.Tensor, top_idx: torch.Tensor, j_dev: Optional[torch.Tensor] = None):
+        """Frame j of the chunk (from the device int64 scalar j_dev when given) for every row that took more than j frames."""
+        _lib.require_gpu(top_val, top_idx, j_dev)
+        if top_val.dtype != torch.float32 or top_idx.dtype != torch.int64 or top_val.numel() != self.B * self.beam * self.beam \
+                or top_idx.numel() != top_val.numel():
+            raise _lib.PafcError("rnnt beam stream step: top_val float32 / top_idx int64 of (B, beam, beam)")
+        _lib.check(self.L.pafc_rnnt_beam_stream_step(self.B, self.Tmax, self.max_total, self.beam, self.blank, int(j),
+                                                     _lib.ptr(j_dev), _lib.ptr(top_val), _lib.ptr(top_idx), _lib.ptr(self.ws),
+                                                     self.nws, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
+                                                     _lib.stream_of(top_val)), "pafc_rnnt_beam_stream_step")
+
+    def select_state(self, h: torch.Tensor, c: torch.Tensor, h_new: torch.Tensor, c_new: torch.Tensor,
+                     next_idx: Optional[torch.Tensor] = None):
+        """h, c (layers, B * beam, hidden) in place: slot i takes row next_idx[i] of [old | new] (default: the last step's)."""
+        rnnt_beam_select_state(h, c, h_new, c_new, self.next_idx if next_idx is None else next_idx, self.B, self.beam)
+
+    def drain(self, counts=None, ld: int = 1):
+        """The n-best of every row as if its stream ended here.  counts: per row the tokens the caller already holds as
+        final (an earlier drain's `committed`), default 0.  Returns a dict of host lists: count (B), committed (B),
+        overflow (B), len (B, beam: total token counts, -1 unused), score (B, beam), tokens (B, beam: the tokens from
+        counts[b] on, at most ld of them).  One device-to-host copy."""
+        B, beam = self.B, self.beam
+        counts = [0] * B if counts is None else [int(c) for c in counts]
+        if counts != self._from_h:
+            self._from.copy_(torch.tensor(counts, dtype=torch.int32).pin_memory(), non_blocking=True)
+            self._from_h = counts
+        ld = max(1, int(ld))
+        # one buffer, one read: score (B, beam) f64 | len (B, beam) | count | committed | overflow (B) | tokens (B, beam, ld) i32
+        nb = B * beam
+        o = [0, nb * 8]
+        for words in (nb, B, B, B, nb * ld):
+            o.append(o[-1] + 4 * words)
+        out = torch.empty(o[-1], dtype=torch.uint8, device=self.device)
+        p = lambda k: _lib.ptr(out[o[k]:o[k + 1]])
+        _lib.check(self.L.pafc_rnnt_beam_stream_drain(B, self.max_total, beam, _lib.ptr(self.ws), self.nws, _lib.ptr(self._from),
+                                                      ld, p(5), p(1), p(0), p(2), p(3), p(4), _lib.stream_of(self.ws)),
+                   "pafc_rnnt_beam_stream_drain")
+        h = out.cpu()                                  # the read
+        self.last_read_bytes = o[-1]
+        i32 = lambda k, *shape: h[o[k]:o[k + 1]].view(torch.int32).view(*shape)
+        lens = i32(1, B, beam).tolist()
+        toks = i32(5, B, beam, ld).tolist()
+        return {"score": h[:o[1]].view(torch.float64).view(B, beam).tolist(), "len": lens, "count": i32(2, B).tolist(),
+                "committed": i32(3, B).tolist(), "overflow": i32(4, B).tolist(),
+                "tokens": [[toks[b][n][:max(0, min(ld, lens[b][n] - counts[b]))] for n in range(beam)] for b in range(B)]}
+
+
+def rnnt_beam_select_state(h: torch.Tensor, c: torch.Tensor, h_new: torch.Tensor, c_new: torch.Tensor, next_idx: torch.Tensor,
+                           B: int, beam: int):
+    """pafc_rnnt_beam_select_state: for h and c (layers, n = B * beam, hidden), in place and in one launch,
+    h[l, i] = (next_idx[i] < n ? h : h_new)[l, next_idx[i] mod n] -- bit-equal to torch.cat([h, h_new], 1).index_select(1,
+    next_idx) copied back.  next_idx must stay within each utterance's slots, as the step kernels emit it."""
+    _lib.require_gpu(h, c, h_new, c_new, next_idx)
+    if h.dim() != 3 or h.shape[1] != B * beam or not (h.shape == c.shape == h_new.shape == c_new.shape) \
+            or not (h.dtype == c.dtype == h_new.dtype == c_new.dtype):
+        raise _lib.PafcError("rnnt_beam_select_state: h, c, h_new, c_new must share the shape (layers, B * beam, hidden) and dtype")
+    if next_idx.dtype != torch.int64 or next_idx.numel() != B * beam:
+        raise _lib.PafcError("rnnt_beam_select_state: next_idx int64 of (B * beam)")
+    _lib.check(_lib.lib().pafc_rnnt_beam_select_state(_lib.dtype_code(h.dtype), h.shape[0], B, beam, h.shape[2], _lib.ptr(h),
+                                                      _lib.ptr(c), _lib.ptr(h_new), _lib.ptr(c_new), _lib.ptr(next_idx),
+                                                      _lib.stream_of(h)), "pafc_rnnt_beam_select_state")
+
+
 def split_bf16(t: torch.Tensor):
     """fp32 tensor -> (hi, lo) bf16 planes with t ~= hi + lo (16 significant bits)."""
     hi = t.to(torch.bfloat16)

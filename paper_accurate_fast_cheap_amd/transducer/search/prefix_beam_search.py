@@ -16,7 +16,7 @@ from typing import List, Optional
 
 import torch
 
-from ...transformer.search import DecodeResult, log_add
+from ...transformer.search import DecodeResult, _common_prefix_len, log_add
 from ...utils import graph_step
 
 
@@ -102,29 +102,7 @@ class PrefixBeamSearch:
             cur = 0
             for i in active:
                 nb = len(beams[i])
-                flat = cand_h[cur:cur + nb].reshape(-1)
-                toks_flat = idx_h[cur:cur + nb].reshape(-1).tolist()
-                vals = flat.tolist()
-                order = torch.argsort(flat, descending=True).tolist()                     # reference: :524
-                beam_A: List[Sequence] = []
-                seen = set()
-                for k in order:
-                    b_idx, tok, score = k // beam_size, toks_flat[k], vals[k]
-                    base = beams[i][b_idx]
-                    new_hyp = list(base.hyp) if tok == self.blank else base.hyp + [tok]
-                    key = tuple(new_hyp)
-                    if key in seen:
-                        for ex in beam_A:
-                            if ex.hyp == new_hyp:
-                                ex.score = log_add([ex.score, score])
-                                break
-                    else:
-                        seen.add(key)
-                        beam_A.append(Sequence(new_hyp, score, (cur + b_idx) if tok == self.blank else (n + cur + b_idx)))
-                        if len(beam_A) >= beam_size:
-                            break
-                beam_A.sort(key=lambda s: s.score, reverse=True)
-                beams[i] = beam_A[:beam_size]
+                beams[i] = self._walk_row(beams[i], cand_h[cur:cur + nb], idx_h[cur:cur + nb], cur, n, beam_size)
                 cur += nb
 
         results = []
@@ -133,6 +111,35 @@ class PrefixBeamSearch:
             nbest_scores = [b.score for b in bs]
             results.append(DecodeResult(tokens=nbest[0], score=nbest_scores[0], nbest=nbest, nbest_scores=nbest_scores))
         return results
+
+    def _walk_row(self, beam: List[Sequence], cand_h: torch.Tensor, idx_h: torch.Tensor, cur: int, n: int,
+                  beam_size: int) -> List[Sequence]:
+        """One frame of one utterance on the host: the candidates (len(beam), beam_size) of its live beams, visited in
+        descending order, equal hypotheses merged with log_add, stopped at beam_size distinct ones, sorted.  A survivor's
+        cache is its column in [old states | new states] of this frame's n slots; the utterance's beams begin at `cur`."""
+        flat = cand_h.reshape(-1)
+        toks_flat = idx_h.reshape(-1).tolist()
+        vals = flat.tolist()
+        order = torch.argsort(flat, descending=True).tolist()                     # reference: :524
+        beam_A: List[Sequence] = []
+        seen = set()
+        for k in order:
+            b_idx, tok, score = k // beam_size, toks_flat[k], vals[k]
+            base = beam[b_idx]
+            new_hyp = list(base.hyp) if tok == self.blank else base.hyp + [tok]
+            key = tuple(new_hyp)
+            if key in seen:
+                for ex in beam_A:
+                    if ex.hyp == new_hyp:
+                        ex.score = log_add([ex.score, score])
+                        break
+            else:
+                seen.add(key)
+                beam_A.append(Sequence(new_hyp, score, (cur + b_idx) if tok == self.blank else (n + cur + b_idx)))
+                if len(beam_A) >= beam_size:
+                    break
+        beam_A.sort(key=lambda s: s.score, reverse=True)
+        return beam_A[:beam_size]
 
     @torch.no_grad()
     def _decode_batch_resident(self, encoder_outs, encoder_lens, ctc_probs, beam_size: int, ctc_weight: float,
@@ -194,3 +201,262 @@ class PrefixBeamSearch:
             nsc = [scores_h[b][k] for k in range(beam_size) if lens_h[b][k] >= 0]
             results.append(DecodeResult(tokens=nbest[0], score=nsc[0], nbest=nbest, nbest_scores=nsc))
         return results
+
+
+class BeamStreamer:
+    """CTC-fused RNN-T prefix beam search of `batch_size` streams fed chunk by chunk, the beams and the LSTM state of
+    every stream carried from one feed to the next.  `model` holds predictor, joint and blank (a Transducer or a
+    PrefixBeamSearch).  Over a stream, for any cut of its frames into chunks, the n-best token lists and float64 scores
+    equal the offline search of the concatenated frames where both sides run the same arithmetic: host loop against
+    prefix_beam_search_decode_batch's, device path against _decode_batch_resident's -- the same frame body on the same
+    B x beam slots and the same candidate walk (csrc/rnnt_beam_frame.inc).
+
+    feed(encoder_chunk (B, n <= max_frames, D), ctc_chunk (B, n, V) log-probs, nframes=None): row b consumes its first
+    nframes[b] frames (default n; 0 = the row sits the chunk out, state unchanged).  Returns per row a partial
+    DecodeResult: the 1-best and n-best if the stream ended here (None with partials=False).  `.committed` holds per row
+    the tokens that can no longer change -- the common prefix of the row's live hypotheses; every later hypothesis is a
+    live one or a live one plus a token -- and only grows.  reset(rows=None) restarts rows (all when None) from their
+    next chunk on, LSTM state zeroed.  results(): per row the full DecodeResult.
+    max_total_frames: the most frames a row may take between resets (the device path's trie pools are sized by it and are
+    not compacted: reset a row at an endpoint).  A feed that would pass it leaves that row as it was, serves the other
+    rows and raises PafcError naming the rows.
+
+    Device path (GPU tensors, beam_size <= 16; hip_ops.RnntBeamStream, never a fallback): fixed (B, max_frames, D) and
+    (B, max_frames, V) staging buffers; the frame body -- predictor step, joint, log-softmax, fusion, top-k, the step
+    kernel, pafc_rnnt_beam_select_state -- reads chunk frame j_dev of them, always under cudnn.flags(enabled=False), and
+    is captured once per streamer into a hipGraph (two eager warm-up frames on a side stream, with no row taking frames,
+    so no state moves) and replayed once per chunk frame: max(nframes) times when the host knows the counts, else n
+    times.  Only a REFUSED capture runs the body eagerly, with the same results.  Host reads per feed: one, the drain
+    (none with partials=False); the chunk copies, the frame counts and the `from` offsets go to the device without a
+    synchronising call (pass nframes as a device int64 tensor to keep them off the host altogether).
+    Host path (CPU tensors, or beam_size > 16): the loop of prefix_beam_search_decode_batch with the beams and each row's
+    LSTM state carried between feeds; the active set of a frame is the rows with nframes[b] > j."""
+
+    def __init__(self, model, batch_size: int, max_frames: int, beam_size: int = 10, ctc_weight: float = 0.3,
+                 transducer_weight: float = 0.7, max_total_frames: int = 4096, use_graph: bool = True, partials: bool = True):
+        if batch_size < 1 or max_frames < 1 or max_total_frames < 1 or beam_size < 1:
+            raise ValueError("BeamStreamer: batch_size, max_frames, max_total_frames and beam_size must be >= 1")
+        self.bs = model if isinstance(model, PrefixBeamSearch) else PrefixBeamSearch(
+            getattr(model, "encoder", None), model.predictor, model.joint, getattr(model, "ctc", None), model.blank)
+        self.blank = self.bs.blank
+        self.B, self.Tmax, self.beam, self.max_total = batch_size, max_frames, beam_size, max_total_frames
+        self.ctc_weight, self.transducer_weight = ctc_weight, transducer_weight
+        self.use_graph, self.want_partials = use_graph, partials
+        self.committed: List[List[int]] = [[] for _ in range(batch_size)]
+        self._device = None
+        self._gpu = None                                   # hip_ops.RnntBeamStream, made by the first feed of GPU tensors
+        self._graph = False                                # False: not tried yet; None: the capture was refused
+        self._frames = [0] * batch_size                    # frames consumed per row, as far as the host knows
+        self._maxlen = [0] * batch_size                    # the longest token list of a row's beam as of the last drain
+        self._full = [False] * batch_size
+        self._beams = [[Sequence([self.blank], 0.0, 0)] for _ in range(batch_size)]      # host path
+        self._hstate: List[Optional[List[torch.Tensor]]] = [None] * batch_size           # host path: (layers, beams, H) per row
+        self._last: Optional[List[DecodeResult]] = None
+
+    @property
+    def graphed(self) -> bool:
+        """Whether the device path replays a captured graph."""
+        return bool(self._graph)
+
+    def reset(self, rows=None):
+        rows = list(range(self.B)) if rows is None else [int(b) for b in rows]
+        for b in rows:
+            self.committed[b] = []
+            self._frames[b], self._maxlen[b], self._full[b] = 0, 0, False
+            self._beams[b] = [Sequence([self.blank], 0.0, 0)]
+            self._hstate[b] = None
+        if self._gpu is not None:
+            self._gpu.reset(None if len(rows) == self.B else rows)
+            for s in self._cache:                          # the LSTM state of the rows' slots
+                if len(rows) == self.B:
+                    s.zero_()
+                else:
+                    s.view(s.shape[0], self.B, -1).index_fill_(1, torch.tensor(rows, device=s.device), 0)
+
+    # ---- device path -------------------------------------------------------------------------------------------
+    def _make_gpu(self, enc: torch.Tensor, ctc: torch.Tensor):
+        from ...hip_ops import RnntBeamStream
+        dev, B, beam = enc.device, self.B, self.beam
+        self._gpu = RnntBeamStream(B, self.Tmax, beam, self.blank, dev, self.max_total)
+        state = self.bs.predictor.init_state(B * beam, method="zero", device=dev)
+        self._cache = [s.to(enc.dtype).contiguous() for s in state]          # static buffers, updated in place
+        self._enc = torch.zeros(B, self.Tmax, enc.shape[2], dtype=enc.dtype, device=dev)
+        self._ctc = torch.zeros(B, self.Tmax, ctc.shape[2], dtype=ctc.dtype, device=dev)
+        self._j = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _frame(self):
+        # the frame body of PrefixBeamSearch._decode_batch_resident on chunk frame j_dev of the staging buffers; every
+        # tensor it touches has a fixed address and shape, so it can be captured once and replayed
+        st, cache, beam, last = self._gpu, self._cache, self.beam, self.Tmax - 1
+        enc = self._enc.index_select(1, self._j.clamp(max=last)).squeeze(1)
+        enc = enc.repeat_interleave(beam, dim=0).unsqueeze(1)                                    # (n, 1, D)
+        logp, new_cache = self.bs.forward_decoder_one_step(enc, st.last_tok, cache)
+        logp = logp.squeeze(1).squeeze(1)                                                        # (n, V)
+        ctc_t = self._ctc.index_select(1, self._j.clamp(max=last)).squeeze(1).repeat_interleave(beam, dim=0)
+        logp = torch.log(torch.add(self.transducer_weight * torch.exp(logp), self.ctc_weight * torch.exp(ctc_t)))
+        top_val, top_idx = logp.topk(beam)
+        st.step(0, top_val.float().contiguous(), top_idx.contiguous(), j_dev=self._j)
+        st.select_state(cache[0], cache[1], new_cache[0].contiguous(), new_cache[1].contiguous())
+        self._j.add_(1)
+
+    def _capture(self):
+        """Once per streamer: two eager frames on a side stream while no row takes frames (they warm every library handle
+        and move no state), then the capture.  A refused capture leaves None: the frames run eagerly."""
+        dev = self._device
+        self._gpu.feed(0)
+        graph_step.on_side_stream(dev, lambda: (self._frame(), self._frame()))
+        self._graph = graph_step.capture(self._frame, dev)[0]
+
+    def _feed_gpu(self, enc, ctc, nf, n):
+        st = self._gpu
+        if n:
+            self._enc[:, :n].copy_(enc.detach())
+            self._ctc[:, :n].copy_(ctc.detach())
+        with torch.backends.cudnn.flags(enabled=False):      # MIOpen's RNN call is not capturable; the same cell eagerly
+            if self.use_graph and self._graph is False:
+                self._capture()
+            st.feed(nf, n)
+            self._j.zero_()
+            steps = n if isinstance(nf, torch.Tensor) else max(nf)
+            for _ in range(steps):
+                if self._graph:
+                    self._graph.replay()
+                else:
+                    self._frame()
+
+    def _drain_gpu(self, ld: int) -> List[DecodeResult]:
+        """One drain from the committed counts on; full token lists are the committed tokens + the returned tails."""
+        d = self._gpu.drain([len(c) for c in self.committed], ld)
+        out = []
+        for b in range(self.B):
+            live = range(d["count"][b])
+            head = list(self.committed[b])
+            nbest = [head + list(d["tokens"][b][k]) for k in live]
+            nsc = [d["score"][b][k] for k in live]
+            new = d["committed"][b] - len(head)
+            if new > 0:
+                self.committed[b] += d["tokens"][b][0][:new]
+            self._maxlen[b] = max([d["len"][b][k] for k in live], default=0)
+            if d["overflow"][b]:
+                self._full[b] = True
+            out.append(DecodeResult(tokens=nbest[0], score=nsc[0], nbest=nbest, nbest_scores=nsc) if nbest
+                       else DecodeResult(tokens=[], score=0.0, nbest=[], nbest_scores=[]))
+        self._overflow = d["overflow"]
+        return out
+
+    def _tail(self) -> int:
+        return max(self._maxlen[b] - len(self.committed[b]) for b in range(self.B))
+
+    # ---- host path ---------------------------------------------------------------------------------------------
+    def _feed_host(self, enc, ctc, nf):
+        bs, B, beam_size, device = self.bs, self.B, self.beam, enc.device
+        beams = self._beams
+        for b in range(B):
+            if self._hstate[b] is None:
+                self._hstate[b] = [s.to(enc.dtype) for s in bs.predictor.init_state(1, method="zero", device=device)]
+        for t in range(max(nf) if nf else 0):
+            active = [i for i in range(B) if t < nf[i]]
+            if not active:
+                break
+            rows, toks, scores = [], [], []
+            for i in active:
+                for s in beams[i]:
+                    rows.append(i)
+                    toks.append(s.hyp[-1])
+                    scores.append(s.score)
+            n = len(rows)
+            rows_t = torch.tensor(rows, device=device)
+            # the live beams' states, utterance by utterance: the columns prefix_beam_search_decode_batch selects
+            cache = [torch.cat([self._hstate[i][k] for i in active], dim=1) for k in (0, 1)]
+            enc_t = enc[rows_t, t, :].unsqueeze(1)                                         # (n, 1, D)
+            logp, new_cache = bs.forward_decoder_one_step(enc_t, torch.tensor(toks, device=device), cache)
+            logp = logp.squeeze(1).squeeze(1)                                              # (n, V)
+            logp = torch.log(torch.add(self.transducer_weight * torch.exp(logp),
+                                       self.ctc_weight * torch.exp(ctc[rows_t, t, :])))
+            top_k_logp, top_k_index = logp.topk(beam_size)                                 # (n, beam)
+            cand = torch.tensor(scores, device=device).unsqueeze(1) + top_k_logp          # float32, as the reference
+            packed = torch.cat([cand.float(), top_k_index.float()], dim=1).cpu()           # ONE device->host copy
+            cand_h = packed[:, :beam_size]
+            idx_h = packed[:, beam_size:].to(torch.int64)
+            pool = [torch.cat([cache[0], new_cache[0]], dim=1), torch.cat([cache[1], new_cache[1]], dim=1)]
+            cur = 0
+            for i in active:
+                nb = len(beams[i])
+                beams[i] = bs._walk_row(beams[i], cand_h[cur:cur + nb], idx_h[cur:cur + nb], cur, n, beam_size)
+                cols = torch.tensor([s.cache for s in beams[i]], device=device)
+                self._hstate[i] = [pool[0].index_select(1, cols), pool[1].index_select(1, cols)]   # the row's own columns
+                for k, s in enumerate(beams[i]):
+                    s.cache = k
+                cur += nb
+
+    def _host_results(self) -> List[DecodeResult]:
+        out = []
+        for b, seqs in enumerate(self._beams):
+            nbest = [s.hyp[1:] for s in seqs]
+            nsc = [s.score for s in seqs]
+            self.committed[b] = list(nbest[0][:_common_prefix_len(nbest)])
+            out.append(DecodeResult(tokens=nbest[0], score=nsc[0], nbest=nbest, nbest_scores=nsc))
+        return out
+
+    # ---- both --------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def feed(self, encoder_chunk: torch.Tensor, ctc_chunk: torch.Tensor, nframes=None) -> Optional[List[DecodeResult]]:
+        from ..._lib import PafcError
+        B = self.B
+        if encoder_chunk.dim() != 3 or encoder_chunk.shape[0] != B or encoder_chunk.shape[1] > self.Tmax:
+            raise ValueError(f"BeamStreamer.feed: the encoder chunk must be ({B}, n <= {self.Tmax}, D)")
+        if ctc_chunk.dim() != 3 or ctc_chunk.shape[:2] != encoder_chunk.shape[:2] or ctc_chunk.device != encoder_chunk.device:
+            raise ValueError("BeamStreamer.feed: the CTC chunk must be (B, n, V) on the encoder chunk's device")
+        n = encoder_chunk.shape[1]
+        on_gpu = encoder_chunk.is_cuda and self.beam <= 16
+        if self._device is None:
+            self._device = encoder_chunk.device
+            if on_gpu:
+                self._make_gpu(encoder_chunk, ctc_chunk)
+        elif encoder_chunk.device != self._device:
+            raise ValueError(f"BeamStreamer.feed: the stream began on {self._device}, this chunk is on {encoder_chunk.device}")
+        if self._gpu is not None and isinstance(nframes, torch.Tensor) and nframes.is_cuda:
+            if nframes.shape != (B,):
+                raise ValueError(f"BeamStreamer.feed: nframes must be ({B},)")
+            nf, over = nframes, []                          # the counts stay on the device: the kernel's flags report overflow
+        else:
+            nf = [n] * B if nframes is None else [max(0, min(n, int(v))) for v in torch.as_tensor(nframes).tolist()]
+            if len(nf) != B:
+                raise ValueError(f"BeamStreamer.feed: nframes must be ({B},)")
+            over = [b for b in range(B) if nf[b] > 0 and (self._full[b] or self._frames[b] + nf[b] > self.max_total)]
+            for b in over:
+                self._full[b] = True
+        if self._gpu is not None:
+            self._feed_gpu(encoder_chunk, ctc_chunk, nf, n)   # (a row in `over` is refused by the kernel itself)
+        else:
+            self._feed_host(encoder_chunk, ctc_chunk, [0 if b in over else v for b, v in enumerate(nf)])
+        if isinstance(nf, list):
+            for b in range(B):
+                if b not in over:
+                    self._frames[b] += nf[b]
+        self._last = None
+        out = None
+        if self.want_partials:
+            if self._gpu is not None:
+                # a list grows by at most one token per frame: the tails fit in the longest tail so far + n
+                out = self._last = self._drain_gpu(self._tail() + n)
+                over = sorted(set(over) | {b for b in range(B) if self._overflow[b] and not isinstance(nf, list)})
+            else:
+                out = self._last = self._host_results()
+        if over:
+            raise PafcError(f"BeamStreamer.feed: rows {over} would pass max_total_frames = {self.max_total} and took no frames; "
+                            "reset them (the other rows were served)")
+        return out
+
+    def partials(self) -> List[DecodeResult]:
+        """Per row the result if the stream ended here (what the last feed returned, when it returned partials)."""
+        if self._last is not None:
+            return self._last
+        return self.results()
+
+    def results(self) -> List[DecodeResult]:
+        if self._gpu is not None:
+            # with partials switched off no drain has bounded the tails: a list holds at most one token per frame
+            ld = self._tail() if self.want_partials else max(1, min(self.max_total, max(self._frames) or self.max_total))
+            return self._drain_gpu(max(1, ld))
+        return self._host_results()

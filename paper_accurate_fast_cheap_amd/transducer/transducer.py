@@ -1,7 +1,8 @@
 """Transducer container around the accelerated encoder (reference: wenet/transducer/transducer.py): encoder + CTC +
 RNN predictor + joint, `decode(methods=[...,'rnnt_beam_search', 'rnnt_greedy_search'])` (:695-813), `beam_search_decode`
-(:644-693), `greedy_search` (:427-472), the runtime step API (:474-505) and `stream_greedy_search`: the streaming encoder
-and the greedy search chunk by chunk with carried decoder state.
+(:644-693), `greedy_search` (:427-472), the runtime step API (:474-505) and `stream_greedy_search` /
+`stream_beam_search`: the streaming encoder and the greedy / CTC-fused prefix beam search chunk by chunk with carried
+decoder state.
 
 Training objective (forward, :105-175): transducer_weight * RNN-T loss + ctc_weight * CTC loss over the accelerated
 encoder.  The reference's RNN-T loss is the third-party `optimized_transducer.transducer_loss` (transducer.py:506-523;
@@ -15,7 +16,7 @@ from ..transformer.asr_model import ASRModel
 from ..transformer.search import DecodeResult
 from .loss import transducer_loss
 from .search.greedy_search import GreedyStreamer, batch_greedy_search
-from .search.prefix_beam_search import PrefixBeamSearch
+from .search.prefix_beam_search import BeamStreamer, PrefixBeamSearch
 
 IGNORE_ID = -1
 FUSED_JOINT = "fused_joint"
@@ -143,6 +144,30 @@ class Transducer(ASRModel):
                     new[b] += tk
             if on_tokens is not None:
                 on_tokens(i, new)
+        return streamer.results()
+
+    @torch.no_grad()
+    def stream_beam_search(self, speech: torch.Tensor, decoding_chunk_size: int, beam_size: int = 10, ctc_weight: float = 0.3,
+                           transducer_weight: float = 0.7, blank_penalty: float = 0.0,
+                           on_partial: Optional[Callable[[int, List[DecodeResult], List[List[int]]], None]] = None,
+                           max_total_frames: Optional[int] = None) -> List[DecodeResult]:
+        """Streaming CTC-fused RNN-T prefix beam search of B equal-length streams (B, T, F): the window walk of
+        ASRModel._stream_windows, each window's frames and their ctc_logprobs into one BeamStreamer.
+        on_partial(window_index, partial_results, committed_tokens_per_row) is called once per window.  Returns per stream
+        the n-best DecodeResult.  Over the stream the result equals the offline rnnt_beam_search of the concatenated encoder
+        outputs of the same steps.  max_total_frames (default: what the speech can produce) sizes the trie pools."""
+        windows = self._stream_windows(speech, decoding_chunk_size, "stream_beam_search")
+        if max_total_frames is None:
+            max_total_frames = speech.size(1) // self.encoder.embed.subsampling_rate + decoding_chunk_size
+        streamer = BeamStreamer(self, speech.size(0), decoding_chunk_size, beam_size, ctc_weight, transducer_weight,
+                                max_total_frames)
+        for i, y in windows:
+            partial = None                                      # (a window may come without output frames)
+            for a in range(0, y.size(1), decoding_chunk_size):      # (the final drain of the look-ahead emits more frames)
+                yc = y[:, a:a + decoding_chunk_size]
+                partial = streamer.feed(yc, self.ctc_logprobs(yc, blank_penalty, self.blank))
+            if on_partial is not None:
+                on_partial(i, partial if partial is not None else streamer.partials(), [list(c) for c in streamer.committed])
         return streamer.results()
 
     # ---- the reference's runtime step API (transducer.py:474-505), for runtimes that drive their own loop ----
