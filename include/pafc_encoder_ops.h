@@ -434,7 +434,8 @@ int pafc_mamba2_scan_state(int B, int L, int H, const void *xbc, long ldx, const
 /* Hand-written bf16 GEMM with fused epilogue, batched (csrc/gemm_bf16.hip: 128 x 128 tiles, two blocks per CU;
  * csrc/gemm_ph.hip: persistent 256-wide phase-pipelined tiles for problems that fill the chip with them -- the entry point
  * picks):
- *   out[z][m][n] = act(alpha * sum_k A[z][m][k] * W[z][n][k] + bias[z][n] + residual[z][m][n]),   z < batch
+ *   out[z][m][n] = act(alpha * sum_k A[z][m][k] * W[z][n][k] + bias[z][n]) + residual[z][m][n],   z < batch
+ * (the activation BEFORE the residual add, as pafc_gemm_bf16_f32out; pafc_gemm_f32 applies it after)
  * A: (M, K) rows lda apart; W: (N, K) = nn.Linear.weight layout, rows ldw apart; out / residual: (M, N), rows ldo / ldr
  * apart; stride*: elements between consecutive batch entries (strideBias = 0 shares one bias); bias, residual may be
  * NULL; residual may alias out.  act: 0 none, 1 SiLU, 2 tanh, 3 ReLU, 4 GLU (out has N / 2 columns: the weight rows come

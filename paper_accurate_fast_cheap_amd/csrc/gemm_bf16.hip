@@ -1,7 +1,7 @@
 // Dense projections of the encoder as a hand-written bf16 GEMM with fused epilogues (gfx950).
 // C ABI: include/pafc_encoder_ops.h: pafc_gemm_bf16.
 //
-//   out[z][m][n] = act(alpha * sum_k A[z][m][k] * W[z][n][k] + bias[z][n] + residual[z][m][n])
+//   out[z][m][n] = act(alpha * sum_k A[z][m][k] * W[z][n][k] + bias[z][n]) + residual[z][m][n]
 // i.e. nn.Linear (weight stored (N, K), K contiguous) with the bias, the activation (SiLU / tanh / ReLU), the
 // ff_scale and the residual add applied to the fp32 accumulator before the single rounding to bf16.  Replaces the
 // FFN / 1x1-conv / r,k,v / output projections of ConformerEncoderLayer, ConvolutionModule and RWKV_Tmix_x060c

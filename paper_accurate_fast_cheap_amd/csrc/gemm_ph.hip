@@ -2,7 +2,7 @@
 // C ABI: include/pafc_encoder_ops.h: pafc_gemm_bf16 dispatches here for large problems (see gemm_bf16.hip for the
 // 128 x 128 kernel that keeps the small and oddly shaped ones); pafc_gemm_ph_ex is the general entry point.
 //
-//   out[z][m][n] = act(alpha * sum_k A[z][m][k] * W[z][n][k] + bias[z][n] + residual[z][m][n])
+//   out[z][m][n] = act(alpha * sum_k A[z][m][k] * W[z][n][k] + bias[z][n]) + residual[z][m][n]
 // nn.Linear (weight (N, K), K contiguous) with bias, SiLU / tanh / ReLU / GLU, ff_scale and the residual add applied to
 // the fp32 accumulator before the single rounding: the FFN, 1x1-conv, r/k/v and output projections of
 // ConformerEncoderLayer, ConvolutionModule and RWKV_Tmix_x060c (wenet/transformer/positionwise_feed_forward.py:47-55,

@@ -1926,7 +1926,8 @@ def gemm_f32_ok(a: torch.Tensor, w: torch.Tensor) -> bool:
 
 def linear_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: str = "silu",
                     alpha: float = 1.0, residual: Optional[torch.Tensor] = None, inplace: bool = False):
-    """act(alpha * x @ weight.T + residual + bias) as ONE GEMM with a fused epilogue (act: 'silu' or 'none'), for the operands
+    """act(alpha * x @ weight.T + bias), or alpha * x @ weight.T + bias + residual, as ONE GEMM with a fused epilogue (act:
+    'silu' or 'none'; not an activation together with a residual: the layer never pairs them), for the operands
     the tiled bf16 kernels do not take: fp32 (exact fp32 products on the fp32 matrix cores, pafc_gemm_f32) and bf16 shapes off the
     bf16 kernels' grid (K % 64 or N % 8: through the same kernel in fp32, one rounding at the end).  bias is added as given
     (not scaled by alpha).  inplace: write the result over ``residual``.
@@ -1943,6 +1944,9 @@ def linear_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
         raise _lib.PafcError("linear_bias_act: residual must be (rows, N) in the activation dtype")
     if act not in ("silu", "none"):
         raise _lib.PafcError("linear_bias_act: act is 'silu' or 'none'")
+    if act != "none" and residual is not None:
+        # pafc_gemm_f32 applies the activation after the residual add, the bf16 kernels before it
+        raise _lib.PafcError("linear_bias_act: an activation with a residual (the layer never pairs them)")
     x2 = x.reshape(rows, K)
     r2 = residual.reshape(rows, N) if residual is not None else None
     if x.dtype == torch.float32 and gemm_f32_ok(x2, weight):
@@ -1961,7 +1965,7 @@ def linear_bias_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
         y = y * alpha
     if bias is not None:
         y = y + bias
-    if residual is not None:           # act(alpha * x W^T + residual + bias), as the fused kernels compute it
+    if residual is not None:
         y = y + residual.view(y.shape)
     if act == "silu":
         y = torch.nn.functional.silu(y)

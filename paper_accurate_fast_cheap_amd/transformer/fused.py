@@ -250,7 +250,8 @@ def _skinny(x: torch.Tensor, w: torch.Tensor, glu: bool = False) -> bool:
 
 def proj(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], act: str = "none", alpha: float = 1.0,
          residual: Optional[torch.Tensor] = None, inplace: bool = False) -> torch.Tensor:
-    """act(alpha * x w^T + bias + residual) as ONE GEMM with a fused epilogue; w in nn.Linear layout (N, K)."""
+    """act(alpha * x w^T + bias) + residual as ONE GEMM with a fused epilogue (no caller passes an activation together with a
+    residual); w in nn.Linear layout (N, K)."""
     if _own_gemm(x, w):
         N, K = w.shape
         x2 = x.reshape(-1, K)

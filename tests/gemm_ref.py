@@ -1,0 +1,239 @@
+"""float64 reference of the fused-epilogue GEMMs (csrc/gemm_ph.hip, csrc/gemm_bf16.hip) and a derived per-element error
+bound.  Plain torch, CPU or GPU, no kernels of this package.
+
+`ideal(form, operands)` is the float64 value of what a kernel is specified to compute from the operands AS IT RECEIVES
+THEM (the bf16 values, the planes of a split operand), so it depends on torch alone:
+
+    P    = A W^T                                   plain bf16 operands: the float64 product of the bf16 values
+         = hi W0^T + lo W1^T + hi W2^T             split operands: A = [hi | lo], W = [W0 | W1 | W2] = [hi_w | hi_w | lo_w]
+    pre  = alpha P + bias
+    out  = act(pre) + residual                     the activation BEFORE the residual
+    GLU:   out[t h + c] = pre[2h t + c] * sigmoid(pre[2h t + h + c]),  h = 32 (operands["glu_half"])
+
+`bound(form, operands)` is what a correct kernel may differ from `ideal` by, per element.  With u = 2^-24:
+
+    S    = |alpha| (|A| |W|^T) + |bias| + |residual|      over the operands the kernel multiplies (three plane products)
+    E    = L (Kw + 8) u S       fp32 accumulation of the Kw columns the K loop walks, in any order, plus up to eight fp32
+                                roundings in the epilogue (the alpha / bias fma, the activation's own steps, the residual
+                                add); L = the activation's Lipschitz constant (1; SiLU: 1.1 >= sup |silu'| = 1.0998).
+                                GLU: E = E_a + (|a| + E_a) E_b / 4   (|d/da| = sigmoid <= 1, |d/db| = |a| sigmoid' <= |a| / 4)
+    out  = u_out (|ideal| + E)  the ONE rounding to the output type, relative to the value that is rounded:
+                                fp32 2^-24; planes hi + lo 2^-16 (lo = bf16(x - hi) leaves 2^-8 of 2^-8); bf16 2^-8.
+    act  = activation_term()    SiLU / tanh / GLU: 4 x the worst error of the same formula in float32 torch against
+                                float64 over the case's own pre-activation values (4 x: fast exponentials and reciprocals).
+                                A measured number of torch's, not of the kernel; tests write it to the parity log.
+    bound = E + out + act
+
+The bf16 term is 2^-8 |x|, not 2^-9 |x|: half a bf16 step is 2^(e - 8) for |x| in [2^e, 2^(e + 1)), which is 2^-8 |x| at the
+bottom of the binade (x = 1 + 2^-8 rounds to 1 or 1 + 2^-7, either way 2^-8 off).  tests/test_gemm_ref.py shows that a
+correctly rounded `ideal` breaks a 2^-9 term on a quarter of the elements, and that 2^-8 still tells a second rounding, a
+dropped plane product and a bias scaled by alpha from a correct kernel."""
+from collections import namedtuple
+
+import torch
+
+# a_split: A / W are planes of fp32 operands; out: "bf16" | "f32" | "planes"; act: "none" | "silu" | "tanh" | "relu" | "glu";
+# res: None | "bf16" | "f32" (the residual's type)
+Form = namedtuple("Form", "a_split out act res")
+
+U32 = 2.0 ** -24
+_U_OUT = {"f32": 2.0 ** -24, "planes": 2.0 ** -16, "bf16": 2.0 ** -8}
+_LIP = {"none": 1.0, "relu": 1.0, "tanh": 1.0, "silu": 1.1, "glu": 1.0}
+
+# every instantiation pafc_gemm_ph_ex2 can launch (the CONV and folded-LayerNorm ones have their own entry points)
+SHARED_FRAGMENT_FORMS = {
+    "split-f32": Form(True, "f32", "none", None),
+    "split-f32-res": Form(True, "f32", "none", "f32"),
+    "split-f32-res-inplace": Form(True, "f32", "none", "f32"),
+    "split-f32-glu": Form(True, "f32", "glu", None),
+    "split-planes": Form(True, "planes", "none", None),
+    "split-planes-silu": Form(True, "planes", "silu", None),
+}
+HI_LO_HI_FORMS = {
+    "split-bf16": Form(True, "bf16", "none", None),
+    "split-bf16-silu": Form(True, "bf16", "silu", None),
+    "split-bf16-res": Form(True, "bf16", "none", "bf16"),
+    "split-bf16-glu": Form(True, "bf16", "glu", None),
+}
+PLAIN_FORMS = {
+    "bf16": Form(False, "bf16", "none", None),
+    "bf16-silu": Form(False, "bf16", "silu", None),
+    "bf16-tanh": Form(False, "bf16", "tanh", None),
+    "bf16-relu": Form(False, "bf16", "relu", None),
+    "bf16-glu": Form(False, "bf16", "glu", None),
+    "bf16-res": Form(False, "bf16", "none", "bf16"),
+    "f32": Form(False, "f32", "none", None),
+    "f32-glu": Form(False, "f32", "glu", None),
+    "f32-res": Form(False, "f32", "none", "f32"),
+    "planes": Form(False, "planes", "none", None),
+    "planes-silu": Form(False, "planes", "silu", None),
+}
+FORMS = {**SHARED_FRAGMENT_FORMS, **HI_LO_HI_FORMS, **PLAIN_FORMS}
+
+
+def split_hi_lo(x: torch.Tensor):
+    """fp32 x -> bf16 (hi, lo) with hi = bf16(x), lo = bf16(x - hi): x = hi + lo to 2^-16 relative."""
+    hi = x.float().bfloat16()
+    lo = (x.float() - hi.float()).bfloat16()
+    return hi, lo
+
+
+def split_a(x: torch.Tensor, plane_block: int = 0) -> torch.Tensor:
+    """fp32 (..., K) -> the split A operand (..., 2K): [hi K | lo K], or blocks [hi PB | lo PB] ... of plane_block columns."""
+    hi, lo = split_hi_lo(x)
+    if not plane_block:
+        return torch.cat([hi, lo], dim=-1)
+    K = x.shape[-1]
+    sh = x.shape[:-1] + (K // plane_block, plane_block)
+    return torch.cat([hi.reshape(sh), lo.reshape(sh)], dim=-1).reshape(x.shape[:-1] + (2 * K,))
+
+
+def split_w(w: torch.Tensor) -> torch.Tensor:
+    """fp32 (..., K) -> the split weight (..., 3K) = [hi | hi | lo]."""
+    hi, lo = split_hi_lo(w)
+    return torch.cat([hi, hi, lo], dim=-1)
+
+
+def glu_interleave(t: torch.Tensor, half: int = 32, dim: int = 0) -> torch.Tensor:
+    """Rows [values C | gates C] along `dim` -> blocks of `half` value rows followed by the `half` gate rows of the same
+    channels (the row order the kernels want for act "glu")."""
+    t = t.movedim(dim, 0)
+    C = t.shape[0] // 2
+    v = t[:C].reshape(C // half, half, *t.shape[1:])
+    g = t[C:].reshape(C // half, half, *t.shape[1:])
+    return torch.cat([v, g], dim=1).reshape(t.shape).movedim(0, dim).contiguous()
+
+
+def planes_value(out: torch.Tensor, n: int, lo_off: int = None) -> torch.Tensor:
+    """A planes output (..., >= lo_off + n) bf16 read back as the float64 value hi + lo."""
+    lo_off = n if lo_off is None else lo_off
+    return out[..., :n].double() + out[..., lo_off:lo_off + n].double()
+
+
+def _planes_of(form: Form, ops: dict):
+    """[(A plane, W plane)] the kernel multiplies, as float64, and Kw."""
+    A, W = ops["A"].double(), ops["W"].double()
+    if not form.a_split:
+        return [(A, W)], A.shape[-1]
+    K = W.shape[-1] // 3
+    pb = ops.get("plane_block", 0) or K
+    blocks = A.reshape(A.shape[:-1] + (K // pb, 2, pb))
+    hi = blocks[..., 0, :].reshape(A.shape[:-1] + (K,))
+    lo = blocks[..., 1, :].reshape(A.shape[:-1] + (K,))
+    return [(hi, W[..., :K]), (lo, W[..., K:2 * K]), (hi, W[..., 2 * K:])], 3 * K
+
+
+def products(form: Form, ops: dict):
+    """(P, |A| |W|^T, Kw) in float64; kept in `ops` so that ideal(), bound() and the forms that share operands form them once."""
+    if "_prod" not in ops:
+        pairs, Kw = _planes_of(form, ops)
+        P = sum(a @ w.transpose(-1, -2) for a, w in pairs)
+        Sp = sum(a.abs() @ w.abs().transpose(-1, -2) for a, w in pairs)
+        ops["_prod"] = (P, Sp, Kw)
+    return ops["_prod"]
+
+
+def rows(ops: dict, M: int) -> dict:
+    """The problem of the first M rows: A, the residual and the products sliced, everything else shared."""
+    out = dict(ops)
+    out["A"] = ops["A"][..., :M, :]
+    if ops.get("residual") is not None:
+        out["residual"] = ops["residual"][..., :M, :]
+    if "_prod" in ops:
+        P, Sp, Kw = ops["_prod"]
+        out["_prod"] = (P[..., :M, :], Sp[..., :M, :], Kw)
+    return out
+
+
+def _row_vec(t):
+    return 0.0 if t is None else t.double().unsqueeze(-2)
+
+
+def _glu_parts(x: torch.Tensor, half: int):
+    b = x.reshape(x.shape[:-1] + (x.shape[-1] // (2 * half), 2, half))
+    sh = x.shape[:-1] + (x.shape[-1] // 2,)
+    return b[..., 0, :].reshape(sh), b[..., 1, :].reshape(sh)
+
+
+def _act(form: Form, pre: torch.Tensor, half: int) -> torch.Tensor:
+    if form.act == "glu":
+        a, b = _glu_parts(pre, half)
+        return a * torch.sigmoid(b)
+    if form.act == "silu":
+        return pre * torch.sigmoid(pre)
+    if form.act == "tanh":
+        return torch.tanh(pre)
+    if form.act == "relu":
+        return torch.relu(pre)
+    return pre
+
+
+def pre_activation(form: Form, ops: dict) -> torch.Tensor:
+    P, _, _ = products(form, ops)
+    return float(ops.get("alpha", 1.0)) * P + _row_vec(ops.get("bias"))
+
+
+def ideal(form: Form, ops: dict) -> torch.Tensor:
+    out = _act(form, pre_activation(form, ops), ops.get("glu_half", 32))
+    if ops.get("residual") is not None:
+        out = out + ops["residual"].double()
+    return out
+
+
+def activation_term(form: Form, ops: dict) -> float:
+    """4 x the worst |float32 formula - float64 formula| over this case's pre-activation values (0 for none / ReLU)."""
+    if form.act not in ("silu", "tanh", "glu"):
+        return 0.0
+    pre = pre_activation(form, ops).cpu()          # measured with the CPU's float32 kernels, wherever the operands live
+    half = ops.get("glu_half", 32)
+    return 4.0 * float((_act(form, pre.float(), half).double() - _act(form, pre, half)).abs().max())
+
+
+def bound(form: Form, ops: dict, act_term: float = None) -> torch.Tensor:
+    _, Sp, Kw = products(form, ops)
+    S = abs(float(ops.get("alpha", 1.0))) * Sp
+    if ops.get("bias") is not None:
+        S = S + _row_vec(ops["bias"]).abs()
+    res = ops["residual"].double().abs() if ops.get("residual") is not None else 0.0
+    c = (Kw + 8) * U32
+    if form.act == "glu":
+        half = ops.get("glu_half", 32)
+        Ea, Eb = _glu_parts(c * S, half)
+        a, _ = _glu_parts(pre_activation(form, ops), half)
+        E = Ea + (a.abs() + Ea) * Eb / 4
+    else:
+        E = _LIP[form.act] * c * (S + res)
+    if act_term is None:
+        act_term = activation_term(form, ops)
+    return E + _U_OUT[form.out] * (ideal(form, ops).abs() + E) + act_term
+
+
+def round_to(form: Form, x: torch.Tensor) -> torch.Tensor:
+    """float64 x rounded once to the form's output type, read back as float64 (planes: hi + lo)."""
+    x32 = x.float()
+    if form.out == "f32":
+        return x32.double()
+    if form.out == "bf16":
+        return x32.bfloat16().double()
+    hi, lo = split_hi_lo(x32)
+    return hi.double() + lo.double()
+
+
+def make_operands(form: Form, M: int, N: int, K: int, seed: int, batch: int = 0, alpha: float = 1.0, plane_block: int = 0,
+                  shared_bias: bool = False, device="cpu") -> dict:
+    """Seeded operands as the kernel receives them: randn A, W scaled by K^-0.5, bias by 0.3, residual by 1; bias and
+    residual in the types the form takes.  batch > 0 adds a leading batch dimension.  GLU: N counts the weight rows."""
+    g = torch.Generator().manual_seed(seed)
+    lead = (batch,) if batch else ()
+    rnd = lambda *s: torch.randn(lead + s, generator=g)
+    a, w = rnd(M, K), rnd(N, K) * K ** -0.5
+    b = (torch.randn((N,), generator=g) if shared_bias else rnd(N)) * 0.3
+    No = N // 2 if form.act == "glu" else N
+    r = rnd(M, No)
+    ops = {"alpha": alpha, "plane_block": plane_block}
+    ops["A"] = split_a(a, plane_block) if form.a_split else a.bfloat16()
+    ops["W"] = split_w(w) if form.a_split else w.bfloat16()
+    ops["bias"] = b.bfloat16() if form.out == "bf16" else b
+    ops["residual"] = None if form.res is None else (r.bfloat16() if form.res == "bf16" else r)
+    ops["a32"], ops["w32"] = a, w                # the fp32 operands the planes were split from
+    return {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in ops.items()}

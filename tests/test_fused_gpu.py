@@ -12,6 +12,21 @@ from tests.conftest import load_golden
 pytestmark = pytest.mark.gpu
 
 
+def _one_rounding(got, a, w, b, act="none", alpha=1.0, residual=None, glu_half=32, what=""):
+    """The bf16-output contract, "everything is applied to the fp32 accumulator, one rounding to bf16": |got - ideal| <= bound
+    of tests/gemm_ref.py, the float64 value of act(alpha a w^T + b) + residual from the same bf16 operands and what fp32
+    accumulation plus ONE rounding may differ from it by.  A second rounding, a bias added after the rounding or a different
+    epilogue order fall outside.  Computed on the GPU in float64.  -> worst err / bound."""
+    from tests import gemm_ref
+    dev = lambda t: None if t is None else t.cuda()
+    form = gemm_ref.Form(False, "bf16", act, None if residual is None else "bf16")
+    ops = dict(A=dev(a), W=dev(w), bias=dev(b), residual=dev(residual), alpha=alpha, glu_half=glu_half)
+    err = (got.cuda().double() - gemm_ref.ideal(form, ops)).abs()
+    worst = float((err / gemm_ref.bound(form, ops)).max())
+    assert worst <= 1.0, (what, act, worst)
+    return worst
+
+
 @pytest.mark.parametrize("dtype,out_dtype", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
                                              (torch.float32, torch.bfloat16)])
 @pytest.mark.parametrize("C", [128, 512])
@@ -124,6 +139,26 @@ def test_linear_bias_silu_epilogue(hip, dtype):
     same = linear_bias_act(x.cuda(), w.cuda(), None, "none", residual=buf, inplace=True)
     assert same.data_ptr() == buf.data_ptr()
     torch.testing.assert_close(buf.cpu().float(), res.float() + F.linear(x.float(), w.float()), **tol)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_linear_bias_act_refuses_an_activation_with_a_residual(hip, dtype):
+    """The layer never pairs a residual with an activation, and the kernels do not agree on the order of the two: the front
+    end refuses the pair instead of answering by dtype."""
+    from paper_accurate_fast_cheap_amd._lib import PafcError
+    from paper_accurate_fast_cheap_amd.hip_ops import linear_bias_act
+    x = synth.randn((41, 128), 1).to(dtype).cuda()
+    w = synth.randn((256, 128), 2, 0.1).to(dtype).cuda()
+    b = synth.randn((256,), 3, 0.2).to(dtype).cuda()
+    res = synth.randn((41, 256), 4).to(dtype).cuda()
+    keep = res.clone()
+    with pytest.raises(PafcError):
+        linear_bias_act(x, w, b, "silu", residual=res)
+    with pytest.raises(PafcError):
+        linear_bias_act(x, w, b, "silu", residual=res, inplace=True)
+    assert torch.equal(res, keep)
+    linear_bias_act(x, w, b, "none", residual=res)            # each alone is served
+    linear_bias_act(x, w, b, "silu")
 
 
 @pytest.mark.parametrize("M,N,K,act,res,bias", [
@@ -344,11 +379,14 @@ def test_gemm_bf16_hand_written(hip, M, N, K, Z, act):
     tol = dict(rtol=2 ** -7, atol=2e-2)
     got = gemm_bf16(a.cuda(), w.cuda(), b.cuda(), act)
     torch.testing.assert_close(got.cpu().float(), f(lin + bb), **tol)
+    _one_rounding(got, a, w, b, act, what="bias + act")
     got = gemm_bf16(a.cuda(), w.cuda(), None, act, alpha=0.5, residual=r.cuda())
     torch.testing.assert_close(got.cpu().float(), f(0.5 * lin) + r.float(), **tol)
+    _one_rounding(got, a, w, None, act, alpha=0.5, residual=r, what="act, then the residual")
     buf = r.cuda().clone()
     assert gemm_bf16(a.cuda(), w.cuda(), b.cuda(), "none", residual=buf, out=buf).data_ptr() == buf.data_ptr()
     torch.testing.assert_close(buf.cpu().float(), lin + bb + r.float(), **tol)
+    _one_rounding(buf, a, w, b, residual=r, what="over the residual")
 
 
 @pytest.mark.parametrize("tile", ["128x128", "128x64", "64x64", "auto"])
@@ -371,8 +409,12 @@ def test_gemm_bf16_tile_variants_mid_rows(hip, monkeypatch, tile, M, N, K, Z, ac
     lin = torch.matmul(a.float(), w.float().transpose(-1, -2))
     bb = b.float().unsqueeze(-2) if Z > 1 else b.float()
     tol = dict(rtol=2 ** -7, atol=1e-2)
-    torch.testing.assert_close(gemm_bf16(a, w, b, act).float(), f(lin + bb), **tol)
-    torch.testing.assert_close(gemm_bf16(a, w, None, act, alpha=0.5, residual=r).float(), f(0.5 * lin) + r.float(), **tol)
+    got = gemm_bf16(a, w, b, act)
+    torch.testing.assert_close(got.float(), f(lin + bb), **tol)
+    _one_rounding(got, a, w, b, act, what=tile)
+    got = gemm_bf16(a, w, None, act, alpha=0.5, residual=r)
+    torch.testing.assert_close(got.float(), f(0.5 * lin) + r.float(), **tol)
+    _one_rounding(got, a, w, None, act, alpha=0.5, residual=r, what=tile + " residual")
     # nothing is written past the matrix: rows beyond M of a larger buffer keep their sentinel
     buf = torch.full(shp(M + 70, N), 7.0, dtype=bf, device="cuda")
     view = buf[..., :M, :]
@@ -646,8 +688,10 @@ def test_gemm_bf16_glu_epilogue(hip, M, N, K):
     got = gemm_bf16(a.cuda(), glu_interleave(w.cuda()), glu_interleave(b.cuda()), act="glu")
     assert got.shape == (M, N // 2)
     torch.testing.assert_close(got.cpu().float(), want, rtol=2 ** -7, atol=1e-2)
+    _one_rounding(got, a, glu_interleave(w), glu_interleave(b), "glu", glu_half=64, what="bias")
     got = gemm_bf16(a.cuda(), glu_interleave(w.cuda()), None, act="glu")
     torch.testing.assert_close(got.cpu().float(), F.glu(F.linear(a.float(), w.float()), dim=-1), rtol=2 ** -7, atol=1e-2)
+    _one_rounding(got, a, glu_interleave(w), None, "glu", glu_half=64, what="no bias")
 
 
 @pytest.mark.parametrize("B,T,Fd,C", [(1, 7, 80, 512), (3, 64, 80, 256), (2, 33, 23, 128), (1, 1003, 80, 512)])
@@ -1101,13 +1145,16 @@ def test_gemm_phase_pipelined(hip, tile_n, tile_m, M, N, K, Z, act):
     want = f(lin + (b.float().unsqueeze(-2) if Z > 1 else b.float()))
     got = gemm_bf16_ph(a.cuda(), w.cuda(), b.cuda(), act, tile_n=tile_n, tile_m=tile_m)
     torch.testing.assert_close(got.cpu().float(), want, rtol=2 ** -7, atol=2e-2)
+    _one_rounding(got, a, w, b, act, what="bias + act")
     got = gemm_bf16_ph(a.cuda(), w.cuda(), None, "none", alpha=0.5, residual=r.cuda(), tile_n=tile_n, tile_m=tile_m)
     torch.testing.assert_close(got.cpu().float(), r.float() + 0.5 * lin, rtol=2 ** -7, atol=2e-2)
+    _one_rounding(got, a, w, None, alpha=0.5, residual=r, what="residual")
     buf = r.cuda().clone()
     same = gemm_bf16_ph(a.cuda(), w.cuda(), b.cuda(), "none", residual=buf, out=buf, tile_n=tile_n, tile_m=tile_m)
     assert same.data_ptr() == buf.data_ptr()
     torch.testing.assert_close(buf.cpu().float(), r.float() + lin + (b.float().unsqueeze(-2) if Z > 1 else b.float()),
                                rtol=2 ** -7, atol=2e-2)
+    _one_rounding(buf, a, w, b, residual=r, what="over the residual")
 
 
 @pytest.mark.parametrize("tile_n", [256])
@@ -1123,6 +1170,7 @@ def test_gemm_phase_pipelined_glu(hip, tile_n, M, N, K):
     got = gemm_bf16_ph(a.cuda(), glu_interleave(w.cuda(), half), glu_interleave(b.cuda(), half), act="glu", tile_n=tile_n)
     assert got.shape == (M, N // 2)
     torch.testing.assert_close(got.cpu().float(), want, rtol=2 ** -7, atol=2e-2)
+    _one_rounding(got, a, glu_interleave(w, half), glu_interleave(b, half), "glu", glu_half=half)
 
 
 
@@ -1153,13 +1201,17 @@ def test_gemm_at_the_production_shape(hip, K, N, Z, act, res, name):
         half = gemm_glu_half(M, N, K)
         got = gemm_bf16(a, glu_interleave(w, half), glu_interleave(b, half), act="glu")
         want = F.glu(lin, dim=-1)
+        one = _one_rounding(got, a, glu_interleave(w, half), glu_interleave(b, half), "glu", glu_half=half, what=name)
     elif res:
         wb = alpha * (lin - (b.float() if b is not None else 0)) + (b.float() if b is not None else 0) + r.float()
         got = gemm_bf16(a, w, b, "none", alpha=alpha, residual=r)
         want = wb
+        one = _one_rounding(got, a, w, b, alpha=alpha, residual=r, what=name)
     else:
         got = gemm_bf16(a, w, b, act)
         want = {"none": lambda t: t, "silu": F.silu}[act](lin)
+        one = _one_rounding(got, a, w, b, act, what=name)
+    parity_log.record(f"gemm M=44998/{name}", one_rounding_worst_err_over_bound=one)
     assert got.shape == want.shape and got.dtype == bf
     d = (got.float() - want).abs()
     tol = 2 ** -7 * want.abs() + 2e-2
