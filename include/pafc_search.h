@@ -115,6 +115,35 @@ int pafc_ctc_greedy_stream(int dtype, int B, int Tmax, int V, const void *scores
                            void *workspace, size_t workspace_bytes, int32_t *best, int32_t *tokens, int32_t *ntok,
                            int64_t *frames, pafc_stream_t stream);
 
+/* CTC forced alignment (force_align, wenet/utils/ctc_utils.py:105-161, for B utterances at once): the best path of the
+ * log-probabilities lp through the extended labels l' = (blank, y_1, blank, ..., y_L, blank), S = 2 L + 1 states, and the
+ * frames of its tokens.  One block per utterance, one launch; nothing reads the host, allocates or synchronises.
+ * Recursion, all in fp32, each value one add: alpha_t(s) = max(cands) + lp[t, l'_s], the candidates in this order
+ *   alpha_{t-1}(s); alpha_{t-1}(s-1) if s >= 1; alpha_{t-1}(s-2) if s >= 2, l'_s != blank and l'_s != l'_{s-2};
+ * a later candidate wins only when strictly greater (torch.argmax).  alpha_0(0) = lp[0, blank], alpha_0(1) = lp[0, y_1], the
+ * rest -inf.  The path ends in state S-1 unless alpha(S-2) > alpha(S-1).  -inf entries are data; NaN input is undefined.
+ * State 0 has itself as its only predecessor (the reference indexes state -1 there, the LAST state: DESIGN.md).
+ * lp: (B, T, V) of PAFC_F32 or PAFC_BF16 in rows of ldl >= V elements.  hlens (B) int32 frames; ys (B, ldy) int64 labels,
+ * ylens (B) int32 label counts.  ldy is also the most labels an utterance may have (Lmax): it sizes the workspace and
+ * the kernel's LDS, two frames of alpha with two guard entries each: 2 x (64 ceil((2 ldy + 1) / 64) + 2) x 4 bytes of the
+ * CU's 160 KiB.  The cap is ldy <= 8191 (S <= 16383: 128 KiB of LDS, 16 states per thread of a 1024-thread block -- more
+ * per thread spills registers before the LDS is full), else PAFC_ERR_UNSUPPORTED; V < 2^30.  ys may be NULL when ldy == 0,
+ * first / last when ld_times == 0.
+ * align (B, T) int32: the token of every frame, -1 from hlens[b] on.  first / last (B, ld_times >= ldy) int32: the first and
+ * the last frame of label i's state 2 i + 1 (first = gen_ctc_peak_time of the alignment), -1 from ylens[b] on.
+ * score (B) fp32: the end state's alpha.  ok (B) int32: 1, or 0 for a row that cannot be aligned -- hlens[b] outside [1, T],
+ * ylens[b] outside [0, ldy], a label that is the blank or outside [0, V), more labels plus adjacent equal labels than frames,
+ * a final score of -inf -- which gets score -inf and -1 in all of align, first and last.  L = 0: every frame blank.
+ * Frames beyond hlens[b] and labels beyond ylens[b] are never read.
+ * workspace: pafc_ctc_align_workspace_bytes(B, T, ldy) = B T ceil((2 ldy + 1) / 64) 16 + 32 B bytes (0 when B, T <= 0 or
+ *   Lmax < 0), 16-byte aligned: the back-pointers (0, 1 or 2: 2 bits each, two 64-bit planes per 64 states and frame) and, per
+ *   utterance, three 64-bit wall-clock stamps (start, recursion done, backtrace done).  The stamps are a diagnostic for
+ *   tools/bench_ctc_align.py, not a stable contract: only the size of the workspace is, what the kernel leaves in it is not. */
+size_t pafc_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int pafc_ctc_align(int dtype, int B, int T, int V, const void *lp, long ldl, const int32_t *hlens, const int64_t *ys, int ldy,
+                   const int32_t *ylens, int blank, void *workspace, size_t workspace_bytes, int32_t *align, int32_t *first,
+                   int32_t *last, int ld_times, float *score, int32_t *ok, pafc_stream_t stream);
+
 /* CTC-fused RNN-T prefix beam search (PrefixBeamSearch.prefix_beam_search_decode_batch,
  * wenet/transducer/search/prefix_beam_search.py:428-574): the per-frame candidate walk on the device.  The caller keeps
  * B x beam fixed slots; per frame it runs predictor step + joint + log-softmax + fusion + top-`beam` for all slots with

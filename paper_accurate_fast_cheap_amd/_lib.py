@@ -149,6 +149,8 @@ SIGNATURES = {
     "pafc_ctc_greedy_stream_workspace_bytes": (Z, [I]),
     "pafc_ctc_greedy_stream_reset": (I, [I, P, P, Z, P]),
     "pafc_ctc_greedy_stream": (I, [I, I, I, I, P, P, I, P, Z, P, P, P, P, P]),
+    "pafc_ctc_align_workspace_bytes": (Z, [I, I, I]),
+    "pafc_ctc_align": (I, [I, I, I, I, P, G, P, P, I, P, I, P, Z, P, P, P, I, P, P, P]),
     "pafc_rnnt_beam_workspace_bytes": (Z, [I, I, I]),
     "pafc_rnnt_beam_init": (I, [I, I, I, I, P, Z, P, P, P]),
     "pafc_rnnt_beam_step": (I, [I, I, I, I, I, P, P, P, P, P, Z, P, P, P]),

@@ -2211,6 +2211,47 @@ def ctc_greedy(scores: torch.Tensor, lens: Optional[torch.Tensor], blank_id: int
     return (tokens, ntok, frames) if want_frames else (tokens, ntok)
 
 
+def ctc_align(lp: torch.Tensor, hlens: torch.Tensor, ys: torch.Tensor, ylens: torch.Tensor, blank_id: int = 0,
+              workspace: Optional[torch.Tensor] = None):
+    """GPU-resident CTC forced alignment (include/pafc_search.h: pafc_ctc_align, csrc/ctc_align.hip).  lp (B, T, V) float32 or
+    bfloat16 log-probabilities (a view with row stride >= V is taken as it is), hlens (B) frames, ys (B, Lmax) labels, ylens (B)
+    label counts -> (align (B, T) int32 [-1 beyond hlens], first (B, Lmax) int32, last (B, Lmax) int32 [-1 beyond ylens],
+    score (B) float32, ok (B) int32).  One launch, no host read: the call can be captured or its results fetched later.
+    workspace: a uint8 tensor of at least pafc_ctc_align_workspace_bytes(B, T, Lmax) bytes that the caller owns and keeps to
+    itself until the call has run (tools/bench_ctc_align.py reads the kernel's stamps from it); by default the call makes its own."""
+    for t in (lp, hlens, ys, ylens):
+        if not t.is_cuda:
+            raise _lib.PafcError("this op runs on the MI355X only (tensor is on %s); there is no CPU fallback" % t.device)
+    if lp.dim() != 3 or ys.dim() != 2 or ys.shape[0] != lp.shape[0] or hlens.numel() != lp.shape[0] or ylens.numel() != lp.shape[0]:
+        raise _lib.PafcError("ctc_align wants lp (B, T, V), hlens (B), ys (B, Lmax), ylens (B)")
+    B, T, V = lp.shape
+    if lp.stride(2) != 1 or lp.stride(1) < V or lp.stride(0) != T * lp.stride(1):
+        lp = lp.contiguous()
+    L = _lib.lib()
+    dev, Lmax = lp.device, ys.shape[1]
+    h32, y64, l32 = hlens.to(torch.int32).contiguous(), ys.to(torch.int64).contiguous(), ylens.to(torch.int32).contiguous()
+    align = torch.empty(B, T, dtype=torch.int32, device=dev)
+    first = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
+    last = torch.empty(B, Lmax, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    ok = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0 or T == 0:
+        return align, first, last, score, ok
+    nws = L.pafc_ctc_align_workspace_bytes(B, T, Lmax)
+    # the workspace is the call's own: the caching allocator hands a block of this size back to the next call on the stream,
+    # and inside a capture the block belongs to the graph's pool, so a replay never writes into memory another tensor owns
+    if workspace is None:
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    else:
+        ws = workspace
+        if not ws.is_cuda or ws.device != dev or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nws:
+            raise _lib.PafcError("ctc_align: workspace must be a contiguous uint8 tensor of >= %d bytes on %s" % (nws, dev))
+    _lib.check(L.pafc_ctc_align(_lib.dtype_code(lp.dtype), B, T, V, _lib.ptr(lp), lp.stride(1), _lib.ptr(h32), _lib.ptr(y64), Lmax,
+                                _lib.ptr(l32), int(blank_id), _lib.ptr(ws), nws, _lib.ptr(align), _lib.ptr(first), _lib.ptr(last),
+                                Lmax, _lib.ptr(score), _lib.ptr(ok), _lib.stream_of(lp)), "pafc_ctc_align")
+    return align, first, last, score, ok
+
+
 _ACTS = {"none": 0, "silu": 1, "tanh": 2, "relu": 3, "glu": 4}
 
 

@@ -72,6 +72,28 @@ class ASRModel(torch.nn.Module):
                 raise NotImplementedError(f"decode mode {m!r} is outside the accelerated path")
         return results
 
+    @torch.no_grad()
+    def align(self, speech: torch.Tensor, speech_lengths: torch.Tensor, text: torch.Tensor, text_lengths: torch.Tensor,
+              blank_id: int = 0, blank_penalty: float = 0.0, tokens_info: bool = False) -> List[DecodeResult]:
+        """Forced alignment of the transcripts text[b, :text_lengths[b]] to the audio (the reference's Model.align,
+        wenet/cli/model.py:92-104,148, for a batch): encoder -> CTC log-probabilities -> search.ctc_forced_align.  Each result
+        carries the tokens handed in, the path score and the first / last encoder frame of every token (times / end_times).
+        tokens_info: also (start, end) seconds per token from gen_timestamps_from_peak with the encoder's frame period
+        (subsampling rate x 0.01 s) and max_token_duration 1.0, as cli/model.py:113-118."""
+        from ..utils.ctc_utils import gen_timestamps_from_peak
+        from .search import ctc_forced_align
+        assert speech.shape[0] == speech_lengths.shape[0] == text.shape[0] == text_lengths.shape[0]
+        encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths)
+        encoder_lens = encoder_mask.squeeze(1).sum(1)
+        ctc_probs = self.ctc_logprobs(encoder_out, blank_penalty, blank_id)
+        results = ctc_forced_align(ctc_probs, encoder_lens, text, text_lengths, blank_id)
+        if tokens_info:
+            frame_rate = self.encoder.embed.subsampling_rate * 0.01
+            max_duration = encoder_out.size(1) * frame_rate
+            for r in results:
+                r.tokens_info = gen_timestamps_from_peak(r.times, max_duration, frame_rate, 1.0)
+        return results
+
     def _stream_windows(self, speech: torch.Tensor, decoding_chunk_size: int, who: str) -> Iterator[Tuple[int, torch.Tensor]]:
         """The window walk of a chunked stream, the contract of encoder.stream_chunks: the windows of forward_chunk_by_chunk
         through the encoder with carried state -- forward_chunk_carry for a causal conv module (or none),

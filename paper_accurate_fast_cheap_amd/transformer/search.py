@@ -12,7 +12,7 @@ from ..utils.mask import make_pad_mask
 class DecodeResult:
     def __init__(self, tokens: List[int], score: float = 0.0, confidence: float = 0.0, tokens_confidence=None,
                  times=None, nbest: Optional[List[List[int]]] = None, nbest_scores: Optional[List[float]] = None,
-                 nbest_times=None):
+                 nbest_times=None, end_times=None, tokens_info=None, ok: bool = True):
         self.tokens = tokens
         self.score = score
         self.confidence = confidence
@@ -21,6 +21,9 @@ class DecodeResult:
         self.nbest = nbest
         self.nbest_scores = nbest_scores
         self.nbest_times = nbest_times
+        self.end_times = end_times          # forced alignment: the last frame of every token (times: the first)
+        self.tokens_info = tokens_info      # forced alignment: (start, end) seconds per token
+        self.ok = ok                        # forced alignment: False when the labels cannot be aligned to the frames
 
 
 def log_add(args: List[float]) -> float:
@@ -239,6 +242,112 @@ def ctc_prefix_beam_search(ctc_probs: torch.Tensor, ctc_lens: torch.Tensor, beam
         _prefix_beam_resume(r, top_p[b], top_i[b], lens[b], beam_size, context_graph, blank_id)
         results.append(_prefix_beam_result(r, context_graph))
     return results
+
+
+def _forced_align_host(lp: torch.Tensor, y: List[int], blank_id: int):
+    """One utterance of ctc_forced_align on the host: lp (T, V) float32, the frames and labels without padding ->
+    (align, first, last, score, ok).  The recursion of include/pafc_search.h (pafc_ctc_align), a frame at a time over all
+    states at once: the same fp32 adds, candidates in the same order, a later one only when strictly greater."""
+    T, V = lp.shape
+    L = len(y)
+    bad = (-1.0 * float("inf"), False)
+    if T <= 0 or any(c == blank_id or c < 0 or c >= V for c in y):
+        return [-1] * T, [-1] * L, [-1] * L, *bad
+    if L + sum(1 for i in range(1, L) if y[i] == y[i - 1]) > T:
+        return [-1] * T, [-1] * L, [-1] * L, *bad
+    S = 2 * L + 1
+    ext = torch.full((S,), blank_id, dtype=torch.long)
+    ext[1::2] = torch.tensor(y, dtype=torch.long)
+    skip = torch.zeros(S, dtype=torch.bool)
+    skip[2:] = (ext[2:] != blank_id) & (ext[2:] != ext[:-2])
+    ninf = torch.full((2,), -float("inf"), dtype=torch.float32)
+    alpha = torch.full((S,), -float("inf"), dtype=torch.float32)
+    alpha[:2] = lp[0, ext[:2]]
+    back = torch.zeros(T, S, dtype=torch.int8)
+    for t in range(1, T):
+        padded = torch.cat([ninf, alpha])                       # two guard entries in front, as the kernel keeps them
+        a1 = padded[1:S + 1]
+        a2 = torch.where(skip, padded[:S], ninf[0])
+        m1 = a1 > alpha
+        best = torch.where(m1, a1, alpha)
+        m2 = a2 > best
+        best = torch.where(m2, a2, best)
+        back[t] = torch.where(m2, 2, m1.to(torch.int8))
+        alpha = best + lp[t, ext]
+    s = S - 1
+    if S >= 2 and bool(alpha[S - 2] > alpha[S - 1]):
+        s = S - 2
+    score = float(alpha[s])
+    if score == -float("inf"):
+        return [-1] * T, [-1] * L, [-1] * L, *bad
+    back = back.numpy()
+    ext_l = ext.tolist()
+    align, first, last = [0] * T, [-1] * L, [-1] * L
+    for t in range(T - 1, -1, -1):
+        align[t] = ext_l[s]
+        if s & 1:
+            first[s >> 1] = t
+            if last[s >> 1] < 0:
+                last[s >> 1] = t
+        s -= int(back[t, s])
+    return align, first, last, score, True
+
+
+def ctc_forced_align(ctc_probs: torch.Tensor, ctc_lens: torch.Tensor, ys: torch.Tensor, ys_lens: torch.Tensor, blank_id: int = 0,
+                     return_alignment: bool = False, defer: bool = False):
+    """CTC forced alignment of a batch (the reference aligns one utterance at a time on the host: force_align,
+    wenet/utils/ctc_utils.py:105-161, and builds this result in wenet/cli/model.py:92-104): the best path of the labels
+    ys[b, :ys_lens[b]] through ctc_probs[b, :ctc_lens[b]] (log-probabilities, float32 or bfloat16).  Each DecodeResult carries
+    tokens = the labels, score = the path's log-probability, times = the first frame of every token (gen_ctc_peak_time of the
+    alignment), end_times = the last, and nbest / nbest_scores / nbest_times holding that one entry.  Labels that cannot be
+    aligned (more labels plus adjacent repeats than frames, a blank or out-of-vocabulary label, no path of finite score,
+    ctc_lens[b] outside [1, T] or ys_lens[b] outside [0, Lmax]) give ok = False, score = -inf and times = []; tokens then holds
+    the labels with ys_lens[b] clamped to [0, Lmax].  Host and GPU paths follow the same rule.  State 0 of the lattice has itself as its only predecessor, which the reference
+    gets wrong (DESIGN.md "CTC forced alignment"); wherever the reference's path collapses to the labels this is its path.
+    return_alignment: -> (results, (B, T) int32 token of every frame, -1 beyond an utterance and in rows that are not ok).
+    GPU tensors run pafc_ctc_align (one launch; PafcError if it cannot, never a fallback); host tensors the recursion above.
+    defer (GPU only): return a zero-argument function that fetches the result; nothing waits for the device before it is called."""
+    B, T = ctc_probs.shape[:2]
+
+    def pack(ys_h, first_h, last_h, score_h, ok_h):
+        out = []
+        for b in range(B):
+            y = list(ys_h[b])
+            if ok_h[b]:
+                out.append(DecodeResult(tokens=y, score=score_h[b], times=first_h[b][:len(y)], nbest=[y], nbest_scores=[score_h[b]],
+                                        nbest_times=[first_h[b][:len(y)]], end_times=last_h[b][:len(y)]))
+            else:
+                out.append(DecodeResult(tokens=y, score=-float("inf"), times=[], nbest=[y], nbest_scores=[-float("inf")],
+                                        nbest_times=[[]], end_times=[], ok=False))
+        return out
+
+    if ctc_probs.is_cuda:
+        from ..hip_ops import ctc_align
+        dev = ctc_probs.device
+        ys_d, yl_d = ys.to(dev), ys_lens.to(dev)
+        align, first, last, score, ok = ctc_align(ctc_probs, ctc_lens.to(dev), ys_d, yl_d, blank_id)
+
+        def fetch():
+            yl = [max(0, min(int(n), ys_d.shape[1])) for n in yl_d.tolist()]
+            ys_h = [row[:n] for row, n in zip(ys_d.tolist(), yl)]
+            res = pack(ys_h, first.tolist(), last.tolist(), score.tolist(), ok.tolist())
+            return (res, align) if return_alignment else res
+        return fetch if defer else fetch()
+    lp = ctc_probs.float()
+    lens = [int(v) for v in ctc_lens.tolist()]
+    yl_raw = [int(n) for n in ys_lens.tolist()]
+    yl = [max(0, min(n, ys.shape[1])) for n in yl_raw]
+    ys_h = [row[:n] for row, n in zip(ys.tolist(), yl)]
+    align = torch.full((B, T), -1, dtype=torch.int32)
+    firsts, lasts, scores, oks = [], [], [], []
+    for b in range(B):
+        n = lens[b] if 0 <= lens[b] <= T and yl_raw[b] == yl[b] else 0       # a length outside its tensor: no frames, not ok
+        a, f, l, sc, ok = _forced_align_host(lp[b, :n], ys_h[b], blank_id)
+        if ok:
+            align[b, :n] = torch.tensor(a, dtype=torch.int32)
+        firsts.append(f); lasts.append(l); scores.append(sc); oks.append(ok)
+    res = pack(ys_h, firsts, lasts, scores, oks)
+    return (res, align) if return_alignment else res
 
 
 def _common_prefix_len(lists) -> int:
