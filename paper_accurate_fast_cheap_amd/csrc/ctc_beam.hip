@@ -84,11 +84,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const BeamParams p)
     if (lane < beam) {
         int32_t *ot = p.out_tokens + ((long)b * beam + lane) * p.T;
         if (lane < nb) {
-            int len = 0;
-            for (int n = c_node[lane]; n > 0; n = pparent[n]) ++len;
-            int pos = len;
-            for (int n = c_node[lane]; n > 0; n = pparent[n]) ot[--pos] = ptoken[n];
-            p.out_len[b * beam + lane] = len;
+            p.out_len[b * beam + lane] = trie_list_back(c_node[lane], pparent, ptoken, ot, p.T);
             if constexpr (CTX) p.out_score[b * beam + lane] = c_sc[lane] + (-p.g.node_score[c_ctx[lane]]);   // finalize
             else p.out_score[b * beam + lane] = c_sc[lane];
         } else {
@@ -98,12 +94,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_beam_kernel(const BeamParams p)
         if constexpr (TIMES) {
             int32_t *tt = p.out_times + ((long)b * beam + lane) * p.T;
             int len = 0;
-            if (lane < nb) {
-                const int h = c_vs[lane] > c_vns[lane] ? c_ts[lane] : c_tns[lane];
-                for (int n = h; n > 0; n = tprev[n]) ++len;
-                int pos = len;
-                for (int n = h; n > 0; n = tprev[n]) tt[--pos] = tframe[n];
-            }
+            if (lane < nb) len = trie_list_back(c_vs[lane] > c_vns[lane] ? c_ts[lane] : c_tns[lane], tprev, tframe, tt, p.T);
             for (int i = len; i < p.T; ++i) tt[i] = -1;
         }
     }
@@ -123,7 +114,7 @@ extern "C" int pafc_ctc_prefix_beam_search(int B, int T, int K, const float *top
                                            pafc_stream_t stream) {
     if (!top_logp || !top_idx || !out_tokens || !out_len || !out_score || !workspace) return PAFC_ERR_NULL_POINTER;
     if (B <= 0 || T <= 0 || K <= 0 || beam <= 0 || blank_id < 0) return PAFC_ERR_BAD_DIMS;
-    if (K > pafc::MAXB || beam > pafc::MAXB) return PAFC_ERR_UNSUPPORTED;
+    if (K > pafc::BEAM_MAX || beam > pafc::BEAM_MAX) return PAFC_ERR_UNSUPPORTED;
     if (workspace_bytes < pafc_ctc_prefix_beam_workspace_bytes(B, T, beam)) return PAFC_ERR_WORKSPACE;
     pafc::BeamParams p{};
     p.T = T; p.K = K; p.beam = beam; p.blank = blank_id;
@@ -146,12 +137,10 @@ extern "C" int pafc_ctc_prefix_beam_search_ex(int B, int T, int K, const float *
                                               double *out_score, int32_t *out_times, void *workspace,
                                               size_t workspace_bytes, pafc_stream_t stream) {
     if (!top_logp || !top_idx || !out_tokens || !out_len || !out_score || !workspace) return PAFC_ERR_NULL_POINTER;
-    if (graph && (!graph->child_begin || !graph->child_token || !graph->child_node || !graph->fail ||
-                  !graph->token_score || !graph->node_score || !graph->output_score))
-        return PAFC_ERR_NULL_POINTER;
+    if (graph && !pafc::graph_ok(graph)) return PAFC_ERR_NULL_POINTER;
     if (B <= 0 || T <= 0 || K <= 0 || beam <= 0 || blank_id < 0) return PAFC_ERR_BAD_DIMS;
     if (graph && graph->num_nodes < 1) return PAFC_ERR_BAD_DIMS;
-    if (K > pafc::MAXB || beam > pafc::MAXB) return PAFC_ERR_UNSUPPORTED;
+    if (K > pafc::BEAM_MAX || beam > pafc::BEAM_MAX) return PAFC_ERR_UNSUPPORTED;
     if (workspace_bytes < pafc_ctc_prefix_beam_ex_workspace_bytes(B, T, beam)) return PAFC_ERR_WORKSPACE;
     pafc::BeamParams p{};
     const size_t pool = (size_t)B * (1 + (size_t)T * beam);
@@ -162,12 +151,7 @@ extern "C" int pafc_ctc_prefix_beam_search_ex(int B, int T, int K, const float *
     p.time_frame = p.pool_token + pool;
     p.time_prev = p.time_frame + pool;
     p.out_tokens = out_tokens; p.out_len = out_len; p.out_score = out_score; p.out_times = out_times;
-    if (graph) {
-        p.g.num_nodes = graph->num_nodes;
-        p.g.child_begin = graph->child_begin; p.g.child_token = graph->child_token; p.g.child_node = graph->child_node;
-        p.g.fail = graph->fail;
-        p.g.token_score = graph->token_score; p.g.node_score = graph->node_score; p.g.output_score = graph->output_score;
-    }
+    p.g = pafc::to_graph(graph);
     const dim3 grid(B), block(64);
     hipStream_t s = (hipStream_t)stream;
     if (graph && out_times) hipLaunchKernelGGL((pafc::ctc_prefix_beam_kernel<true, true>), grid, block, 0, s, p);

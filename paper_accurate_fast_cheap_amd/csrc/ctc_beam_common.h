@@ -1,30 +1,38 @@
 // What the offline CTC prefix beam search (ctc_beam.hip) and the streaming one (ctc_beam_stream.hip) share outside the
-// kernel body: limits, the float64 log-add and the context graph walk.  The per-frame body itself is ctc_beam_frame.inc,
-// its LDS arrays ctc_beam_lds.inc; both kernels include the same text, so their arithmetic cannot drift apart.
+// kernel body, beyond beam_trie.h: the slot count and the context graph with its walk.  The per-frame body itself is
+// ctc_beam_frame.inc, its LDS arrays ctc_beam_lds.inc; both kernels include the same text, so their arithmetic cannot
+// drift apart.
 #ifndef PAFC_CTC_BEAM_COMMON_H
 #define PAFC_CTC_BEAM_COMMON_H
 
-#include "pafc_common.h"
-#include "../../include/pafc_search.h"
+#include "beam_trie.h"
 
 namespace pafc {
 namespace {
 
-constexpr int MAXB = 16;                   // beam size and top-k limit
-constexpr int NSLOT = MAXB + MAXB * MAXB;  // S slots then E slots
-constexpr double NEG_INF = -__builtin_huge_val();
-
-__device__ __forceinline__ double log_add2(double a, double b) {
-    if (a == NEG_INF && b == NEG_INF) return NEG_INF;
-    const double m = a > b ? a : b;
-    return m + log(exp(a - m) + exp(b - m));
-}
+constexpr int NSLOT = BEAM_MAX + BEAM_MAX * BEAM_MAX;  // S slots then E slots
 
 struct Graph {
     int num_nodes;
     const int32_t *child_begin, *child_token, *child_node, *fail;
     const double *token_score, *node_score, *output_score;
 };
+
+// every table of a caller's context graph is there
+inline bool graph_ok(const pafc_ctc_context_graph *g) {
+    return g->child_begin && g->child_token && g->child_node && g->fail && g->token_score && g->node_score && g->output_score;
+}
+
+// the kernels' copy of a caller's context graph; no graph: all zero
+inline Graph to_graph(const pafc_ctc_context_graph *g) {
+    Graph r{};
+    if (g) {
+        r.num_nodes = g->num_nodes;
+        r.child_begin = g->child_begin; r.child_token = g->child_token; r.child_node = g->child_node; r.fail = g->fail;
+        r.token_score = g->token_score; r.node_score = g->node_score; r.output_score = g->output_score;
+    }
+    return r;
+}
 
 // the child of `node` for token `tok`, or -1 (children sorted by token)
 __device__ __forceinline__ int ctx_child(const Graph &g, int node, int tok) {

@@ -78,12 +78,12 @@
             s_vs[m] = vs; s_vns[m] = vns; s_ts[m] = ts; s_top[m] = top; s_tbase[m] = tbase;
         }
         if constexpr (CTX) { s_ctx[m] = c_ctx[m]; s_cs[m] = c_cs[m]; }
-    } else if (lane < MAXB) {
+    } else if (lane < BEAM_MAX) {
         s_order[lane] = UNTOUCHED;
     }
     // ---- E slots: (member m, token rank r) -> a new prefix, unless it already is a member ---------------
-    for (int e = lane; e < MAXB * MAXB; e += 64) {
-        const int m = e / MAXB, r = e % MAXB;
+    for (int e = lane; e < BEAM_MAX * BEAM_MAX; e += 64) {
+        const int m = e / BEAM_MAX, r = e % BEAM_MAX;
         int order = UNTOUCHED;
         double ns = NEG_INF;
         double vns = NEG_INF, cs = 0.0;
@@ -104,7 +104,7 @@
                 if constexpr (CTX) { int nx; const double sc = ctx_step(p.g, c_ctx[m], tok[r], nx); cn = nx; cs = c_cs[m] + sc; }
             }
         }
-        const int si = MAXB + e;
+        const int si = BEAM_MAX + e;
         if constexpr (TIMES) { s_vs[si] = NEG_INF; s_vns[si] = vns; s_ts[si] = 0; s_top[si] = top; s_tbase[si] = tbase; }
         if constexpr (CTX) { s_ctx[si] = cn; s_cs[si] = cs; }
         s_s[si] = NEG_INF; s_ns[si] = ns; s_order[si] = order; s_node[si] = -1;
@@ -150,7 +150,7 @@
                 n_vs[rank] = s_vs[i]; n_vns[rank] = s_vns[i]; n_ts[rank] = s_ts[i]; n_tns[rank] = tns;
             }
             if constexpr (CTX) { n_ctx[rank] = s_ctx[i]; n_cs[rank] = s_cs[i]; }
-            if constexpr (STREAM) n_len[rank] = i < MAXB ? c_len[i] : c_len[(i - MAXB) / MAXB] + 1;   // an E slot is a new prefix
+            if constexpr (STREAM) n_len[rank] = i < BEAM_MAX ? c_len[i] : c_len[(i - BEAM_MAX) / BEAM_MAX] + 1;   // an E slot is a new prefix
         }
     }
     __syncthreads();

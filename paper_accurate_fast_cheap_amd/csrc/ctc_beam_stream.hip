@@ -12,13 +12,9 @@
 // the empty prefix / the empty list.  A feed that would take a row past max_total_frames consumes nothing and raises
 // the row's overflow flag (kept until the row is reset), so no index beyond the pool is ever formed.
 //
-// drain reads the state and writes the n-best lists as if the stream ended here: the finalize bonus goes to the
-// returned score only.  committed = the length of the longest common prefix of the members' token lists.  Every
-// hypothesis of a later frame extends a member, so those tokens never change again.  The same prefix can own two trie
-// nodes (it left the beam and was formed again), so the walk compares tokens, not node ids, and it stops at `from`, the
-// count the caller already holds: all members agree below it.  Token copies stop at `from` too, which needs each
-// member's token count; the feed carries it (c_len).  Work and bytes per drain follow the uncommitted tail, not the
-// length of the stream.
+// drain reads the state and writes the n-best lists as if the stream ended here: trie_drain (beam_trie.h), which says
+// what `committed` and `from` mean; the finalize bonus goes to the returned score only.  It needs each member's token
+// count; the feed carries it (c_len).
 #include "ctc_beam_common.h"
 
 namespace pafc {
@@ -29,8 +25,8 @@ constexpr int32_t STATE_MAGIC = 0x43544253;      // a row that was reset
 struct RowState {
     int64_t base;                                 // frames consumed since the reset
     int32_t nb, overflow, magic, beam;
-    double s[MAXB], ns[MAXB], sc[MAXB], vs[MAXB], vns[MAXB], cs[MAXB];
-    int32_t node[MAXB], last[MAXB], parent[MAXB], ts[MAXB], tns[MAXB], ctx[MAXB], len[MAXB];
+    double s[BEAM_MAX], ns[BEAM_MAX], sc[BEAM_MAX], vs[BEAM_MAX], vns[BEAM_MAX], cs[BEAM_MAX];
+    int32_t node[BEAM_MAX], last[BEAM_MAX], parent[BEAM_MAX], ts[BEAM_MAX], tns[BEAM_MAX], ctx[BEAM_MAX], len[BEAM_MAX];
 };
 
 struct Layout {
@@ -76,8 +72,7 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_feed_kernel(const StreamPa
 
     const int b = blockIdx.x, lane = threadIdx.x;
     RowState &r = p.state[b];
-    const int64_t nf = p.nframes[b];
-    const int n = (int)(nf < 0 ? 0 : (nf > p.T ? p.T : nf));
+    const int n = clamp_frames(p.nframes[b], p.T);
     if (n == 0) return;                                           // the row sits this feed out
     const int K = p.K, beam = p.beam;
     const int64_t base = r.base;
@@ -136,45 +131,18 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_drain_kernel(const DrainPa
     const long pool_stride = 1 + (long)p.max_total * beam;
     const int32_t *pparent = p.pool_parent + b * pool_stride, *ptoken = p.pool_token + b * pool_stride;
     const bool active = lane < nb;
-    const int node = active ? r.node[lane] : 0, len = active ? r.len[lane] : 0x7fffffff;
+    const long o = (long)b * beam + lane;
+    const int node = active ? r.node[lane] : 0, len = active ? r.len[lane] : 0;
 
-    int dmin = len;                                               // the shortest member
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dmin = min(dmin, __shfl_xor(dmin, off, 64));
-    if (nb == 0) dmin = 0;
-    int from = p.from ? p.from[b] : 0;
-    from = min(max(from, 0), dmin);
-
-    // ---- committed: the longest common prefix of the members' token lists, looked for in [from, dmin] -------------
-    int n = node, d = active ? len : dmin;
-    while (d > dmin) { n = pparent[n]; --d; }                     // every member at depth dmin
-    int committed = dmin;
-    while (d > from) {                                            // (d is wave-uniform from here on)
-        const int n0 = __shfl(n, 0, 64);
-        if (__all(!active || n == n0)) break;                     // one node: the lists agree below d
-        const int tk = active ? ptoken[n] : -1;
-        const int tk0 = __shfl(tk, 0, 64);
-        if (!__all(!active || tk == tk0)) committed = d - 1;      // position d - 1 differs
-        if (active) n = pparent[n];
-        --d;
-    }
+    const int committed = trie_drain(active, node, len, nb, pparent, ptoken, p.from ? p.from[b] : 0, p.ld,
+                                     active ? p.out_tokens + o * p.ld : nullptr);
     if (lane == 0) {
         p.out_count[b] = nb;
         p.out_committed[b] = committed;
         p.out_overflow[b] = valid ? r.overflow : 2;
     }
-
-    // ---- per member: total token count, score, tokens [from, from + ld) --------------------------------------------
-    if (lane < beam) {
-        const long o = (long)b * beam + lane;
+    if (lane < beam) {                                            // per member: total token count, score, frame list
         if (active) {
-            int32_t *ot = p.out_tokens + o * p.ld;
-            int m = node;
-            for (int dd = len; dd > from; --dd) {
-                const int pos = dd - 1 - from;
-                if (pos < p.ld) ot[pos] = ptoken[m];
-                m = pparent[m];
-            }
             p.out_len[o] = len;
             p.out_score[o] = p.node_score ? r.sc[lane] + (-p.node_score[r.ctx[lane]]) : r.sc[lane];     // finalize, on a copy
         } else {
@@ -183,31 +151,19 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_drain_kernel(const DrainPa
         }
         if (p.out_ntimes) {
             int cnt = 0;
-            if (active) {
-                const int32_t *tframe = p.time_frame + b * pool_stride, *tprev = p.time_prev + b * pool_stride;
-                const int h = r.vs[lane] > r.vns[lane] ? r.ts[lane] : r.tns[lane];
-                for (int m = h; m > 0; m = tprev[m]) ++cnt;
-                int pos = cnt;
-                for (int m = h; m > 0; m = tprev[m]) {
-                    --pos;
-                    if (pos < p.ld_times) p.out_times[o * p.ld_times + pos] = tframe[m];
-                }
-            }
+            if (active)
+                cnt = trie_list_back(r.vs[lane] > r.vns[lane] ? r.ts[lane] : r.tns[lane], p.time_prev + b * pool_stride,
+                                     p.time_frame + b * pool_stride, p.out_times + o * p.ld_times, p.ld_times);
             p.out_ntimes[o] = cnt;
         }
     }
-}
-
-bool graph_ok(const pafc_ctc_context_graph *g) {
-    return g->child_begin && g->child_token && g->child_node && g->fail && g->token_score && g->node_score && g->output_score;
 }
 
 }  // namespace
 }  // namespace pafc
 
 extern "C" size_t pafc_ctc_beam_stream_workspace_bytes(int B, int max_total_frames, int beam, int with_times) {
-    if (B <= 0 || max_total_frames <= 0 || beam <= 0 || beam > pafc::MAXB) return 0;
-    if ((long)max_total_frames * beam >= 0x7fffffffL) return 0;
+    if (pafc::beam_dims_check(B, max_total_frames, beam)) return 0;
     return pafc::layout(B, max_total_frames, beam, with_times).total;
 }
 
@@ -220,18 +176,12 @@ void pools(void *workspace, const pafc::Layout &l, int B, int with_times, int32_
     frame = with_times ? token + (size_t)B * l.pool : nullptr;
     prev = with_times ? frame + (size_t)B * l.pool : nullptr;
 }
-
-int check_dims(int B, int max_total_frames, int beam) {
-    if (B <= 0 || max_total_frames <= 0 || beam <= 0) return PAFC_ERR_BAD_DIMS;
-    if (beam > pafc::MAXB || (long)max_total_frames * beam >= 0x7fffffffL) return PAFC_ERR_UNSUPPORTED;
-    return PAFC_OK;
-}
 }  // namespace
 
 extern "C" int pafc_ctc_beam_stream_reset(int B, int max_total_frames, int beam, int with_times, const int32_t *row_mask,
                                           void *workspace, size_t workspace_bytes, pafc_stream_t stream) {
     if (!workspace) return PAFC_ERR_NULL_POINTER;
-    if (const int e = check_dims(B, max_total_frames, beam)) return e;
+    if (const int e = pafc::beam_dims_check(B, max_total_frames, beam)) return e;
     const pafc::Layout l = pafc::layout(B, max_total_frames, beam, with_times);
     if (workspace_bytes < l.total) return PAFC_ERR_WORKSPACE;
     int32_t *parent, *token, *frame, *prev;
@@ -250,8 +200,8 @@ extern "C" int pafc_ctc_beam_stream_feed(int B, int Tmax, int K, const float *to
     if (Tmax <= 0 || K <= 0 || blank_id < 0) return PAFC_ERR_BAD_DIMS;
     if (B <= 0 || max_total_frames <= 0 || beam <= 0) return PAFC_ERR_BAD_DIMS;
     if (graph && graph->num_nodes < 1) return PAFC_ERR_BAD_DIMS;
-    if (K > pafc::MAXB) return PAFC_ERR_UNSUPPORTED;
-    if (const int e = check_dims(B, max_total_frames, beam)) return e;
+    if (K > pafc::BEAM_MAX) return PAFC_ERR_UNSUPPORTED;
+    if (const int e = pafc::beam_dims_check(B, max_total_frames, beam)) return e;
     const pafc::Layout l = pafc::layout(B, max_total_frames, beam, with_times);
     if (workspace_bytes < l.total) return PAFC_ERR_WORKSPACE;
     pafc::StreamParams p{};
@@ -259,12 +209,7 @@ extern "C" int pafc_ctc_beam_stream_feed(int B, int Tmax, int K, const float *to
     p.top_logp = top_logp; p.top_idx = top_idx; p.nframes = nframes;
     p.state = (pafc::RowState *)workspace;
     pools(workspace, l, B, with_times, p.pool_parent, p.pool_token, p.time_frame, p.time_prev);
-    if (graph) {
-        p.g.num_nodes = graph->num_nodes;
-        p.g.child_begin = graph->child_begin; p.g.child_token = graph->child_token; p.g.child_node = graph->child_node;
-        p.g.fail = graph->fail;
-        p.g.token_score = graph->token_score; p.g.node_score = graph->node_score; p.g.output_score = graph->output_score;
-    }
+    p.g = pafc::to_graph(graph);
     const dim3 grid(B), block(64);
     hipStream_t s = (hipStream_t)stream;
     if (graph && with_times) hipLaunchKernelGGL((pafc::ctc_beam_stream_feed_kernel<true, true>), grid, block, 0, s, p);
@@ -285,7 +230,7 @@ extern "C" int pafc_ctc_beam_stream_drain(int B, int max_total_frames, int beam,
     if (graph && !pafc::graph_ok(graph)) return PAFC_ERR_NULL_POINTER;
     if (ld < 0 || ld_times < 0) return PAFC_ERR_BAD_DIMS;
     if (graph && graph->num_nodes < 1) return PAFC_ERR_BAD_DIMS;
-    if (const int e = check_dims(B, max_total_frames, beam)) return e;
+    if (const int e = pafc::beam_dims_check(B, max_total_frames, beam)) return e;
     if (out_ntimes && !with_times) return PAFC_ERR_UNSUPPORTED;           // the workspace holds no frame lists
     const pafc::Layout l = pafc::layout(B, max_total_frames, beam, with_times);
     if (workspace_bytes < l.total) return PAFC_ERR_WORKSPACE;

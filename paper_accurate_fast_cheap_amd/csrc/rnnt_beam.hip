@@ -23,7 +23,7 @@ __global__ void rnnt_beam_init_kernel(void *ws, int B, int T, int beam, int blan
     if (i >= B * beam) return;
     const int b = i / beam, m = i % beam;
     s.node[i] = 0; s.parent[i] = -1; s.last[i] = blank;
-    s.score[i] = m == 0 ? 0.0 : RNEG_INF;
+    s.score[i] = m == 0 ? 0.0 : NEG_INF;
     next_idx[i] = i;
     last_tok[i] = blank;
     if (m == 0) {
@@ -59,15 +59,11 @@ __global__ __launch_bounds__(64) void rnnt_beam_finish_kernel(void *ws, int B, i
     const int32_t *pp = s.pool_parent + b * pstride, *pt = s.pool_token + b * pstride;
     int32_t *ot = out_tokens + ((size_t)b * beam + lane) * T;
     if (lane < s.nb[b]) {
-        int len = 0;
-        for (int n = s.node[b * beam + lane]; n > 0; n = pp[n]) ++len;
-        int pos = len;
-        for (int n = s.node[b * beam + lane]; n > 0; n = pp[n]) ot[--pos] = pt[n];
-        out_len[b * beam + lane] = len;
+        out_len[b * beam + lane] = trie_list_back(s.node[b * beam + lane], pp, pt, ot, T);
         out_score[b * beam + lane] = s.score[b * beam + lane];
     } else {
         out_len[b * beam + lane] = -1;
-        out_score[b * beam + lane] = RNEG_INF;
+        out_score[b * beam + lane] = NEG_INF;
     }
 }
 
@@ -81,8 +77,7 @@ extern "C" size_t pafc_rnnt_beam_workspace_bytes(int B, int T, int beam) {
 
 static int rnnt_check(int B, int T, int beam, const void *ws, size_t ws_bytes) {
     if (!ws) return PAFC_ERR_NULL_POINTER;
-    if (B <= 0 || T <= 0 || beam <= 0) return PAFC_ERR_BAD_DIMS;
-    if (beam > pafc::RB) return PAFC_ERR_UNSUPPORTED;
+    if (const int rc = pafc::beam_dims_check(B, T, beam)) return rc;
     if (ws_bytes < pafc_rnnt_beam_workspace_bytes(B, T, beam)) return PAFC_ERR_WORKSPACE;
     return PAFC_OK;
 }

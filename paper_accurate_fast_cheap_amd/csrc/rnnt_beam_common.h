@@ -1,23 +1,13 @@
 // What the offline CTC-fused RNN-T prefix beam search (rnnt_beam.hip) and the streaming one (rnnt_beam_stream.hip) share
-// outside the kernel body: the beam limit, the float64 log-add and the layout of the beam state.  The per-frame candidate
-// walk itself is rnnt_beam_frame.inc; both step kernels include the same text, so their arithmetic cannot drift apart.
+// outside the kernel body, beyond beam_trie.h: the layout of the beam state.  The per-frame candidate walk itself is
+// rnnt_beam_frame.inc; both step kernels include the same text, so their arithmetic cannot drift apart.
 #ifndef PAFC_RNNT_BEAM_COMMON_H
 #define PAFC_RNNT_BEAM_COMMON_H
 
-#include "pafc_common.h"
-#include "../../include/pafc_search.h"
+#include "beam_trie.h"
 
 namespace pafc {
 namespace {
-
-constexpr int RB = 16;                      // beam limit
-constexpr double RNEG_INF = -__builtin_huge_val();
-
-__device__ __forceinline__ double rlog_add2(double a, double b) {
-    if (a == RNEG_INF && b == RNEG_INF) return RNEG_INF;
-    const double m = a > b ? a : b;
-    return m + log(exp(a - m) + exp(b - m));
-}
 
 struct RnntState {
     int32_t *nb;                                   // (B) live beams

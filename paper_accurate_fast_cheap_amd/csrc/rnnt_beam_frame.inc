@@ -6,13 +6,14 @@
 // equal values in flat order; walked best first, equal hypotheses merged with log_add, stopped at `beam` distinct ones;
 // the collected ones sorted stably by score; written back by rank.  Leaves in LDS for the includer: m_* (the beam before
 // the frame), a_src / a_new / a_rank per collected hypothesis and cnt, their number.
-    __shared__ float c_val[RB * RB];
-    __shared__ int c_tok[RB * RB], c_order[RB * RB];
-    __shared__ int m_node[RB], m_parent[RB], m_last[RB];
-    __shared__ double m_score[RB];
+    __shared__ float c_val[BEAM_MAX * BEAM_MAX];
+    __shared__ int c_tok[BEAM_MAX * BEAM_MAX], c_order[BEAM_MAX * BEAM_MAX];
+    __shared__ int m_node[BEAM_MAX], m_parent[BEAM_MAX], m_last[BEAM_MAX];
+    __shared__ double m_score[BEAM_MAX];
     // collected hypotheses (beam_A of the reference), in first-seen order
-    __shared__ double a_score[RB];
-    __shared__ int a_node[RB], a_parent[RB], a_tok[RB], a_last[RB], a_src[RB], a_new[RB], a_rank[RB];
+    __shared__ double a_score[BEAM_MAX];
+    __shared__ int a_node[BEAM_MAX], a_parent[BEAM_MAX], a_tok[BEAM_MAX], a_last[BEAM_MAX];
+    __shared__ int a_src[BEAM_MAX], a_new[BEAM_MAX], a_rank[BEAM_MAX];
     __shared__ int a_count;
 
     const int nbm = s.nb[b];
@@ -55,7 +56,7 @@
                 if (same) { hit = e; break; }
             }
             if (hit >= 0) {
-                a_score[hit] = rlog_add2(a_score[hit], v);
+                a_score[hit] = log_add2(a_score[hit], v);
             } else {
                 a_score[cnt] = v; a_node[cnt] = node; a_parent[cnt] = par; a_tok[cnt] = tok; a_last[cnt] = lastt;
                 a_src[cnt] = m; a_new[cnt] = tk != blank;
@@ -88,7 +89,7 @@
         next_idx[base + p] = (int64_t)(base + a_src[lane]) + (a_new[lane] ? (int64_t)B * beam : 0);
         last_tok[base + p] = a_last[lane];
     } else if (lane < beam) {                       // unused slot: inert
-        s.score[base + lane] = RNEG_INF; s.node[base + lane] = 0; s.parent[base + lane] = -1; s.last[base + lane] = blank;
+        s.score[base + lane] = NEG_INF; s.node[base + lane] = 0; s.parent[base + lane] = -1; s.last[base + lane] = blank;
         next_idx[base + lane] = base + lane;
         last_tok[base + lane] = blank;
     }

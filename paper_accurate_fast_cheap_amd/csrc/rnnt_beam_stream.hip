@@ -11,12 +11,8 @@
 // take a row past max_total_frames takes nothing and raises the row's flag (kept until the reset), so no index beyond the
 // pool is ever formed.
 //
-// drain reads the state and writes the n-best lists as if the stream ended here.  committed = the length of the longest
-// common prefix of the live members' token lists: every hypothesis of a later frame is a member or a member plus one
-// token, so those tokens never change again.  The same token list can own two trie nodes (it left the beam and was formed
-// again), so the walk compares tokens, not node ids, and it stops at `from`, the count the caller already holds.  The
-// token copies stop at `from` too, which needs each member's token count; the step carries it.  Work and bytes per drain
-// follow the uncommitted tail, not the length of the stream.
+// drain reads the state and writes the n-best lists as if the stream ended here: trie_drain (beam_trie.h), which says what
+// `committed` and `from` mean.  It needs each member's token count; the step carries it.
 #include "rnnt_beam_common.h"
 
 namespace pafc {
@@ -57,7 +53,7 @@ __global__ void rnnt_beam_stream_reset_kernel(void *ws, int B, int T, int beam, 
     const int b = i / beam, m = i % beam;
     if (row_mask != nullptr && row_mask[b] == 0) return;
     s.node[i] = 0; s.parent[i] = -1; s.last[i] = blank;
-    s.score[i] = m == 0 ? 0.0 : RNEG_INF;
+    s.score[i] = m == 0 ? 0.0 : NEG_INF;
     x.len[i] = 0;
     next_idx[i] = i;
     last_tok[i] = blank;
@@ -73,8 +69,7 @@ __global__ void rnnt_beam_stream_feed_kernel(void *ws, int B, int Tmax, int T, i
     const RnntStreamRows x = carve_rows(ws, B, T, beam);
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int64_t nf = nframes[b];
-    const int n = (int)(nf < 0 ? 0 : (nf > Tmax ? Tmax : nf));
+    const int n = clamp_frames(nframes[b], Tmax);
     int take = n;
     if (x.magic[b] != RSTREAM_MAGIC) {                      // never reset: nothing of this row can be trusted
         x.overflow[b] = 2;
@@ -92,7 +87,7 @@ __global__ __launch_bounds__(64) void rnnt_beam_stream_step_kernel(void *ws, int
                                                                    int64_t *last_tok) {
     // the chunk frame comes from device memory when the frame body is replayed from a captured graph
     const int64_t j = j_dev != nullptr ? *j_dev : (int64_t)j_host;
-    __shared__ int m_len[RB];
+    __shared__ int m_len[BEAM_MAX];
 
     const RnntState s = carve(ws, B, T, beam);
     const RnntStreamRows x = carve_rows(ws, B, T, beam);
@@ -129,51 +124,19 @@ __global__ __launch_bounds__(64) void rnnt_beam_stream_drain_kernel(const RnntDr
     const size_t pstride = 1 + (size_t)p.T * beam;
     const int32_t *pparent = s.pool_parent + b * pstride, *ptoken = s.pool_token + b * pstride;
     const bool active = lane < nb;
-    const int node = active ? s.node[b * beam + lane] : 0, len = active ? x.len[b * beam + lane] : 0x7fffffff;
+    const long o = (long)b * beam + lane;
+    const int node = active ? s.node[o] : 0, len = active ? x.len[o] : 0;
 
-    int dmin = len;                                               // the shortest member
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dmin = min(dmin, __shfl_xor(dmin, off, 64));
-    if (nb == 0) dmin = 0;
-    int from = p.from ? p.from[b] : 0;
-    from = min(max(from, 0), dmin);
-
-    // ---- committed: the longest common prefix of the members' token lists, looked for in [from, dmin] -------------
-    int n = node, d = active ? len : dmin;
-    while (d > dmin) { n = pparent[n]; --d; }                     // every member at depth dmin
-    int committed = dmin;
-    while (d > from) {                                            // (d is wave-uniform from here on)
-        const int n0 = __shfl(n, 0, 64);
-        if (__all(!active || n == n0)) break;                     // one node: the lists agree below d
-        const int tk = active ? ptoken[n] : -1;
-        const int tk0 = __shfl(tk, 0, 64);
-        if (!__all(!active || tk == tk0)) committed = d - 1;      // position d - 1 differs
-        if (active) n = pparent[n];
-        --d;
-    }
+    const int committed = trie_drain(active, node, len, nb, pparent, ptoken, p.from ? p.from[b] : 0, p.ld,
+                                     active ? p.out_tokens + o * p.ld : nullptr);
     if (lane == 0) {
         p.out_count[b] = nb;
         p.out_committed[b] = committed;
         p.out_overflow[b] = valid ? x.overflow[b] : 2;
     }
-
-    // ---- per member: total token count, score, tokens [from, from + ld) --------------------------------------------
-    if (lane < beam) {
-        const long o = (long)b * beam + lane;
-        if (active) {
-            int32_t *ot = p.out_tokens + o * p.ld;
-            int m = node;
-            for (int dd = len; dd > from; --dd) {
-                const int pos = dd - 1 - from;
-                if (pos < p.ld) ot[pos] = ptoken[m];
-                m = pparent[m];
-            }
-            p.out_len[o] = len;
-            p.out_score[o] = s.score[o];
-        } else {
-            p.out_len[o] = -1;
-            p.out_score[o] = RNEG_INF;
-        }
+    if (lane < beam) {                                            // per member: total token count and score
+        p.out_len[o] = active ? len : -1;
+        p.out_score[o] = active ? s.score[o] : NEG_INF;
     }
 }
 
@@ -194,9 +157,9 @@ __global__ __launch_bounds__(256) void rnnt_beam_select_state_kernel(int L, int 
         const int which = it / per, rem = it - which * per, l = rem / rowv, col = rem - l * rowv;
         V *dst = which ? c : h;
         const V *fresh = which ? cn : hn;
-        V vals[RB];
+        V vals[BEAM_MAX];
 #pragma unroll
-        for (int i = 0; i < RB; ++i) {
+        for (int i = 0; i < BEAM_MAX; ++i) {
             if (i < beam) {
                 const long slot = (long)b * beam + i;
                 long v = next_idx[slot];
@@ -207,7 +170,7 @@ __global__ __launch_bounds__(256) void rnnt_beam_select_state_kernel(int L, int 
             }
         }
 #pragma unroll
-        for (int i = 0; i < RB; ++i)
+        for (int i = 0; i < BEAM_MAX; ++i)
             if (i < beam) dst[((long)l * n + (long)b * beam + i) * rowv + col] = vals[i];
     }
 }
@@ -224,8 +187,7 @@ void launch_select(int L, int B, int beam, long row_bytes, void *h, void *c, con
 
 int stream_check(int B, int T, int beam, const void *ws, size_t ws_bytes) {
     if (!ws) return PAFC_ERR_NULL_POINTER;
-    if (B <= 0 || T <= 0 || beam <= 0) return PAFC_ERR_BAD_DIMS;
-    if (beam > RB || (long)T * beam >= 0x7fffffffL) return PAFC_ERR_UNSUPPORTED;
+    if (const int rc = beam_dims_check(B, T, beam)) return rc;
     if (ws_bytes < stream_bytes(B, T, beam)) return PAFC_ERR_WORKSPACE;
     return PAFC_OK;
 }
@@ -234,8 +196,7 @@ int stream_check(int B, int T, int beam, const void *ws, size_t ws_bytes) {
 }  // namespace pafc
 
 extern "C" size_t pafc_rnnt_beam_stream_workspace_bytes(int B, int max_total_frames, int beam) {
-    if (B <= 0 || max_total_frames <= 0 || beam <= 0 || beam > pafc::RB) return 0;
-    if ((long)max_total_frames * beam >= 0x7fffffffL) return 0;
+    if (pafc::beam_dims_check(B, max_total_frames, beam)) return 0;
     return pafc::stream_bytes(B, max_total_frames, beam);
 }
 
@@ -293,7 +254,7 @@ extern "C" int pafc_rnnt_beam_select_state(int dtype, int num_layers, int B, int
     if (!h || !c || !h_new || !c_new || !next_idx) return PAFC_ERR_NULL_POINTER;
     if (dtype != PAFC_F32 && dtype != PAFC_BF16) return PAFC_ERR_DTYPE;
     if (num_layers <= 0 || B <= 0 || beam <= 0 || hidden <= 0) return PAFC_ERR_BAD_DIMS;
-    if (beam > pafc::RB) return PAFC_ERR_UNSUPPORTED;
+    if (beam > pafc::BEAM_MAX) return PAFC_ERR_UNSUPPORTED;
     const long row_bytes = (long)hidden * (dtype == PAFC_F32 ? 4 : 2);
     if ((long)num_layers * row_bytes >= 0x3fffffffL) return PAFC_ERR_UNSUPPORTED;
     // the widest vector that divides a row and every base address

@@ -1,6 +1,7 @@
 """torch-tensor front ends of the glue kernels in include/pafc_encoder_ops.h (GPU only, no fallback)."""
 import contextlib
 import ctypes
+import math
 import os
 import threading
 import weakref
@@ -1171,6 +1172,112 @@ def rnnt_joint_loss(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: tor
 RNNT_GREEDY_CHUNK = 32     # lockstep steps between two reads of the running-row count, after the first T steps
 
 
+class _Packed:
+    """Several result arrays in one uint8 device buffer, so that one copy brings them all to the host.  fields: (name, dtype,
+    shape) in the order they are laid out, those of 8-byte elements first, so every field is aligned to its element size."""
+
+    def __init__(self, fields, device):
+        self._at, off = {}, 0
+        for name, dtype, shape in sorted(fields, key=lambda f: f[1].itemsize != 8):
+            end = off + dtype.itemsize * math.prod(shape)
+            self._at[name] = (off, end, dtype, tuple(shape))
+            off = end
+        self.nbytes = off
+        self.buf = torch.empty(off, dtype=torch.uint8, device=device)
+        self._host = None
+
+    def offset(self, name: str) -> int:
+        return self._at[name][0]
+
+    def ptr(self, name: str):
+        a, b = self._at[name][:2]
+        return _lib.ptr(self.buf[a:b])
+
+    def read(self):
+        """The one copy to the host."""
+        self._host = self.buf.cpu()
+        return self
+
+    def host(self, name: str) -> torch.Tensor:
+        """The field as the last read() brought it, typed and shaped."""
+        a, b, dtype, shape = self._at[name]
+        return self._host[a:b].view(dtype).view(shape)
+
+
+class _RowStream:
+    """What the chunk-by-chunk searches of B rows share: the library, the workspace (_ws, _nbytes), the frame counts of the next
+    chunk (_nf), the row mask of a reset and, for the two beam searches, the drain."""
+
+    _pinned = False       # host frame counts and `from` offsets go up from pinned memory, without a synchronising call
+
+    def _device(self, device) -> torch.device:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.PafcError(f"{type(self).__name__} runs on the MI355X only (device {dev}); there is no CPU fallback")
+        return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+
+    def _init_rows(self, B: int, dev, fn: str, args, why: str = "unsupported dimensions"):
+        """The workspace of the size the library's `fn(*args)` gives, and the per-row device buffers."""
+        self.B, self.device, self._L = B, dev, _lib.lib()
+        self._nbytes = getattr(self._L, fn)(*args)
+        if self._nbytes == 0:
+            raise _lib.PafcError(f"{fn}: {why}")
+        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _up(self, dst: torch.Tensor, src: torch.Tensor):
+        if self._pinned and not src.is_cuda:
+            dst.copy_(src.pin_memory(), non_blocking=True)     # (the pinned block is not reused before the copy ran)
+        else:
+            dst.copy_(src)
+
+    def _row_mask(self, rows):
+        """The pointer a reset takes: null for all rows, else the device mask with the given rows set."""
+        if rows is None:
+            return None
+        m = torch.zeros(self.B, dtype=torch.int32)
+        m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
+        self._mask.copy_(m)
+        return _lib.ptr(self._mask)
+
+    def _set_nframes(self, nframes, n: int):
+        """The frame counts of a chunk of n frames into _nf: n for every row when None, else (B,) counts clamped to [0, n]."""
+        if nframes is None:
+            self._nf.fill_(n)
+            return
+        nf = torch.as_tensor(nframes, dtype=torch.int64)
+        if nf.shape != (self.B,):
+            raise _lib.PafcError(f"{type(self).__name__}.feed: nframes must be ({self.B},)")
+        self._up(self._nf, nf.clamp(0, n))
+
+    def _init_drain(self):
+        self._from = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self._from_h = [0] * self.B
+        self.last_read_bytes = 0
+
+    def _drain_nbest(self, call, counts, ld: int):
+        """The drain of a beam search: counts into the `from` buffer, call(out, ld) launches the drain kernel into the packed
+        buffer `out`: score (B, beam) f64 | len (B, beam) | count | committed | overflow (B) | tokens (B, beam, ld) i32; then
+        the one read and the dict of host lists."""
+        B, beam = self.B, self.beam
+        counts = [0] * B if counts is None else [int(c) for c in counts]
+        if counts != self._from_h:
+            self._up(self._from, torch.tensor(counts, dtype=torch.int32))
+            self._from_h = counts
+        ld = max(1, int(ld))
+        i32 = torch.int32
+        out = _Packed([("score", torch.float64, (B, beam)), ("len", i32, (B, beam)), ("count", i32, (B,)),
+                       ("committed", i32, (B,)), ("overflow", i32, (B,)), ("tokens", i32, (B, beam, ld))], self.device)
+        call(out, ld)
+        out.read()
+        self.last_read_bytes = out.nbytes
+        res = {k: out.host(k).tolist() for k in ("score", "len", "count", "committed", "overflow")}
+        lens, toks = res["len"], out.host("tokens").tolist()
+        res["tokens"] = [[toks[b][n][:max(0, min(ld, lens[b][n] - counts[b]))] for n in range(beam)] for b in range(B)]
+        return res
+
+
 class _GreedyNet(ctypes.Structure):
     """include/pafc_search.h: pafc_rnnt_greedy_net."""
     _PP = ctypes.POINTER(c_void_p)
@@ -1306,20 +1413,15 @@ def rnnt_greedy_search(predictor, joint, encoder_out: torch.Tensor, encoder_out_
             raise _lib.PafcError("rnnt_greedy_search: rows still running after T * (n_steps + 1) steps")
         todo = chunk
     ld = steps                                     # a row emits at most one token per step
-    out = torch.empty(B * 8 + B * 4 + 2 * B * ld * 4, dtype=torch.uint8, device=dev)
-    score = out[:B * 8].view(torch.float64)
-    ntok = out[B * 8:B * 12].view(torch.int32)
-    toks = out[B * 12:B * 12 + B * ld * 4].view(torch.int32)
-    frames = out[B * 12 + B * ld * 4:].view(torch.int32)
-    _lib.check(L.pafc_rnnt_greedy_finish(pnet, B, T, n_steps, _lib.ptr(ws), nbytes, ld, _lib.ptr(toks), _lib.ptr(frames),
-                                         _lib.ptr(ntok), _lib.ptr(score), None, st), "pafc_rnnt_greedy_finish")
-    h = out.cpu()                                  # the final read
+    out = _Packed([("score", torch.float64, (B,)), ("ntok", torch.int32, (B,)), ("tokens", torch.int32, (B, ld)),
+                   ("frames", torch.int32, (B, ld))], dev)
+    _lib.check(L.pafc_rnnt_greedy_finish(pnet, B, T, n_steps, _lib.ptr(ws), nbytes, ld, out.ptr("tokens"), out.ptr("frames"),
+                                         out.ptr("ntok"), out.ptr("score"), None, st), "pafc_rnnt_greedy_finish")
+    out.read()                                     # the final read
     del keep
-    n_h = h[B * 8:B * 12].view(torch.int32).tolist()
-    s_h = h[:B * 8].view(torch.float64).tolist()
-    t_h = h[B * 12:B * 12 + B * ld * 4].view(torch.int32).view(B, ld)
-    f_h = h[B * 12 + B * ld * 4:].view(torch.int32).view(B, ld)
-    return ([t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)], s_h)
+    n_h, t_h, f_h = out.host("ntok").tolist(), out.host("tokens"), out.host("frames")
+    return ([t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)],
+            out.host("score").tolist())
 
 
 def rnnt_greedy_stream_unmet(predictor, joint, B: int, Tmax: int, D: int, device, n_steps: int = 64) -> Optional[str]:
@@ -1334,7 +1436,7 @@ def rnnt_greedy_stream_unmet(predictor, joint, B: int, Tmax: int, D: int, device
     return rnnt_greedy_unmet(predictor, joint, like, n_steps)
 
 
-class RnntGreedyStream:
+class RnntGreedyStream(_RowStream):
     """Greedy search of B streams chunk by chunk on the lockstep kernels of csrc/rnnt_greedy.hip (include/pafc_search.h:
     pafc_rnnt_greedy_stream_*), the decoder state carried from one chunk to the next.  The object owns the workspace, a fixed
     (B, Tmax, D) input buffer, the fixed (B, Tmax, J) E = enc_ffn buffer (gemm_f32 / gemm_bf16 into it) and the weights'
@@ -1359,24 +1461,18 @@ class RnntGreedyStream:
         unmet = rnnt_greedy_stream_unmet(predictor, joint, B, Tmax, D or 0, dev, n_steps)
         if unmet is not None:
             raise _lib.PafcError(f"RnntGreedyStream: {unmet}")
-        self.B, self.Tmax, self.D, self.n_steps, self.blank, self.chunk = B, Tmax, D, n_steps, int(blank), chunk
-        self.device, self.use_graph = dev, use_graph
+        self.Tmax, self.D, self.n_steps, self.blank, self.chunk = Tmax, D, n_steps, int(blank), chunk
+        self.use_graph = use_graph
         self.dtype = joint.ffn_out.weight.dtype
         ef = joint.enc_ffn
         self._w = ef.weight.detach().contiguous()
         self._b = None if ef.bias is None else ef.bias.detach().contiguous()
         J = joint.ffn_out.in_features
-        self._L = _lib.lib()
         self._net, self._keep = _greedy_net(predictor, joint)
         self._pnet = ctypes.byref(self._net)
-        self._nbytes = self._L.pafc_rnnt_greedy_stream_workspace_bytes(self._pnet, B, Tmax, n_steps)
-        if self._nbytes == 0:
-            raise _lib.PafcError("pafc_rnnt_greedy_stream_workspace_bytes: unsupported dimensions")
-        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self._init_rows(B, dev, "pafc_rnnt_greedy_stream_workspace_bytes", (self._pnet, B, Tmax, n_steps))
         self._x = torch.zeros(B * Tmax, D, dtype=self.dtype, device=dev)
         self._E = torch.empty(B * Tmax, J, dtype=self.dtype, device=dev)
-        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
-        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
         self._running = torch.zeros(1, dtype=torch.int32, device=dev)
         self._graphs = {}
         self._last_n = None
@@ -1387,12 +1483,7 @@ class RnntGreedyStream:
     def reset(self, rows=None):
         """Restart the given rows (all when None): a fresh decode from their next chunk on; other rows are untouched."""
         st = _lib.stream_of(self._ws)
-        mask = None
-        if rows is not None:
-            m = torch.zeros(self.B, dtype=torch.int32)
-            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
-            self._mask.copy_(m)
-            mask = _lib.ptr(self._mask)
+        mask = self._row_mask(rows)
         for b in (range(self.B) if rows is None else rows):
             self._score[b] = 0.0
         _lib.check(self._L.pafc_rnnt_greedy_stream_reset(self._pnet, self.B, self.Tmax, self.n_steps, self.blank, mask,
@@ -1447,13 +1538,7 @@ class RnntGreedyStream:
             raise _lib.PafcError("RnntGreedyStream.feed: the chunk is not on the weights' GPU")
         if n:
             self._x.view(B, Tmax, self.D)[:, :n].copy_(encoder_chunk.detach())
-        if nframes is None:
-            self._nf.fill_(n)
-        else:
-            nf = torch.as_tensor(nframes, dtype=torch.int64)
-            if nf.shape != (B,):
-                raise _lib.PafcError(f"RnntGreedyStream.feed: nframes must be ({B},)")
-            self._nf.copy_(nf.clamp(0, n))
+        self._set_nframes(nframes, n)
         self._last_n = n
         self._run_fixed(n)
         st = _lib.stream_of(self._ws)
@@ -1467,20 +1552,14 @@ class RnntGreedyStream:
             steps += self.chunk
         self.last_steps = steps
         ld = max(1, steps)                             # a row emits at most one token per step
-        # one buffer, one read: score (B) f64 | frames (B, ld) i64 | ntok (B) i32 | tokens (B, ld) i32 -- 8-byte fields first
-        o1, o2, o3 = B * 8, B * 8 + B * ld * 8, B * 12 + B * ld * 8
-        out = torch.empty(o3 + B * ld * 4, dtype=torch.uint8, device=self.device)
+        out = _Packed([("score", torch.float64, (B,)), ("frames", torch.int64, (B, ld)), ("ntok", torch.int32, (B,)),
+                       ("tokens", torch.int32, (B, ld))], self.device)
         _lib.check(self._L.pafc_rnnt_greedy_stream_drain(self._pnet, B, Tmax, self.n_steps, _lib.ptr(self._ws), self._nbytes, ld,
-                                                          _lib.ptr(out[o3:].view(torch.int32)),
-                                                          _lib.ptr(out[o1:o2].view(torch.int64)),
-                                                          _lib.ptr(out[o2:o3].view(torch.int32)),
-                                                          _lib.ptr(out[:o1].view(torch.float64)), None, st),
-                   "pafc_rnnt_greedy_stream_drain")
-        h = out.cpu()                                  # the final read
-        self._score = h[:o1].view(torch.float64).tolist()
-        f_h = h[o1:o2].view(torch.int64).view(B, ld)
-        n_h = h[o2:o3].view(torch.int32).tolist()
-        t_h = h[o3:].view(torch.int32).view(B, ld)
+                                                          out.ptr("tokens"), out.ptr("frames"), out.ptr("ntok"),
+                                                          out.ptr("score"), None, st), "pafc_rnnt_greedy_stream_drain")
+        out.read()                                     # the final read
+        self._score = out.host("score").tolist()
+        f_h, n_h, t_h = out.host("frames"), out.host("ntok").tolist(), out.host("tokens")
         return [t_h[b, :n_h[b]].tolist() for b in range(B)], [f_h[b, :n_h[b]].tolist() for b in range(B)]
 
     @property
@@ -2530,7 +2609,7 @@ def ctc_prefix_beam(top_logp: torch.Tensor, top_idx: torch.Tensor, lens: Optiona
     return tokens, lengths, scores, times
 
 
-class CtcBeamStream:
+class CtcBeamStream(_RowStream):
     """CTC prefix beam search of B streams chunk by chunk (include/pafc_search.h: pafc_ctc_beam_stream_*,
     csrc/ctc_beam_stream.hip): the beam of every stream lives in the workspace between feeds, and the n-best lists over a
     stream equal ctc_prefix_beam on the concatenated frames bit for bit.  The object owns the workspace, the fixed
@@ -2543,44 +2622,28 @@ class CtcBeamStream:
 
     def __init__(self, B: int, Tmax: int, K: int, beam: int, device, blank_id: int = 0, graph_tables: Optional[dict] = None,
                  max_total_frames: int = 4096, want_times: bool = True):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.PafcError(f"CtcBeamStream runs on the MI355X only (device {dev}); there is no CPU fallback")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = self._device(device)
         if B < 1 or Tmax < 1 or max_total_frames < 1:
             raise _lib.PafcError(f"CtcBeamStream: B {B}, Tmax {Tmax}, max_total_frames {max_total_frames} must be >= 1")
         if not 1 <= beam <= 16 or not 1 <= K <= 16:
             raise _lib.PafcError(f"CtcBeamStream: beam {beam} and K {K} must be in 1 .. 16")
-        self.B, self.Tmax, self.K, self.beam, self.blank, self.device = B, Tmax, K, beam, int(blank_id), dev
+        self.Tmax, self.K, self.beam, self.blank = Tmax, K, beam, int(blank_id)
         self.max_total, self.times = int(max_total_frames), int(bool(want_times))
-        self._L = _lib.lib()
         self._tables = graph_tables
         self._graph = None if graph_tables is None else _ctx_graph(graph_tables, dev, "CtcBeamStream")
         self._pgraph = None if self._graph is None else ctypes.addressof(self._graph)
-        self._nbytes = self._L.pafc_ctc_beam_stream_workspace_bytes(B, self.max_total, beam, self.times)
-        if self._nbytes == 0:
-            raise _lib.PafcError("pafc_ctc_beam_stream_workspace_bytes: unsupported dimensions (max_total_frames * beam < 2^31)")
-        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self._init_rows(B, dev, "pafc_ctc_beam_stream_workspace_bytes", (B, self.max_total, beam, self.times),
+                        "unsupported dimensions (max_total_frames * beam < 2^31)")
+        self._init_drain()
         self._top_p = torch.zeros(B, Tmax, K, dtype=torch.float32, device=dev)
         self._top_i = torch.zeros(B, Tmax, K, dtype=torch.int32, device=dev)
-        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
-        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
-        self._from = torch.zeros(B, dtype=torch.int32, device=dev)
-        self._from_h = [0] * B
-        self.last_read_bytes = 0
         self.reset()
 
     def reset(self, rows=None):
         """Restart the given rows (all when None) from the empty prefix at frame 0; other rows are untouched."""
-        mask = None
-        if rows is not None:
-            m = torch.zeros(self.B, dtype=torch.int32)
-            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
-            self._mask.copy_(m)
-            mask = _lib.ptr(self._mask)
-        _lib.check(self._L.pafc_ctc_beam_stream_reset(self.B, self.max_total, self.beam, self.times, mask, _lib.ptr(self._ws),
-                                                       self._nbytes, _lib.stream_of(self._ws)), "pafc_ctc_beam_stream_reset")
+        _lib.check(self._L.pafc_ctc_beam_stream_reset(self.B, self.max_total, self.beam, self.times, self._row_mask(rows),
+                                                       _lib.ptr(self._ws), self._nbytes, _lib.stream_of(self._ws)),
+                   "pafc_ctc_beam_stream_reset")
 
     def launch_feed(self):
         """The feed kernel on the fixed buffers (top-k, frame counts): reads nothing from the host, allocates nothing."""
@@ -2602,13 +2665,7 @@ class CtcBeamStream:
         if n:
             self._top_p[:, :n].copy_(top_logp)
             self._top_i[:, :n].copy_(top_idx)
-        if nframes is None:
-            self._nf.fill_(n)
-        else:
-            nf = torch.as_tensor(nframes, dtype=torch.int64)
-            if nf.shape != (B,):
-                raise _lib.PafcError(f"CtcBeamStream.feed: nframes must be ({B},)")
-            self._nf.copy_(nf.clamp(0, n))
+        self._set_nframes(nframes, n)
 
     def feed(self, top_logp: torch.Tensor, top_idx: torch.Tensor, nframes=None):
         self.load(top_logp, top_idx, nframes)
@@ -2620,80 +2677,54 @@ class CtcBeamStream:
         overflow (B), len (B, beam: total token counts, -1 unused), score (B, beam), tokens (B, beam: the tokens from
         counts[b] on, at most ld of them) and, with want_times, times (B, beam: the whole frame list)."""
         B, beam = self.B, self.beam
-        counts = [0] * B if counts is None else [int(c) for c in counts]
-        if counts != self._from_h:
-            self._from.copy_(torch.tensor(counts, dtype=torch.int32))
-            self._from_h = counts
         if want_times and not self.times:
             raise _lib.PafcError("CtcBeamStream.drain: the stream was made with want_times=False")
-        ld = max(1, int(ld))
-        # one buffer, one read: score (B, beam) f64 | len (B, beam) | count | committed | overflow (B) | tokens (B, beam, ld) i32
-        nb = B * beam
-        o = [0, nb * 8]
-        for words in (nb, B, B, B, nb * ld):
-            o.append(o[-1] + 4 * words)
-        out = torch.empty(o[-1], dtype=torch.uint8, device=self.device)
         ntim = tim = None
-        if want_times:               # the frame lists' lengths first: they size the second call's copy
-            ntim = torch.empty(B, beam, dtype=torch.int32, device=self.device)
-            self._drain(out, o, ld, 0, None, ntim)
-            ldt = max(1, int(ntim.max()))
-            tim = torch.empty(B, beam, ldt, dtype=torch.int32, device=self.device)
-            self._drain(out, o, ld, ldt, tim, ntim)
-        else:
-            self._drain(out, o, ld, 0, None, None)
-        h = out.cpu()                                  # the read
-        self.last_read_bytes = o[-1]
-        i32 = lambda k, *shape: h[o[k]:o[k + 1]].view(torch.int32).view(*shape)
-        lens = i32(1, B, beam).tolist()
-        toks = i32(5, B, beam, ld).tolist()
-        res = {"score": h[:o[1]].view(torch.float64).view(B, beam).tolist(), "len": lens, "count": i32(2, B).tolist(),
-               "committed": i32(3, B).tolist(), "overflow": i32(4, B).tolist(),
-               "tokens": [[toks[b][n][:max(0, min(ld, lens[b][n] - counts[b]))] for n in range(beam)] for b in range(B)]}
+
+        def call(out, ld):
+            nonlocal ntim, tim
+            ldt = 0
+            if want_times:           # the frame lists' lengths first: they size the second call's copy
+                ntim = torch.empty(B, beam, dtype=torch.int32, device=self.device)
+                self._drain(out, ld, 0, None, ntim)
+                ldt = max(1, int(ntim.max()))
+                tim = torch.empty(B, beam, ldt, dtype=torch.int32, device=self.device)
+            self._drain(out, ld, ldt, tim, ntim)
+
+        res = self._drain_nbest(call, counts, ld)
         if want_times:
             nt_h, tm_h = ntim.tolist(), tim.tolist()
             res["times"] = [[tm_h[b][n][:nt_h[b][n]] for n in range(beam)] for b in range(B)]
         return res
 
-    def _drain(self, out, o, ld, ldt, tim, ntim):
-        p = lambda k: _lib.ptr(out[o[k]:o[k + 1]])
+    def _drain(self, out, ld, ldt, tim, ntim):
         _lib.check(self._L.pafc_ctc_beam_stream_drain(self.B, self.max_total, self.beam, self._pgraph, self.times,
-                                                       _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._from), ld, p(5), p(1),
-                                                       p(0), p(2), p(3), p(4), ldt, _lib.ptr(tim), _lib.ptr(ntim),
-                                                       _lib.stream_of(self._ws)), "pafc_ctc_beam_stream_drain")
+                                                       _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._from), ld,
+                                                       out.ptr("tokens"), out.ptr("len"), out.ptr("score"), out.ptr("count"),
+                                                       out.ptr("committed"), out.ptr("overflow"), ldt, _lib.ptr(tim),
+                                                       _lib.ptr(ntim), _lib.stream_of(self._ws)), "pafc_ctc_beam_stream_drain")
 
 
-class CtcGreedyStream:
+class CtcGreedyStream(_RowStream):
     """CTC greedy search of B streams chunk by chunk (pafc_ctc_greedy_stream, csrc/ctc_greedy.hip): the offline argmax
     kernel on the chunk and a collapse that carries the previous frame's argmax and the frame base per row, so the tokens
     and absolute frames over a stream equal ctc_greedy(want_frames=True) on the concatenated frames."""
 
     def __init__(self, B: int, Tmax: int, device, blank_id: int = 0):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.PafcError(f"CtcGreedyStream runs on the MI355X only (device {dev}); there is no CPU fallback")
+        dev = self._device(device)
         if B < 1 or Tmax < 1:
             raise _lib.PafcError(f"CtcGreedyStream: B {B} and Tmax {Tmax} must be >= 1")
-        self.B, self.Tmax, self.blank, self.device = B, Tmax, int(blank_id), dev
-        self._L = _lib.lib()
-        self._nbytes = self._L.pafc_ctc_greedy_stream_workspace_bytes(B)
-        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
+        self.Tmax, self.blank = Tmax, int(blank_id)
+        self._init_rows(B, dev, "pafc_ctc_greedy_stream_workspace_bytes", (B,))
         self._best = torch.empty(B, Tmax, dtype=torch.int32, device=dev)
-        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
-        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
-        # one buffer, one read: frames (B, Tmax) i64 | ntok (B) i32 | tokens (B, Tmax) i32
-        self._o = (B * Tmax * 8, B * Tmax * 8 + B * 4)
-        self._out = torch.empty(self._o[1] + B * Tmax * 4, dtype=torch.uint8, device=dev)
+        # (a feed of n frames uses rows of n: the chunk's own frame count is the row stride)
+        self._out = _Packed([("frames", torch.int64, (B * Tmax,)), ("ntok", torch.int32, (B,)),
+                             ("tokens", torch.int32, (B * Tmax,))], dev)
         self.reset()
 
     def reset(self, rows=None):
-        mask = None
-        if rows is not None:
-            m = torch.zeros(self.B, dtype=torch.int32)
-            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
-            self._mask.copy_(m)
-            mask = _lib.ptr(self._mask)
-        _lib.check(self._L.pafc_ctc_greedy_stream_reset(self.B, mask, _lib.ptr(self._ws), self._nbytes, _lib.stream_of(self._ws)),
+        _lib.check(self._L.pafc_ctc_greedy_stream_reset(self.B, self._row_mask(rows), _lib.ptr(self._ws), self._nbytes,
+                                                         _lib.stream_of(self._ws)),
                    "pafc_ctc_greedy_stream_reset")
 
     def feed(self, scores: torch.Tensor, nframes=None):
@@ -2707,23 +2738,15 @@ class CtcGreedyStream:
         if n == 0:
             return [[] for _ in range(B)], [[] for _ in range(B)]
         scores = scores.contiguous()
-        if nframes is None:
-            self._nf.fill_(n)
-        else:
-            nf = torch.as_tensor(nframes, dtype=torch.int64)
-            if nf.shape != (B,):
-                raise _lib.PafcError(f"CtcGreedyStream.feed: nframes must be ({B},)")
-            self._nf.copy_(nf.clamp(0, n))
-        o1, o2 = self._o
-        out = self._out                                    # rows of n: the chunk's own frame count is the row stride
+        self._set_nframes(nframes, n)
+        out = self._out
         _lib.check(self._L.pafc_ctc_greedy_stream(_lib.dtype_code(scores.dtype), B, n, V, _lib.ptr(scores), _lib.ptr(self._nf),
                                                    self.blank, _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._best),
-                                                   _lib.ptr(out[o2:]), _lib.ptr(out[o1:o2]), _lib.ptr(out[:o1]),
+                                                   out.ptr("tokens"), out.ptr("ntok"), out.ptr("frames"),
                                                    _lib.stream_of(scores)), "pafc_ctc_greedy_stream")
-        h = out.cpu()
-        cnt = h[o1:o2].view(torch.int32).tolist()
-        fr = h[:B * n * 8].view(torch.int64).view(B, n)
-        tk = h[o2:o2 + B * n * 4].view(torch.int32).view(B, n)
+        out.read()
+        cnt = out.host("ntok").tolist()
+        fr, tk = out.host("frames")[:B * n].view(B, n), out.host("tokens")[:B * n].view(B, n)
         return [tk[b, :cnt[b]].tolist() for b in range(B)], [fr[b, :cnt[b]].tolist() for b in range(B)]
 
 
@@ -2732,15 +2755,15 @@ class RnntBeamState:
 
     def __init__(self, B: int, T: int, beam: int, blank: int, device):
         L = _lib.lib()
-        self.L, self.B, self.T, self.beam, self.blank = L, B, T, beam, blank
-        self.nws = L.pafc_rnnt_beam_workspace_bytes(B, T, beam)
-        if self.nws == 0:
+        self._L, self.B, self.T, self.beam, self.blank = L, B, T, beam, blank
+        self._nbytes = L.pafc_rnnt_beam_workspace_bytes(B, T, beam)
+        if self._nbytes == 0:
             raise _lib.PafcError("rnnt beam search: B, T, beam must be positive")
-        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=device)
+        self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=device)
         self.next_idx = torch.empty(B * beam, dtype=torch.int64, device=device)
         self.last_tok = torch.empty(B * beam, dtype=torch.int64, device=device)
-        self.stream = _lib.stream_of(self.ws)
-        _lib.check(L.pafc_rnnt_beam_init(B, T, beam, blank, _lib.ptr(self.ws), self.nws, _lib.ptr(self.next_idx),
+        self.stream = _lib.stream_of(self._ws)
+        _lib.check(L.pafc_rnnt_beam_init(B, T, beam, blank, _lib.ptr(self._ws), self._nbytes, _lib.ptr(self.next_idx),
                                          _lib.ptr(self.last_tok), self.stream), "pafc_rnnt_beam_init")
 
     def step(self, t: int, lens64: Optional[torch.Tensor], top_val: torch.Tensor, top_idx: torch.Tensor,
@@ -2749,22 +2772,22 @@ class RnntBeamState:
         _lib.require_gpu(top_val, top_idx, lens64, t_dev)
         if top_val.dtype != torch.float32 or top_idx.dtype != torch.int64 or top_val.numel() != self.B * self.beam * self.beam:
             raise _lib.PafcError("rnnt beam step: top_val float32 / top_idx int64 of (B, beam, beam)")
-        _lib.check(self.L.pafc_rnnt_beam_step(self.B, self.T, self.beam, self.blank, int(t), _lib.ptr(t_dev),
-                                              _lib.ptr(lens64), _lib.ptr(top_val), _lib.ptr(top_idx), _lib.ptr(self.ws),
-                                              self.nws, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
+        _lib.check(self._L.pafc_rnnt_beam_step(self.B, self.T, self.beam, self.blank, int(t), _lib.ptr(t_dev),
+                                              _lib.ptr(lens64), _lib.ptr(top_val), _lib.ptr(top_idx), _lib.ptr(self._ws),
+                                              self._nbytes, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
                                               _lib.stream_of(top_val)), "pafc_rnnt_beam_step")
 
     def finish(self):
-        dev = self.ws.device
+        dev = self._ws.device
         tokens = torch.empty(self.B, self.beam, self.T, dtype=torch.int32, device=dev)
         lengths = torch.empty(self.B, self.beam, dtype=torch.int32, device=dev)
         scores = torch.empty(self.B, self.beam, dtype=torch.float64, device=dev)
-        _lib.check(self.L.pafc_rnnt_beam_finish(self.B, self.T, self.beam, _lib.ptr(self.ws), self.nws, _lib.ptr(tokens),
+        _lib.check(self._L.pafc_rnnt_beam_finish(self.B, self.T, self.beam, _lib.ptr(self._ws), self._nbytes, _lib.ptr(tokens),
                                                 _lib.ptr(lengths), _lib.ptr(scores), self.stream), "pafc_rnnt_beam_finish")
         return tokens, lengths, scores
 
 
-class RnntBeamStream:
+class RnntBeamStream(_RowStream):
     """Device-side beams of the CTC-fused RNN-T prefix beam search for B streams fed chunk by chunk (include/pafc_search.h:
     pafc_rnnt_beam_stream_*, csrc/rnnt_beam_stream.hip).  The object owns the workspace, `next_idx` / `last_tok` of the
     B x beam slots, the frame counts and the `from` offsets; the caller owns the frame body and the LSTM state.  Per chunk:
@@ -2773,44 +2796,30 @@ class RnntBeamStream:
     top_idx, every frame's next_idx / last_tok and the drained lists equal RnntBeamState's over the concatenated frames,
     bit for bit.  A row that would pass max_total_frames takes nothing and is reported by drain's `overflow`."""
 
+    _pinned = True
+
     def __init__(self, B: int, Tmax: int, beam: int, blank: int, device, max_total_frames: int = 4096):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise _lib.PafcError(f"RnntBeamStream runs on the MI355X only (device {dev}); there is no CPU fallback")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = self._device(device)
         if B < 1 or Tmax < 1 or max_total_frames < 1:
             raise _lib.PafcError(f"RnntBeamStream: B {B}, Tmax {Tmax}, max_total_frames {max_total_frames} must be >= 1")
         if not 1 <= beam <= 16:
             raise _lib.PafcError(f"RnntBeamStream: beam {beam} must be in 1 .. 16")
-        self.L = _lib.lib()
-        self.B, self.Tmax, self.beam, self.blank, self.device = B, Tmax, beam, int(blank), dev
+        self.Tmax, self.beam, self.blank = Tmax, beam, int(blank)
         self.max_total = int(max_total_frames)
-        self.nws = self.L.pafc_rnnt_beam_stream_workspace_bytes(B, self.max_total, beam)
-        if self.nws == 0:
-            raise _lib.PafcError("pafc_rnnt_beam_stream_workspace_bytes: unsupported dimensions (max_total_frames * beam < 2^31)")
-        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev)
+        self._init_rows(B, dev, "pafc_rnnt_beam_stream_workspace_bytes", (B, self.max_total, beam),
+                        "unsupported dimensions (max_total_frames * beam < 2^31)")
+        self._init_drain()
         self.next_idx = torch.empty(B * beam, dtype=torch.int64, device=dev)
         self.last_tok = torch.empty(B * beam, dtype=torch.int64, device=dev)
-        self._nf = torch.zeros(B, dtype=torch.int64, device=dev)
-        self._mask = torch.zeros(B, dtype=torch.int32, device=dev)
-        self._from = torch.zeros(B, dtype=torch.int32, device=dev)
-        self._from_h = [0] * B
-        self.last_read_bytes = 0
         self.reset()
 
     def reset(self, rows=None):
         """Restart the given rows (all when None): one live beam of score 0, the root node, last_tok = blank, the identity
         next_idx, no frames consumed, overflow flag cleared; other rows are untouched."""
-        mask = None
-        if rows is not None:
-            m = torch.zeros(self.B, dtype=torch.int32)
-            m[torch.as_tensor(list(rows), dtype=torch.long)] = 1
-            self._mask.copy_(m)
-            mask = _lib.ptr(self._mask)
-        _lib.check(self.L.pafc_rnnt_beam_stream_reset(self.B, self.max_total, self.beam, self.blank, mask, _lib.ptr(self.ws),
-                                                      self.nws, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
-                                                      _lib.stream_of(self.ws)), "pafc_rnnt_beam_stream_reset")
+        _lib.check(self._L.pafc_rnnt_beam_stream_reset(self.B, self.max_total, self.beam, self.blank, self._row_mask(rows),
+                                                       _lib.ptr(self._ws), self._nbytes, _lib.ptr(self.next_idx),
+                                                       _lib.ptr(self.last_tok), _lib.stream_of(self._ws)),
+                   "pafc_rnnt_beam_stream_reset")
 
     def load(self, nframes, n: Optional[int] = None):
         """The frame counts of the next chunk into their device buffer (an int: every row; else (B,) counts, clamped to
@@ -2819,17 +2828,12 @@ class RnntBeamStream:
         if isinstance(nframes, int):
             self._nf.fill_(max(0, min(n, nframes)))
         else:
-            nf = torch.as_tensor(nframes, dtype=torch.int64)
-            if nf.shape != (self.B,):
-                raise _lib.PafcError(f"RnntBeamStream.feed: nframes must be ({self.B},)")
-            nf = nf.clamp(0, n)
-            # host counts go up from pinned memory without a synchronising call (the pinned block is not reused before the copy ran)
-            self._nf.copy_(nf if nf.is_cuda else nf.pin_memory(), non_blocking=True)
+            self._set_nframes(nframes, n)
 
     def launch_feed(self):
         """The feed kernel on the frame-count buffer: reads nothing from the host, allocates nothing."""
-        _lib.check(self.L.pafc_rnnt_beam_stream_feed(self.B, self.Tmax, self.max_total, self.beam, _lib.ptr(self._nf),
-                                                     _lib.ptr(self.ws), self.nws, _lib.stream_of(self.ws)),
+        _lib.check(self._L.pafc_rnnt_beam_stream_feed(self.B, self.Tmax, self.max_total, self.beam, _lib.ptr(self._nf),
+                                                     _lib.ptr(self._ws), self._nbytes, _lib.stream_of(self._ws)),
                    "pafc_rnnt_beam_stream_feed")
 
     def feed(self, nframes, n: Optional[int] = None):
@@ -2843,9 +2847,9 @@ class RnntBeamStream:
         if top_val.dtype != torch.float32 or top_idx.dtype != torch.int64 or top_val.numel() != self.B * self.beam * self.beam \
                 or top_idx.numel() != top_val.numel():
             raise _lib.PafcError("rnnt beam stream step: top_val float32 / top_idx int64 of (B, beam, beam)")
-        _lib.check(self.L.pafc_rnnt_beam_stream_step(self.B, self.Tmax, self.max_total, self.beam, self.blank, int(j),
-                                                     _lib.ptr(j_dev), _lib.ptr(top_val), _lib.ptr(top_idx), _lib.ptr(self.ws),
-                                                     self.nws, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
+        _lib.check(self._L.pafc_rnnt_beam_stream_step(self.B, self.Tmax, self.max_total, self.beam, self.blank, int(j),
+                                                     _lib.ptr(j_dev), _lib.ptr(top_val), _lib.ptr(top_idx), _lib.ptr(self._ws),
+                                                     self._nbytes, _lib.ptr(self.next_idx), _lib.ptr(self.last_tok),
                                                      _lib.stream_of(top_val)), "pafc_rnnt_beam_stream_step")
 
     def select_state(self, h: torch.Tensor, c: torch.Tensor, h_new: torch.Tensor, c_new: torch.Tensor,
@@ -2858,30 +2862,13 @@ class RnntBeamStream:
         final (an earlier drain's `committed`), default 0.  Returns a dict of host lists: count (B), committed (B),
         overflow (B), len (B, beam: total token counts, -1 unused), score (B, beam), tokens (B, beam: the tokens from
         counts[b] on, at most ld of them).  One device-to-host copy."""
-        B, beam = self.B, self.beam
-        counts = [0] * B if counts is None else [int(c) for c in counts]
-        if counts != self._from_h:
-            self._from.copy_(torch.tensor(counts, dtype=torch.int32).pin_memory(), non_blocking=True)
-            self._from_h = counts
-        ld = max(1, int(ld))
-        # one buffer, one read: score (B, beam) f64 | len (B, beam) | count | committed | overflow (B) | tokens (B, beam, ld) i32
-        nb = B * beam
-        o = [0, nb * 8]
-        for words in (nb, B, B, B, nb * ld):
-            o.append(o[-1] + 4 * words)
-        out = torch.empty(o[-1], dtype=torch.uint8, device=self.device)
-        p = lambda k: _lib.ptr(out[o[k]:o[k + 1]])
-        _lib.check(self.L.pafc_rnnt_beam_stream_drain(B, self.max_total, beam, _lib.ptr(self.ws), self.nws, _lib.ptr(self._from),
-                                                      ld, p(5), p(1), p(0), p(2), p(3), p(4), _lib.stream_of(self.ws)),
-                   "pafc_rnnt_beam_stream_drain")
-        h = out.cpu()                                  # the read
-        self.last_read_bytes = o[-1]
-        i32 = lambda k, *shape: h[o[k]:o[k + 1]].view(torch.int32).view(*shape)
-        lens = i32(1, B, beam).tolist()
-        toks = i32(5, B, beam, ld).tolist()
-        return {"score": h[:o[1]].view(torch.float64).view(B, beam).tolist(), "len": lens, "count": i32(2, B).tolist(),
-                "committed": i32(3, B).tolist(), "overflow": i32(4, B).tolist(),
-                "tokens": [[toks[b][n][:max(0, min(ld, lens[b][n] - counts[b]))] for n in range(beam)] for b in range(B)]}
+        def call(out, ld):
+            _lib.check(self._L.pafc_rnnt_beam_stream_drain(self.B, self.max_total, self.beam, _lib.ptr(self._ws), self._nbytes,
+                                                           _lib.ptr(self._from), ld, out.ptr("tokens"), out.ptr("len"),
+                                                           out.ptr("score"), out.ptr("count"), out.ptr("committed"),
+                                                           out.ptr("overflow"), _lib.stream_of(self._ws)),
+                       "pafc_rnnt_beam_stream_drain")
+        return self._drain_nbest(call, counts, ld)
 
 
 def rnnt_beam_select_state(h: torch.Tensor, c: torch.Tensor, h_new: torch.Tensor, c_new: torch.Tensor, next_idx: torch.Tensor,

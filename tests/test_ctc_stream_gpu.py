@@ -84,6 +84,57 @@ def test_stream_equals_offline_kernel_bit_for_bit(hip, tmp_path, beam, with_grap
                 assert [t[d["committed"][b]:] for t in d["tokens"][b]] == d2["tokens"][b]
 
 
+@pytest.mark.parametrize("beam", [4, 16])
+@pytest.mark.parametrize("extras", [False, True])
+def test_drain_from_the_committed_count_returns_the_same_lists(hip, tmp_path, beam, extras):
+    """drain(counts, ld) against the matching slices of drain(0, 24) after each of three feeds of 8 frames, for counts = the
+    previous `committed` and ld = 1 and the longest tail: tokens, len, count, overflow, the scores' bits and (extras: a context
+    graph and frame lists) times.  committed is the common prefix of the live members' full lists.  Row 1 sits the middle
+    feed out and row 2 is reset after the first.  A vocabulary of 12 keeps the prefixes few, so they leave the beam and are
+    formed again; it also bounds the top-k, hence K = min(beam, 12)."""
+    from paper_accurate_fast_cheap_amd import hip_ops
+    from paper_accurate_fast_cheap_amd.transformer.search import _common_prefix_len
+    Bn, Tmax, Tn, Vn = 3, 8, 24, 12
+    K = min(beam, Vn)
+    graph, phrases = synthetic_graph(tmp_path, 10, Vn, seed=beam, pool=8)
+    top_p, top_i = planted_logp(Bn, Tn, Vn, phrases, seed=200 + beam).cuda().topk(K, dim=-1)
+    assert bool((top_p[..., 1:] < top_p[..., :-1]).all())        # no ties in a frame's top-k
+    tables = graph.device_tables(torch.device("cuda", torch.cuda.current_device())) if extras else None
+    st = hip_ops.CtcBeamStream(Bn, Tmax, K, beam, "cuda", 0, tables, Tn, extras)
+    bits = lambda rows: torch.tensor(rows, dtype=torch.float64).view(torch.int64).tolist()
+
+    d = st.drain(None, Tn, extras)                            # before any feed: the empty prefix
+    assert d["committed"] == [0] * Bn and d["count"] == [1] * Bn and d["len"] == [[0] + [-1] * (beam - 1)] * Bn
+    assert d["tokens"] == [[[]] * beam] * Bn
+
+    counts, grew = [0] * Bn, False
+    for f, nf in enumerate(([8, 8, 8], [8, 0, 8], [8, 8, 8])):
+        st.feed(top_p[:, 8 * f:8 * f + 8].contiguous(), top_i[:, 8 * f:8 * f + 8].contiguous(), nf)
+        full = st.drain(None, Tn, extras)
+        assert full["overflow"] == [0] * Bn
+        live = [[full["tokens"][b][n] for n in range(full["count"][b])] for b in range(Bn)]
+        assert all(len(live[b][n]) == full["len"][b][n] for b in range(Bn) for n in range(len(live[b])))
+        assert full["committed"] == [_common_prefix_len(x) for x in live]
+        tail = max(1, max(len(x) - counts[b] for b in range(Bn) for x in live[b]))
+        for ld in (1, tail):
+            part = st.drain(counts, ld, extras)
+            for k in ("len", "count", "overflow", "committed"):
+                assert part[k] == full[k], (k, ld)
+            assert bits(part["score"]) == bits(full["score"])
+            for b in range(Bn):
+                assert part["tokens"][b] == [x[counts[b]:counts[b] + ld] for x in full["tokens"][b]]
+            if extras:
+                assert part["times"] == full["times"]
+        grew = grew or any(c > 0 for c in full["committed"])
+        counts = list(full["committed"])
+        if f == 0:
+            st.reset([2])
+            counts[2] = 0
+            d = st.drain(counts, Tn, False)
+            assert d["len"][2] == [0] + [-1] * (beam - 1) and d["committed"] == counts and d["len"][:2] == full["len"][:2]
+    assert grew                                               # the planted peaks commit a prefix in some row
+
+
 @pytest.mark.parametrize("beam", [4, 8, 16])
 @pytest.mark.parametrize("with_graph", [False, True])
 def test_streamer_matches_the_host_loop(hip, tmp_path, beam, with_graph):

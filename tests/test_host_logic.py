@@ -428,3 +428,41 @@ def test_capture_refused_tells_the_runtime_refusing_a_capture_from_an_error_of_t
                                         "error during capture")) is True
     assert capture_refused(RuntimeError("HIP error: hipErrorStreamCaptureUnsupported")) is True
     assert capture_refused(RuntimeError("launch failed")) is False
+
+
+def test_packed_lays_a_beam_drain_out_in_the_documented_order():
+    """hip_ops._Packed on the fields of a beam drain at B = 2, beam = 3, ld = 5: score (B, beam) f64 | len (B, beam) | count |
+    committed | overflow (B) | tokens (B, beam, ld) i32 back to back, 8-byte fields first and 8-byte aligned, and what a kernel
+    writes at ptr(name) is what host(name) shows after the one read."""
+    import ctypes
+    from paper_accurate_fast_cheap_amd.hip_ops import _Packed
+    B, beam, ld = 2, 3, 5
+    i32, f64 = torch.int32, torch.float64
+    fields = [("score", f64, (B, beam)), ("len", i32, (B, beam)), ("count", i32, (B,)), ("committed", i32, (B,)),
+              ("overflow", i32, (B,)), ("tokens", i32, (B, beam, ld))]
+    p = _Packed(fields, "cpu")
+    assert p.nbytes == p.buf.numel() == 2 * 3 * 8 + 4 * (2 * 3 + 3 * 2 + 2 * 3 * 5)
+    want = 0
+    for name, dtype, shape in fields:                           # the documented order, no gaps
+        assert p.offset(name) == want, name
+        assert p.ptr(name).value == p.buf.data_ptr() + want
+        want += dtype.itemsize * torch.Size(shape).numel()
+    assert want == p.nbytes
+    # 8-byte fields go first wherever the caller names them, and are aligned
+    q = _Packed([("n", i32, (3,)), ("frames", torch.int64, (2, 2)), ("score", f64, (3,)), ("tok", i32, (5,))], "cpu")
+    assert [q.offset(k) for k in ("frames", "score", "n", "tok")] == [0, 32, 56, 68] and q.nbytes == 88
+    for pk, names in ((p, ("score",)), (q, ("frames", "score"))):
+        for k in names:
+            assert pk.offset(k) % 8 == 0 and pk.ptr(k).value % 8 == 0
+    # written through the pointers, as a kernel does; read through the host views
+    vals = {}
+    for k, (name, dtype, shape) in enumerate(fields):
+        n = torch.Size(shape).numel()
+        ctype = ctypes.c_double if dtype == f64 else ctypes.c_int32
+        v = [(-1) ** i * (1000 * k + i) * (0.5 if dtype == f64 else 1) for i in range(n)]
+        (ctype * n).from_address(p.ptr(name).value)[:] = v
+        vals[name] = torch.tensor(v, dtype=dtype).view(shape)
+    p.read()
+    for name, dtype, shape in fields:
+        h = p.host(name)
+        assert h.dtype == dtype and tuple(h.shape) == shape and torch.equal(h, vals[name]), name

@@ -106,7 +106,7 @@ def test_overflow_consumes_nothing_and_holds_until_reset(hip):
     from paper_accurate_fast_cheap_amd import hip_ops
     tv, ti, *_ = _offline(3)
     st = hip_ops.RnntBeamStream(B, 16, 3, 0, "cuda", max_total_frames=20)
-    st.ws.zero_()                                             # as if never reset
+    st._ws.zero_()                                             # as if never reset
     st.reset([0, 1])
 
     def run(nf, a):
@@ -199,12 +199,12 @@ def test_bad_arguments_are_rejected(hip):
     tv = torch.zeros(B, 8, 8, device="cuda")
     ti = torch.zeros(B, 8, 8, dtype=torch.int64, device="cuda")
     s = _lib.stream_of(tv)
-    assert L.pafc_rnnt_beam_stream_step(B, 16, 40, 17, 0, 0, None, p(tv), p(ti), p(st.ws), st.nws, p(st.next_idx), p(st.last_tok), s) == -7
-    assert L.pafc_rnnt_beam_stream_step(B, 16, 40, 8, 0, 0, None, p(tv), p(ti), p(st.ws), st.nws - 1, p(st.next_idx), p(st.last_tok), s) == -4
-    assert L.pafc_rnnt_beam_stream_step(B, 16, 40, 8, 0, 0, None, None, p(ti), p(st.ws), st.nws, p(st.next_idx), p(st.last_tok), s) == -1
-    assert L.pafc_rnnt_beam_stream_feed(B, 16, 40, 8, None, p(st.ws), st.nws, s) == -1
-    assert L.pafc_rnnt_beam_stream_reset(B, 40, 8, 0, None, None, st.nws, p(st.next_idx), p(st.last_tok), s) == -1
-    assert L.pafc_rnnt_beam_stream_drain(B, 40, 8, p(st.ws), st.nws, None, 4, None, None, None, None, None, None, s) == -1
+    assert L.pafc_rnnt_beam_stream_step(B, 16, 40, 17, 0, 0, None, p(tv), p(ti), p(st._ws), st._nbytes, p(st.next_idx), p(st.last_tok), s) == -7
+    assert L.pafc_rnnt_beam_stream_step(B, 16, 40, 8, 0, 0, None, p(tv), p(ti), p(st._ws), st._nbytes - 1, p(st.next_idx), p(st.last_tok), s) == -4
+    assert L.pafc_rnnt_beam_stream_step(B, 16, 40, 8, 0, 0, None, None, p(ti), p(st._ws), st._nbytes, p(st.next_idx), p(st.last_tok), s) == -1
+    assert L.pafc_rnnt_beam_stream_feed(B, 16, 40, 8, None, p(st._ws), st._nbytes, s) == -1
+    assert L.pafc_rnnt_beam_stream_reset(B, 40, 8, 0, None, None, st._nbytes, p(st.next_idx), p(st.last_tok), s) == -1
+    assert L.pafc_rnnt_beam_stream_drain(B, 40, 8, p(st._ws), st._nbytes, None, 4, None, None, None, None, None, None, s) == -1
     assert L.pafc_rnnt_beam_select_state(0, 2, B, 8, 64, None, None, None, None, None, s) == -1
     with pytest.raises(_lib.PafcError):
         st.step(0, tv.double(), ti)
