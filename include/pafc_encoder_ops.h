@@ -431,6 +431,20 @@ int pafc_mamba2_scan_state(int B, int L, int H, const void *xbc, long ldx, const
                            float *y_f32, void *y_bf16, const float *s_in, float *s_out, int reverse, int chunk_len,
                            void *workspace, size_t workspace_bytes, pafc_stream_t stream);
 
+/* Backward of pafc_mamba2_scan_dir (csrc/mamba2_scan_bwd.hip), per head with a_t = exp(log_a_t):
+ *   G_t = C_t gy_t^T + a_{t+1} G_{t+1}  (the 128 x 64 adjoint state, walked right to left),  gxu_t = B_t . G_t
+ *   g_x_t = dt_t gxu_t,  g_dt_t = gxu_t . x_t,  g_B_t = sum_heads dt_t G_t x_t,  g_C_t = sum_heads h_t gy_t
+ *   g_la_t = a_t <G_t, h_{t-1}> = sum over the steps s >= t of (gy_s . y_s - dt_s g_dt_s)
+ * gy: (B, L, H * 64) fp32, 16-byte aligned, the gradient of the fp32 scan output (no D term).  g_xbc: (B, L, ldg) bf16 rows
+ * [g_x | g_B | g_C] (ldg >= H * 64 + 256, a multiple of 4; columns beyond stay untouched); g_B and g_C are summed over the
+ * heads in fp32 and rounded once.  g_dt, g_la: (B, L, H) fp32; g_la may be NULL (the caller forms the suffix sum from g_dt and
+ * the saved y).  g_dt is the gradient through the input dt alone: log_a is a separate input.  reverse as in the forward.
+ * workspace: pafc_mamba2_scan_bwd_workspace_bytes() bytes, 16-byte aligned, always needed (per-head partials of g_B / g_C). */
+size_t pafc_mamba2_scan_bwd_workspace_bytes(int B, int L, int H, int chunk_len);
+int pafc_mamba2_scan_backward(int B, int L, int H, const void *xbc, long ldx, const float *dt, const float *log_a,
+                              const float *gy, void *g_xbc, long ldg, float *g_dt, float *g_la, int reverse, int chunk_len,
+                              void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+
 /* Hand-written bf16 GEMM with fused epilogue, batched (csrc/gemm_bf16.hip: 128 x 128 tiles, two blocks per CU;
  * csrc/gemm_ph.hip: persistent 256-wide phase-pipelined tiles for problems that fill the chip with them -- the entry point
  * picks):

@@ -120,6 +120,8 @@ SIGNATURES = {
     "pafc_mamba2_scan_skip_bf16": (I, [I, I, I, P, G, P, P, P, P, I, I, P, Z, P]),
     "pafc_mamba2_gate_norm": (I, [I, G, I, P, P, G, P, F, P, P]),
     "pafc_mamba2_scan_state": (I, [I, I, I, P, G, P, P, P, P, P, P, P, I, I, P, Z, P]),
+    "pafc_mamba2_scan_bwd_workspace_bytes": (Z, [I, I, I, I]),
+    "pafc_mamba2_scan_backward": (I, [I, I, I, P, G, P, P, P, P, G, P, P, I, I, P, Z, P]),
     "pafc_gemm_bf16": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, P]),
     "pafc_gemm_bf16_glu_half": (I, [G, I, I, I]),
     "pafc_conv3x3s2_nhwc_bf16_ph": (I, [I, I, I, I, I, P, P, P, P, I, I, P]),

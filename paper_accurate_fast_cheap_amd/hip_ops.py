@@ -3058,6 +3058,54 @@ def mamba2_scan_state(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, 
     return y, s_out
 
 
+def mamba2_scan_backward(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, gy: torch.Tensor, H: int,
+                         reverse: bool = False, chunk_len: int = 0):
+    """Backward of mamba2_scan's fp32 form (include/pafc_encoder_ops.h: pafc_mamba2_scan_backward): xbc (B, L, ldx) bf16
+    contiguous, dt / log_a (B, L, H) fp32, gy (B, L, H*64) fp32 = dL/dy  ->  (g_xbc bf16 like xbc: [g_x | g_B | g_C] with g_B,
+    g_C summed over the heads, g_dt, g_la fp32 (B, L, H)).  g_dt is the gradient through the argument dt alone."""
+    _lib.require_gpu(xbc, dt, log_a, gy)
+    if xbc.dtype != torch.bfloat16 or dt.dtype != torch.float32 or log_a.dtype != torch.float32 or gy.dtype != torch.float32:
+        raise _lib.PafcError("mamba2_scan_backward: bf16 xbc, fp32 dt / log_a / gy")
+    if xbc.dim() != 3 or not xbc.is_contiguous() or not dt.is_contiguous() or not log_a.is_contiguous() or not gy.is_contiguous():
+        raise _lib.PafcError("mamba2_scan_backward: contiguous xbc (B, L, >= H * 64 + 256), dt / log_a (B, L, H), gy (B, L, H * 64)")
+    B, Lq, ldx = xbc.shape
+    if tuple(dt.shape) != (B, Lq, H) or tuple(log_a.shape) != (B, Lq, H) or tuple(gy.shape) != (B, Lq, H * 64):
+        raise _lib.PafcError("mamba2_scan_backward: dt / log_a must be (B, L, H), gy (B, L, H * 64)")
+    Lb = _lib.lib()
+    nws = Lb.pafc_mamba2_scan_bwd_workspace_bytes(B, Lq, H, chunk_len)
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=xbc.device)
+    g_xbc = torch.empty_like(xbc) if ldx == H * 64 + 256 else torch.zeros_like(xbc)     # (padding columns: zero)
+    g_dt = torch.empty_like(dt)
+    g_la = torch.empty_like(log_a)
+    rc = Lb.pafc_mamba2_scan_backward(B, Lq, H, _lib.ptr(xbc), ldx, _lib.ptr(dt), _lib.ptr(log_a), _lib.ptr(gy), _lib.ptr(g_xbc),
+                                      ldx, _lib.ptr(g_dt), _lib.ptr(g_la), int(reverse), chunk_len, _lib.ptr(ws), nws,
+                                      _lib.stream_of(xbc))
+    _lib.check(rc, "pafc_mamba2_scan_backward")
+    return g_xbc, g_dt, g_la
+
+
+class _Mamba2ScanTrain(torch.autograd.Function):
+    """y = mamba2_scan(xbc, dt, log_a) in fp32 with the SSD backward kernel behind it."""
+
+    @staticmethod
+    def forward(ctx, xbc, dt, log_a, H, reverse):
+        xbc, dt, log_a = xbc.contiguous(), dt.contiguous(), log_a.contiguous()
+        ctx.save_for_backward(xbc, dt, log_a)
+        ctx.H, ctx.reverse = H, reverse
+        return mamba2_scan(xbc, dt, log_a, H, reverse)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xbc, dt, log_a = ctx.saved_tensors
+        g_xbc, g_dt, g_la = mamba2_scan_backward(xbc, dt, log_a, gy.float().contiguous(), ctx.H, ctx.reverse)
+        return g_xbc, g_dt, g_la, None, None
+
+
+def mamba2_scan_train(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, H: int, reverse: bool = False) -> torch.Tensor:
+    """mamba2_scan (fp32 y, no D term) as a differentiable op: gradients reach xbc (bf16, its shape), dt and log_a."""
+    return _Mamba2ScanTrain.apply(xbc, dt, log_a, H, bool(reverse))
+
+
 def mamba2_gate_norm(y: torch.Tensor, z: torch.Tensor, norm_weight: torch.Tensor, eps: float) -> torch.Tensor:
     """RMSNorm(y * silu(z)) * norm_weight over the last axis; z may be a column slice of a wider tensor."""
     _lib.require_gpu(y, norm_weight)

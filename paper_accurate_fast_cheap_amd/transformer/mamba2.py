@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..rwkv_v6.wkv6_op import wkv6_forward
+from ..rwkv_v6.wkv6_op import wkv6, wkv6_forward
 
 _EMPTY_CACHE = torch.zeros((0, 0, 0, 0))
 
@@ -166,7 +166,8 @@ class Mamba2(nn.Module):
 
     def forward(self, u: torch.Tensor, reverse: bool = False) -> torch.Tensor:
         """reverse: the block run right-to-left on the un-flipped sequence = flip(forward(flip(u))) without the copies
-        (only the bf16 kernels take the flag; elsewhere the two flips are made)."""
+        (only the bf16 inference kernels take the flag; elsewhere the two flips are made).  With gradients enabled the scan is
+        differentiable: bf16 on the SSD kernels (hip_ops.mamba2_scan_train), otherwise through the WKV-6 scan's backward."""
         if self.fused_eligible(u) and (not reverse or (u.dtype == torch.bfloat16 and self.ssd_kernel)):
             return self._forward_fused(u, reverse)
         if reverse:
@@ -187,6 +188,13 @@ class Mamba2(nn.Module):
         dt = F.softplus(dt.float() + self.dt_bias.float())                            # (B, L, H)
         A = -torch.exp(self.A_log.float())                                             # (H,)
         logdec = dt * A                                                                # log a_t  (< 0)
+        if torch.is_grad_enabled() and xBC.is_cuda and xBC.dtype == torch.bfloat16 and self.ssd_kernel and N == 128:
+            # training in bf16: the SSD scan kernel and its backward kernel; dt_bias and A_log get their gradients from the two
+            # framework lines above, the D skip, the gate and the norm stay framework ops
+            from .. import hip_ops
+            y = hip_ops.mamba2_scan_train(xBC, dt, logdec, H)                          # fp32 (B, L, H * P)
+            y = y + (x.float().view(Bsz, L, H, P) * self.D.float().view(1, 1, H, 1)).reshape(Bsz, L, H * P)
+            return self.out_proj(self.norm(y.to(z.dtype), z))
         # shifted decay a_{t+1}; the last step's value never reaches an output
         nxt = torch.cat([logdec[:, 1:], torch.zeros_like(logdec[:, :1])], dim=1)       # (B, L, H)
         a_next = torch.exp(nxt)
@@ -201,7 +209,7 @@ class Mamba2(nn.Module):
             Ch = Cm[..., half * 64:(half + 1) * 64].float()
             k = (a_next.unsqueeze(-1) * Bh.unsqueeze(2)).reshape(Bsz, L, H * 64).contiguous()
             r = Ch.unsqueeze(2).expand(Bsz, L, H, 64).reshape(Bsz, L, H * 64).contiguous()
-            y = y + wkv6_forward(r, k, v, wk, u0)
+            y = y + wkv6(r, k, v, wk, u0)                                              # (autograd-aware: the WKV-6 backward)
             y = y + ((Bh * Ch).sum(-1, keepdim=True).unsqueeze(-1) * v.view(Bsz, L, H, P)).reshape(Bsz, L, H * P)
         y = y + (xf * self.D.float().view(1, 1, H, 1)).reshape(Bsz, L, H * P)
         y = self.norm(y.to(z.dtype), z)
