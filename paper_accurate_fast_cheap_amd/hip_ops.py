@@ -2987,6 +2987,8 @@ def causal_conv_silu_cl_prefix(xp: torch.Tensor, weight: torch.Tensor, bias: Opt
 def mamba2_prep(xbc: torch.Tensor, dt_raw: torch.Tensor, dt_bias: torch.Tensor, A_log: torch.Tensor, d_inner: int):
     """xbc (B, L, d_inner + 256) contiguous, dt_raw (B, L, H) slice -> [r0, r1, k0, k1, v, w] fp32 (B, L, d_inner)."""
     _lib.require_gpu(xbc, dt_bias, A_log)
+    if xbc.dim() != 3 or not xbc.is_contiguous() or xbc.shape[2] != d_inner + 256:
+        raise _lib.PafcError("mamba2_prep: contiguous xbc (B, L, d_inner + 256)")
     B, Lq, _ = xbc.shape
     planes = [torch.empty((B, Lq, d_inner), dtype=torch.float32, device=xbc.device) for _ in range(6)]
     rc = _lib.lib().pafc_mamba2_prep(_lib.dtype_code(xbc.dtype), B, Lq, d_inner, _lib.ptr(xbc), _lib.ptr(dt_raw),
@@ -2997,28 +2999,32 @@ def mamba2_prep(xbc: torch.Tensor, dt_raw: torch.Tensor, dt_bias: torch.Tensor, 
 
 
 def mamba2_scan(xbc: torch.Tensor, dt: torch.Tensor, log_a: torch.Tensor, H: int, reverse: bool = False,
-                D: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Mamba-2 selective scan on the dedicated SSD kernel: xbc (B, L, H*64 + 256) bf16 contiguous, dt / log_a (B, L, H)
-    fp32 -> y (B, L, H*64) fp32 (include/pafc_encoder_ops.h: pafc_mamba2_scan_dir); with D (H) fp32 the scan returns
-    bf16(y + D x) as mamba_ssm's does (pafc_mamba2_scan_skip_bf16)."""
+                D: Optional[torch.Tensor] = None, chunk_len: int = 0) -> torch.Tensor:
+    """Mamba-2 selective scan on the dedicated SSD kernel: xbc (B, L, >= H*64 + 256) bf16 contiguous, dt / log_a (B, L, H)
+    fp32 contiguous -> y (B, L, H*64) fp32 (include/pafc_encoder_ops.h: pafc_mamba2_scan_dir); with D (H) fp32 the scan returns
+    bf16(y + D x) as mamba_ssm's does (pafc_mamba2_scan_skip_bf16).  chunk_len 0: the library's own chunk length."""
     _lib.require_gpu(xbc, dt, log_a, D)
     if xbc.dtype != torch.bfloat16 or dt.dtype != torch.float32 or log_a.dtype != torch.float32:
         raise _lib.PafcError("mamba2_scan: bf16 xbc, fp32 dt / log_a")
+    if xbc.dim() != 3 or not xbc.is_contiguous() or not dt.is_contiguous() or not log_a.is_contiguous():
+        raise _lib.PafcError("mamba2_scan: contiguous xbc (B, L, >= H * 64 + 256), dt / log_a (B, L, H)")
     B, Lq, ldx = xbc.shape
+    if tuple(dt.shape) != (B, Lq, H) or tuple(log_a.shape) != (B, Lq, H) or ldx < H * 64 + 256:
+        raise _lib.PafcError("mamba2_scan: dt / log_a must be (B, L, H), xbc rows at least H * 64 + 256 wide")
     Lb = _lib.lib()
-    nws = Lb.pafc_mamba2_scan_workspace_bytes(B, Lq, H, 0)
+    nws = Lb.pafc_mamba2_scan_workspace_bytes(B, Lq, H, chunk_len)
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=xbc.device)
     if D is not None:
         if D.dtype != torch.float32 or D.shape != (H,):
             raise _lib.PafcError("mamba2_scan: D must be float32 (H)")
         y = torch.empty((B, Lq, H * 64), dtype=torch.bfloat16, device=xbc.device)
         rc = Lb.pafc_mamba2_scan_skip_bf16(B, Lq, H, _lib.ptr(xbc), ldx, _lib.ptr(dt), _lib.ptr(log_a), _lib.ptr(D),
-                                           _lib.ptr(y), int(reverse), 0, _lib.ptr(ws) if nws else None, nws,
+                                           _lib.ptr(y), int(reverse), chunk_len, _lib.ptr(ws) if nws else None, nws,
                                            _lib.stream_of(xbc))
         _lib.check(rc, "pafc_mamba2_scan_skip_bf16")
         return y
     y = torch.empty((B, Lq, H * 64), dtype=torch.float32, device=xbc.device)
-    rc = Lb.pafc_mamba2_scan_dir(B, Lq, H, _lib.ptr(xbc), ldx, _lib.ptr(dt), _lib.ptr(log_a), _lib.ptr(y), int(reverse), 0,
+    rc = Lb.pafc_mamba2_scan_dir(B, Lq, H, _lib.ptr(xbc), ldx, _lib.ptr(dt), _lib.ptr(log_a), _lib.ptr(y), int(reverse), chunk_len,
                                  _lib.ptr(ws) if nws else None, nws, _lib.stream_of(xbc))
     _lib.check(rc, "pafc_mamba2_scan_dir")
     return y
@@ -3123,6 +3129,8 @@ def mamba2_gate_norm(y: torch.Tensor, z: torch.Tensor, norm_weight: torch.Tensor
 def mamba2_finish(y0, y1, xbc, dt_raw, z, dt_bias, D, norm_weight, eps: float, d_inner: int, diag: bool = True
                   ) -> torch.Tensor:
     _lib.require_gpu(y0, y1, xbc, dt_bias, D, norm_weight)
+    if xbc.dim() != 3 or not xbc.is_contiguous() or xbc.shape[2] != d_inner + 256:
+        raise _lib.PafcError("mamba2_finish: contiguous xbc (B, L, d_inner + 256)")
     B, Lq, _ = xbc.shape
     out = torch.empty((B, Lq, d_inner), dtype=xbc.dtype, device=xbc.device)
     rc = _lib.lib().pafc_mamba2_finish(_lib.dtype_code(xbc.dtype), B, Lq, d_inner, _lib.ptr(y0), _lib.ptr(y1), _lib.ptr(xbc),
