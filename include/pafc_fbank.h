@@ -16,6 +16,22 @@
  *   mel_weights (num_mel_bins, 257), mel_lo / mel_hi (num_mel_bins): filter b is non-zero on bins [lo, hi)
  * wave: (num_samples) float32 in int16 range; noise: (frames, 400) standard normal or NULL (dither off);
  * out: (frames, num_mel_bins) float32, frames = pafc_fbank_num_frames(num_samples) = 1 + (S - 400) / 160.
+ *
+ * Every frame is computed from its own 400 samples alone, so the batched and the streaming entry points below give, frame by
+ * frame, the bits pafc_fbank_f32 gives for the same samples.
+ *
+ * pafc_fbank_batch: B waveforms as the rows of waves (B, ld_wave >= max_samples) in ONE launch, grid (ceil(T_max / 64), B).
+ *   lengths: device int64 (B) sample counts, clamped to [0, max_samples] in the kernel, or NULL (every row max_samples).
+ *   out: (B, T_max, num_mel_bins), T_max = pafc_fbank_num_frames(max_samples), PAFC_F32 or PAFC_BF16 (round-to-nearest-even of
+ *   the fp32 value); frames of a row at or past its own frame count are written as ZERO.  out_frames: device int32 (B) that
+ *   receives every row's frame count, or NULL.  noise: (B, T_max, 400) or NULL.  No host synchronisation.
+ *
+ * pafc_fbank_stream: B lock-step streams.  Row b's samples are carry[b, 0:c] followed by chunk[b, 0:n] (carry: (B, 560)
+ *   float32, 0 <= c < 560; chunk: (B, ld_chunk >= n)).  frames = pafc_fbank_num_frames(c + n) frames per row are written at
+ *   out + row * out_row_stride + (first_frame + f) * num_mel_bins (strides in elements of out_dtype), and a second small kernel
+ *   on the same stream then moves the last c_next = c + n - 160 * frames samples to the front of carry[b], in place.
+ *   frames == 0 launches only that update, n == 0 launches nothing; both launches can be captured.  pafc_fbank_stream_plan is
+ *   the arithmetic (frames, c_next) on the host, c_next < 560 always.  dither != 0 is PAFC_ERR_UNSUPPORTED here.
  */
 #ifndef PAFC_FBANK_H
 #define PAFC_FBANK_H
@@ -31,6 +47,15 @@ int pafc_fbank_tables_cols(void);
 int pafc_fbank_f32(const float *wave, long num_samples, const float *window, const float *dft_table,
                    const float *mel_weights, const int *mel_lo, const int *mel_hi, int num_mel_bins,
                    const float *noise, float dither, float preemph, float *out, pafc_stream_t stream);
+int pafc_fbank_batch(const float *waves, long ld_wave, const long *lengths, int B, long max_samples, const float *window,
+                     const float *dft_table, const float *mel_weights, const int *mel_lo, const int *mel_hi, int num_mel_bins,
+                     const float *noise, float dither, float preemph, void *out, int out_dtype, int *out_frames,
+                     pafc_stream_t stream);
+int pafc_fbank_stream_plan(int c, long n, long *frames, int *c_next);
+int pafc_fbank_stream(float *carry, int c, const float *chunk, long ld_chunk, long n, int B, const float *window,
+                      const float *dft_table, const float *mel_weights, const int *mel_lo, const int *mel_hi, int num_mel_bins,
+                      float dither, float preemph, void *out, int out_dtype, long out_row_stride, long first_frame,
+                      pafc_stream_t stream);
 
 #ifdef __cplusplus
 }

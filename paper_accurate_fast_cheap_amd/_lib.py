@@ -137,6 +137,9 @@ SIGNATURES = {
     "pafc_fbank_num_frames": (G, [G]),
     "pafc_fbank_tables_cols": (I, []),
     "pafc_fbank_f32": (I, [P, G, P, P, P, P, P, I, P, F, F, P, P]),
+    "pafc_fbank_batch": (I, [P, G, P, I, G, P, P, P, P, P, I, P, F, F, P, I, P, P]),
+    "pafc_fbank_stream_plan": (I, [I, G, P, P]),
+    "pafc_fbank_stream": (I, [P, I, P, G, G, I, P, P, P, P, P, I, F, F, P, I, G, G, P]),
     # include/pafc_search.h
     "pafc_ctc_greedy": (I, [I, I, I, I, P, P, I, P, P, P, P, P]),
     "pafc_log_softmax_rows": (I, [I, G, I, P, P, P]),

@@ -13,18 +13,27 @@
 // lane exchange, written to LDS P[64][257].  (4) 80 mel sums over each filter's support, log(max(., eps)),
 // staged and stored as 64 contiguous rows.  fp32 throughout (bf16 operands would put ~0.4 % noise on the power
 // spectrum).  The DFT is 206 k MAC per frame = 74 GFLOP for 30 minutes of audio.
+//
+// The four stages are one device function, fbank_tile, over a sample-fetch functor (where frame f's sample n lies) and an
+// emit functor (where the tile's rows go).  Every frame depends on its own 400 samples only -- one wave_sum per frame, one A
+// row per MFMA output row --, so each instantiation gives the same bits per frame: pafc_fbank_f32 (one waveform),
+// pafc_fbank_batch (grid.y = row of a ragged batch; rows past a row's frame count are written as zero) and
+// pafc_fbank_stream (a row's samples are its carried tail followed by the new chunk; a second small kernel moves the carry).
 #include "pafc_common.h"
-#include "../../include/pafc_fbank.h"
+#include "fbank_host.h"
 
 namespace pafc {
 namespace {
 
-constexpr int WIN = 400, SHIFT = 160, NBIN = 257;
+using fbank_host::WIN;
+using fbank_host::SHIFT;
+using fbank_host::CARRY;
+using fbank_host::MAXMEL;
+constexpr int NBIN = 257;
 constexpr int NTILE = 17, NCOL = NTILE * 32;  // 544 >= 2 * 257
 constexpr int FPB = 64;                       // frames per block
 constexpr int LDA = WIN + 1;                  // LDS row stride (words)
 constexpr int LDP = NBIN;                     // 257: odd, conflict-free
-constexpr int MAXMEL = 128;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -44,13 +53,16 @@ struct FbankParams {
     float *out;             // (m, nmel)
 };
 
-__global__ __launch_bounds__(256) void fbank_kernel(const FbankParams p) {
+// One tile of 64 frames [m0, m0 + 64) of a row with p.m frames (p.noise: that row's; p.wave and p.out are not used here).
+// fetch(160 f)[n]: sample n of the row's frame f, asked for live frames only (f < p.m, n < 400); emit(O, ldo, tid): called by
+// all 256 threads after the last barrier with the staged tile O[64][ldo].
+template <class Fetch, class Emit>
+__device__ __forceinline__ void fbank_tile(const FbankParams &p, const int m0, Fetch fetch, Emit emit) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *A = lds;                            // [64][401]
     float *P = lds;                            // [64][257], aliases A after the GEMM
     float *O = lds + FPB * LDP + 64;           // [64][nmel] staging, behind P
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int m0 = blockIdx.x * FPB;
 
     // ---- (1) frame conditioning ----------------------------------------------------------------------
     for (int ff = 0; ff < 16; ++ff) {
@@ -59,7 +71,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankParams p) {
         float x[7], xp[7];
         float sum = 0.f;
         const bool live = fr < p.m;
-        const float *src = p.wave + (long)fr * SHIFT;
+        const auto src = fetch((long)fr * SHIFT);
         const float *nz = p.noise ? p.noise + (long)fr * WIN : nullptr;
 #pragma unroll
         for (int q = 0; q < 7; ++q) {
@@ -147,9 +159,113 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankParams p) {
         }
     }
     __syncthreads();
-    const int nvalid = min(FPB, p.m - m0);
-    float *dst = p.out + (long)m0 * p.nmel;
-    for (int i = tid; i < nvalid * p.nmel; i += 256) dst[i] = O[(i / p.nmel) * ldo + (i % p.nmel)];
+    emit(O, ldo, tid);
+}
+
+__global__ __launch_bounds__(256) void fbank_kernel(const FbankParams p) {
+    const int m0 = blockIdx.x * FPB;
+    fbank_tile(p, m0, [&](long s0) { return p.wave + s0; }, [&](const float *O, int ldo, int tid) {
+        const int nvalid = min(FPB, p.m - m0);
+        float *dst = p.out + (long)m0 * p.nmel;
+        for (int i = tid; i < nvalid * p.nmel; i += 256) dst[i] = O[(i / p.nmel) * ldo + (i % p.nmel)];
+    });
+}
+
+// Rows of a batch or of B lock-step streams: grid (tiles, rows).
+struct RowsParams {
+    const float *carry;       // stream: (rows, CARRY), the first c samples of a row; batch: unused
+    int c;
+    long ld_wave;             // row stride of p.wave (the batch's waveforms / the stream's chunk)
+    const long *lens;         // batch: (rows) sample counts or null; stream: null
+    long max_samples;         // batch: the row length the grid was sized for; stream: c + n
+    int t_rows;               // rows [0, t_rows) of a batch row's output are written (zero past its frame count)
+    void *out;                // row b, frame f at out + b * out_row_stride + out_offset + f * nmel  (elements)
+    long out_row_stride, out_offset;
+    int *out_lens;            // (rows) frame counts or null
+};
+
+// sample s0 + n of (carry[0:c] ++ chunk)
+struct CarryThenChunk {
+    const float *carry, *chunk;
+    long c, s0;
+    __device__ __forceinline__ float operator[](int n) const { return s0 + n < c ? carry[s0 + n] : chunk[s0 + n - c]; }
+};
+
+template <typename ET, bool STREAM>
+__global__ __launch_bounds__(256) void fbank_rows_kernel(const FbankParams p, const RowsParams r) {
+    const int b = blockIdx.y, m0 = blockIdx.x * FPB, tid = threadIdx.x;
+    long len = r.max_samples;
+    if (r.lens) {
+        const long v = r.lens[b];
+        len = v < 0 ? 0 : (v > r.max_samples ? r.max_samples : v);
+    }
+    const int m = (int)fbank_host::num_frames(len);             // <= t_rows
+    if (m0 == 0 && tid == 0 && r.out_lens) r.out_lens[b] = m;
+    ET *dst = (ET *)r.out + (long)b * r.out_row_stride + r.out_offset + (long)m0 * p.nmel;
+    const int nrows = min(FPB, r.t_rows - m0);
+    if (m0 >= m) {                                              // block-uniform, before any barrier: a tile of padding
+        for (int i = tid; i < nrows * p.nmel; i += 256) Elem<ET>::store(dst + i, 0.f);
+        return;
+    }
+    FbankParams q = p;
+    q.m = m;
+    q.noise = p.noise ? p.noise + (long)b * r.t_rows * WIN : nullptr;
+    const float *row = p.wave + (long)b * r.ld_wave;
+    const float *car = STREAM ? r.carry + (long)b * CARRY : nullptr;
+    const int c = STREAM ? r.c : 0;
+    auto emit = [&](const float *O, int ldo, int) {
+        const int nvalid = min(FPB, m - m0);
+        for (int i = tid; i < nrows * q.nmel; i += 256) {
+            const int f = i / q.nmel;
+            Elem<ET>::store(dst + i, f < nvalid ? O[f * ldo + (i % q.nmel)] : 0.f);   // padding is zero, not log(eps)
+        }
+    };
+    if (STREAM)
+        fbank_tile(q, m0, [&](long s0) { return CarryThenChunk{car, row, c, s0}; }, emit);
+    else
+        fbank_tile(q, m0, [&](long s0) { return row + s0; }, emit);
+}
+
+// carry[b, 0:c_next] <- the last c_next samples of (carry[b, 0:c] ++ chunk[b, 0:n]).  Source and destination overlap when
+// n < c: one block per row reads its <= CARRY - 1 samples into registers, barriers, then writes.
+__global__ __launch_bounds__(256) void fbank_carry_kernel(float *carry, int c, const float *chunk, long ld_chunk, long n,
+                                                          int c_next) {
+    float *car = carry + (long)blockIdx.x * CARRY;
+    const float *row = chunk + (long)blockIdx.x * ld_chunk;
+    const long first = c + n - c_next;
+    float v[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int j = threadIdx.x + 256 * q;
+        v[q] = 0.f;
+        if (j < c_next) {
+            const long s = first + j;
+            v[q] = s < c ? car[s] : row[s - c];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int j = threadIdx.x + 256 * q;
+        if (j < c_next) car[j] = v[q];
+    }
+}
+
+size_t tile_lds_bytes(int nmel) {
+    const size_t a_bytes = sizeof(float) * FPB * LDA;
+    const size_t po_bytes = sizeof(float) * (FPB * LDP + 64 + FPB * (nmel | 1));
+    return a_bytes > po_bytes ? a_bytes : po_bytes;
+}
+
+template <typename ET, bool STREAM>
+int launch_rows(const FbankParams &p, const RowsParams &r, long tiles, int B, hipStream_t stream) {
+    // > 64 KiB of dynamic LDS needs the attribute; it is per device and idempotent, so set it on every call
+    if (hipFuncSetAttribute((const void *)fbank_rows_kernel<ET, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024) != hipSuccess)
+        return PAFC_ERR_LAUNCH;
+    hipLaunchKernelGGL((fbank_rows_kernel<ET, STREAM>), dim3((unsigned)tiles, (unsigned)B), dim3(256), tile_lds_bytes(p.nmel),
+                       stream, p, r);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 
 }  // namespace
@@ -157,9 +273,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const FbankParams p) {
 
 extern "C" {
 
-long pafc_fbank_num_frames(long num_samples) {
-    return num_samples < pafc::WIN ? 0 : 1 + (num_samples - pafc::WIN) / pafc::SHIFT;
-}
+long pafc_fbank_num_frames(long num_samples) { return pafc::fbank_host::num_frames(num_samples); }
 
 int pafc_fbank_tables_cols(void) { return pafc::NCOL; }
 
@@ -172,15 +286,59 @@ int pafc_fbank_f32(const float *wave, long num_samples, const float *window, con
     if (m <= 0 || m > 0x7fffffffL) return PAFC_ERR_BAD_DIMS;
     pafc::FbankParams p{wave, num_samples, (int)m, window, dft_table, mel_weights, mel_lo, mel_hi, num_mel_bins,
                         noise, dither, preemph, out};
-    const size_t a_bytes = sizeof(float) * pafc::FPB * pafc::LDA;
-    const size_t po_bytes = sizeof(float) * (pafc::FPB * pafc::LDP + 64 + pafc::FPB * (num_mel_bins | 1));
-    const size_t lds = a_bytes > po_bytes ? a_bytes : po_bytes;
+    const size_t lds = pafc::tile_lds_bytes(num_mel_bins);
     // > 64 KiB of dynamic LDS needs the attribute; it is per device and idempotent, so set it on every call
     if (hipFuncSetAttribute((const void *)pafc::fbank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
         hipSuccess)
         return PAFC_ERR_LAUNCH;
     const unsigned blocks = (unsigned)((m + pafc::FPB - 1) / pafc::FPB);
     hipLaunchKernelGGL(pafc::fbank_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+int pafc_fbank_stream_plan(int c, long n, long *frames, int *c_next) {
+    return pafc::fbank_host::stream_plan(c, n, frames, c_next);
+}
+
+int pafc_fbank_batch(const float *waves, long ld_wave, const long *lengths, int B, long max_samples, const float *window,
+                     const float *dft_table, const float *mel_weights, const int *mel_lo, const int *mel_hi, int num_mel_bins,
+                     const float *noise, float dither, float preemph, void *out, int out_dtype, int *out_frames,
+                     pafc_stream_t stream) {
+    long t_max = 0;
+    const int rc = pafc::fbank_host::batch_check(waves, ld_wave, B, max_samples,
+                                                 pafc::fbank_host::tables_null(window, dft_table, mel_weights, mel_lo, mel_hi),
+                                                 num_mel_bins, out, out_dtype, &t_max);
+    if (rc != PAFC_OK) return rc;
+    pafc::FbankParams p{waves, max_samples, (int)t_max, window, dft_table, mel_weights, mel_lo, mel_hi, num_mel_bins,
+                        noise, dither, preemph, nullptr};
+    pafc::RowsParams r{nullptr, 0, ld_wave, lengths, max_samples, (int)t_max, out, t_max * num_mel_bins, 0, out_frames};
+    const long tiles = (t_max + pafc::FPB - 1) / pafc::FPB;
+    return out_dtype == PAFC_BF16 ? pafc::launch_rows<pafc::bf16_t, false>(p, r, tiles, B, (hipStream_t)stream)
+                                  : pafc::launch_rows<float, false>(p, r, tiles, B, (hipStream_t)stream);
+}
+
+int pafc_fbank_stream(float *carry, int c, const float *chunk, long ld_chunk, long n, int B, const float *window,
+                      const float *dft_table, const float *mel_weights, const int *mel_lo, const int *mel_hi, int num_mel_bins,
+                      float dither, float preemph, void *out, int out_dtype, long out_row_stride, long first_frame,
+                      pafc_stream_t stream) {
+    long frames = 0;
+    int c_next = 0;
+    int rc = pafc::fbank_host::stream_check(carry, c, chunk, ld_chunk, n, B,
+                                            pafc::fbank_host::tables_null(window, dft_table, mel_weights, mel_lo, mel_hi),
+                                            num_mel_bins, dither, out, out_dtype, out_row_stride, first_frame, &frames, &c_next);
+    if (rc != PAFC_OK || n == 0) return rc;
+    if (frames > 0) {
+        pafc::FbankParams p{chunk, c + n, (int)frames, window, dft_table, mel_weights, mel_lo, mel_hi, num_mel_bins,
+                            nullptr, 0.f, preemph, nullptr};
+        pafc::RowsParams r{carry, c, ld_chunk, nullptr, c + n, (int)frames, out, out_row_stride, first_frame * num_mel_bins,
+                           nullptr};
+        const long tiles = (frames + pafc::FPB - 1) / pafc::FPB;
+        rc = out_dtype == PAFC_BF16 ? pafc::launch_rows<pafc::bf16_t, true>(p, r, tiles, B, (hipStream_t)stream)
+                                    : pafc::launch_rows<float, true>(p, r, tiles, B, (hipStream_t)stream);
+        if (rc != PAFC_OK) return rc;
+    }
+    hipLaunchKernelGGL(pafc::fbank_carry_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, carry, c, chunk, ld_chunk,
+                       n, c_next);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 

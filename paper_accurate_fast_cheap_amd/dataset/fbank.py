@@ -9,13 +9,17 @@ returns the same (frames, num_mel_bins) float32 tensor -- on the device the wave
 The constant tables (povey window, DFT matrix, mel filters) are built once per device in float64 / float32 on
 the host exactly as torchaudio builds them and handed to the kernel; the library itself keeps no state."""
 import math
-from typing import Dict, Optional, Tuple
+from ctypes import byref, c_int, c_long
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from .. import _lib
 
 _tables: Dict[Tuple[str, int], dict] = {}
+_FIXED = ("fbank kernel is built for the reference's configuration: 25 ms / 10 ms frames at 16 kHz, energy_floor 0 "
+          "(processor.py:363-369)")
+CARRY = 560          # row length of a stream's carry (a row never holds more than 400 + 160 - 1 samples)
 
 
 def mel_banks(num_bins: int, padded: int = 512, sample_freq: float = 16000.0, low_freq: float = 20.0) -> torch.Tensor:
@@ -67,8 +71,7 @@ def fbank(waveform: torch.Tensor, num_mel_bins: int = 23, frame_length: float = 
     channel=-1 -> first channel); returns (frames, num_mel_bins) float32.  dither != 0 draws standard-normal noise
     per frame sample on the device (or uses `noise` (frames, 400) if given)."""
     if (frame_length, frame_shift, sample_frequency, energy_floor) != (25.0, 10.0, 16000.0, 0.0):
-        raise _lib.PafcError("fbank kernel is built for the reference's configuration: 25 ms / 10 ms frames at "
-                             "16 kHz, energy_floor 0 (processor.py:363-369)")
+        raise _lib.PafcError(_FIXED)
     if waveform.dim() != 2:
         raise _lib.PafcError("waveform must be (channels, samples)")
     _lib.require_gpu(waveform)
@@ -92,6 +95,140 @@ def fbank(waveform: torch.Tensor, num_mel_bins: int = 23, frame_length: float = 
                           _lib.stream_of(wave))
     _lib.check(rc, "pafc_fbank_f32")
     return out
+
+
+def _rows(x: torch.Tensor, what: str) -> torch.Tensor:
+    """A (B, n) float32 GPU tensor whose rows the kernel can read where they lie: unit inner stride, any row stride >= n."""
+    if x.dim() != 2:
+        raise _lib.PafcError(f"{what} must be (batch, samples)")
+    if not x.is_cuda:
+        raise _lib.PafcError("this op runs on the MI355X only (tensor is on %s); there is no CPU fallback" % x.device)
+    if x.dtype != torch.float32:
+        raise _lib.PafcError(f"{what} must be float32, got {x.dtype}")
+    if x.size(1) > 1 and x.stride(1) != 1 or x.size(0) > 1 and x.stride(0) < x.size(1):
+        raise _lib.PafcError(f"{what}: rows must have unit inner stride and must not overlap (strides {tuple(x.stride())})")
+    return x
+
+
+def _ld(x: torch.Tensor) -> int:
+    return x.stride(0) if x.size(0) > 1 else max(x.size(1), 1)
+
+
+def fbank_batch(waveforms: torch.Tensor, lengths: Union[None, torch.Tensor, Sequence[int]] = None, num_mel_bins: int = 80,
+                dither: float = 0.0, noise: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32,
+                frame_length: float = 25.0, frame_shift: float = 10.0, energy_floor: float = 0.0,
+                sample_frequency: float = 16000.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fbank() of B utterances in ONE launch.  waveforms: (B, S_max) float32 in int16 range on the GPU, row b holding its
+    utterance in its first lengths[b] samples (rows may be a view with unit inner stride: a slice of a wider buffer);
+    lengths: int64 device tensor (B) or a Python list (copied to the device once), None = every row is S_max long.
+    Returns (feats (B, T_max, num_mel_bins) in out_dtype -- float32 or bfloat16 = the float32 value rounded to nearest even --,
+    feat_lengths (B) int32 on the device): row b's first feat_lengths[b] frames are bit for bit fbank() of its utterance, every
+    frame behind them is 0.  dither != 0 draws (or takes as `noise`) standard-normal noise (B, T_max, 400).  Nothing here waits
+    for the device."""
+    if (frame_length, frame_shift, sample_frequency, energy_floor) != (25.0, 10.0, 16000.0, 0.0):
+        raise _lib.PafcError(_FIXED)
+    wave = _rows(waveforms, "waveforms")
+    code = _lib.dtype_code(out_dtype)
+    L = _lib.lib()
+    B, S = wave.shape
+    dev = wave.device
+    T = L.pafc_fbank_num_frames(S)
+    if lengths is not None:
+        if not torch.is_tensor(lengths):
+            lengths = torch.tensor([int(v) for v in lengths], dtype=torch.int64).to(dev)
+        if lengths.dtype != torch.int64 or lengths.shape != (B,):
+            raise _lib.PafcError(f"lengths must be int64 ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+        _lib.require_gpu(lengths)
+    out = torch.empty((B, T, num_mel_bins), dtype=out_dtype, device=dev)
+    out_len = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B == 0 or T == 0:
+        return out, out_len.zero_()
+    if dither != 0.0 and noise is None:
+        noise = torch.randn((B, T, 400), dtype=torch.float32, device=dev)
+    if noise is not None:
+        _lib.require_gpu(noise)
+        if noise.shape != (B, T, 400) or noise.dtype != torch.float32:
+            raise _lib.PafcError(f"noise must be float32 ({B}, {T}, 400)")
+    t = _get_tables(dev, num_mel_bins)
+    rc = L.pafc_fbank_batch(_lib.ptr(wave), _ld(wave), _lib.ptr(lengths), B, S, _lib.ptr(t["window"]), _lib.ptr(t["dft"]),
+                            _lib.ptr(t["melw"]), _lib.ptr(t["lo"]), _lib.ptr(t["hi"]), num_mel_bins,
+                            _lib.ptr(noise if dither != 0.0 else None), float(dither), 0.97, _lib.ptr(out), code,
+                            _lib.ptr(out_len), _lib.stream_of(wave))
+    _lib.check(rc, "pafc_fbank_batch")
+    return out, out_len
+
+
+def stream_plan(carry_len: int, n: int) -> Tuple[int, int]:
+    """(frames completed, samples carried on) when n samples arrive behind carry_len carried ones: pafc_fbank_stream_plan."""
+    frames, c_next = c_long(0), c_int(0)
+    _lib.check(_lib.lib().pafc_fbank_stream_plan(int(carry_len), int(n), byref(frames), byref(c_next)), "pafc_fbank_stream_plan")
+    return frames.value, c_next.value
+
+
+class FbankStreamer:
+    """fbank of `batch_size` lock-step streams fed packet by packet.  feed(chunk (B, n)) returns the (B, f, num_mel_bins) frames
+    this packet completed (f may be 0) and keeps, on the device, the samples a later frame still needs (`carry_len` of them,
+    < 560).  For any cut of a stream into feeds the concatenated frames are bit for bit fbank_batch of the whole stream.
+    feed_into(chunk, out, first_frame) writes the frames at out[:, first_frame:first_frame + f] instead (out: (B, >= first_frame
+    + f, num_mel_bins) in out_dtype with contiguous frames; rows may be strided) and returns f.  A feed is two launches and no
+    wait, and can be captured.  reset() starts new streams.  Dither is not offered on a stream."""
+
+    def __init__(self, batch_size: int, num_mel_bins: int = 80, out_dtype: torch.dtype = torch.float32, device="cuda",
+                 dither: float = 0.0):
+        if dither != 0.0:
+            raise _lib.PafcError("FbankStreamer: dither is not offered on a stream (dither must be 0)")
+        if batch_size < 1:
+            raise _lib.PafcError("FbankStreamer: batch_size must be >= 1")
+        self.B, self.nmel, self.out_dtype = batch_size, num_mel_bins, out_dtype
+        self._code = _lib.dtype_code(out_dtype)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.PafcError("this op runs on the MI355X only (device is %s); there is no CPU fallback" % self.device)
+        self._L = _lib.lib()
+        self._t = _get_tables(self.device, num_mel_bins)
+        self._carry = torch.zeros((batch_size, CARRY), dtype=torch.float32, device=self.device)
+        self.carry_len = 0
+        self.frames_emitted = 0
+
+    def reset(self):
+        self.carry_len = 0
+        self.frames_emitted = 0
+
+    def _check(self, chunk: torch.Tensor) -> Tuple[int, int]:
+        chunk = _rows(chunk, "chunk")
+        if chunk.size(0) != self.B or chunk.device != self._carry.device:
+            raise _lib.PafcError(f"FbankStreamer.feed: the chunk must be ({self.B}, n) on {self._carry.device}")
+        return stream_plan(self.carry_len, chunk.size(1))
+
+    def feed_into(self, chunk: torch.Tensor, out: Optional[torch.Tensor], first_frame: int = 0, _plan=None) -> int:
+        frames, c_next = _plan or self._check(chunk)
+        n = chunk.size(1)
+        if n == 0:
+            return 0
+        stride = 0
+        if frames > 0:
+            if (out is None or out.dim() != 3 or out.size(0) != self.B or out.size(2) != self.nmel or out.dtype != self.out_dtype
+                    or out.device != chunk.device or first_frame < 0 or out.size(1) < first_frame + frames):
+                raise _lib.PafcError(f"FbankStreamer.feed_into: out must be {self.out_dtype} ({self.B}, >= {first_frame + frames}, "
+                                     f"{self.nmel}) on {chunk.device}")
+            if out.stride(2) != 1 or out.stride(1) != self.nmel or (self.B > 1 and out.stride(0) < out.size(1) * self.nmel):
+                raise _lib.PafcError("FbankStreamer.feed_into: the frames of a row of out must be contiguous")
+            stride = out.stride(0) if self.B > 1 else out.size(1) * self.nmel
+        t = self._t
+        rc = self._L.pafc_fbank_stream(_lib.ptr(self._carry), self.carry_len, _lib.ptr(chunk), _ld(chunk), n, self.B,
+                                       _lib.ptr(t["window"]), _lib.ptr(t["dft"]), _lib.ptr(t["melw"]), _lib.ptr(t["lo"]),
+                                       _lib.ptr(t["hi"]), self.nmel, 0.0, 0.97, _lib.ptr(out if frames > 0 else None), self._code,
+                                       stride, first_frame, _lib.stream_of(chunk))
+        _lib.check(rc, "pafc_fbank_stream")
+        self.carry_len = c_next
+        self.frames_emitted += frames
+        return frames
+
+    def feed(self, chunk: torch.Tensor) -> torch.Tensor:
+        plan = self._check(chunk)
+        out = torch.empty((self.B, plan[0], self.nmel), dtype=self.out_dtype, device=self._carry.device)
+        self.feed_into(chunk, out, 0, plan)
+        return out
 
 
 def compute_fbank(sample: dict, num_mel_bins: int = 23, frame_length: int = 25, frame_shift: int = 10,

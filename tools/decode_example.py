@@ -7,9 +7,10 @@ chain and its interfaces -- pass --checkpoint / --config of a real GigaSpeech mo
                                  [--mode ctc_prefix_beam_search --context_list_path hotwords.txt --context_graph_score 3.0]
                                  [--stream 16]
 
---stream CHUNK decodes one utterance as a stream instead (ASRModel.stream_ctc_search): the default model becomes the
-uni-directional encoder with a causal conv module, the encoder runs window by window with carried state, every CHUNK
-output frames go through the streaming CTC search, and the committed text -- the tokens that can no longer change --
+--stream CHUNK decodes one utterance as a stream instead, from its AUDIO (utils.audio_stream.AudioStreamer): the default
+model becomes the uni-directional encoder with a causal conv module, the waveform arrives in packets of 0.64 s, the streaming
+fbank turns them into frames, the encoder runs window by window with carried state as soon as a window's frames exist, every
+CHUNK output frames go through the streaming CTC search, and the committed text -- the tokens that can no longer change --
 is printed as it grows, followed by the final result.
 """
 import argparse, io, os, sys
@@ -17,7 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench as B                                                                  # noqa: E402
-from paper_accurate_fast_cheap_amd.dataset.fbank import fbank                       # noqa: E402
+from paper_accurate_fast_cheap_amd.dataset.fbank import fbank_batch                 # noqa: E402
 from paper_accurate_fast_cheap_amd.scoring.wer import WerScorer, giga_post_process  # noqa: E402
 from paper_accurate_fast_cheap_amd.text import RevBpeTokenizer                      # noqa: E402
 from paper_accurate_fast_cheap_amd.utils.init_model import init_model               # noqa: E402
@@ -57,18 +58,19 @@ def main(argv=None):
     # three synthetic "utterances" (2.5 s, 4 s, 1.2 s) and made-up reference transcripts
     waves = [B.synthetic_waveform(s, 10 + i).to(dev) for i, s in enumerate((2.5, 4.0, 1.2))]
     refs = ["THE STATE-OF-THE-ART", "IT'S UH E-COMMERCE <COMMA> OKAY", "HELLO"]
-    feats = [fbank(w, num_mel_bins=80, frame_length=25.0, frame_shift=10.0, dither=0.0, energy_floor=0.0,
-                   sample_frequency=16000.0) for w in waves]
-    lens = torch.tensor([f.shape[0] for f in feats], device=dev)
-    batch = torch.zeros(len(feats), int(lens.max()), 80, dtype=torch.bfloat16, device=dev)
-    for i, f in enumerate(feats):
-        batch[i, :f.shape[0]] = f.to(torch.bfloat16)
+    samples = [w.shape[1] for w in waves]
+    padded = torch.zeros(len(waves), max(samples), device=dev)
+    for i, w in enumerate(waves):
+        padded[i, :samples[i]] = w[0]
     context_graph = None
     if args.context_list_path:
         from paper_accurate_fast_cheap_amd.utils.context_graph import ContextGraph
         context_graph = ContextGraph(args.context_list_path, tok.symbol_table, args.bpe_model, args.context_graph_score)
     if args.stream:
-        return stream_one(model, tok, batch[1:2, :int(lens[1])], args, context_graph)
+        return stream_one(model, tok, waves[1], args, context_graph)
+    # one launch for the whole batch: (B, T_max, 80) bf16, zero behind every utterance's frames, and the frame counts
+    batch, lens = fbank_batch(padded, samples, num_mel_bins=80, dither=0.0, out_dtype=torch.bfloat16)
+    lens = lens.to(torch.int64)
     with torch.no_grad():
         results = model.decode([args.mode], batch, lens, beam_size=args.beam_size,
                                context_graph=context_graph)[args.mode]
@@ -86,7 +88,11 @@ def main(argv=None):
     return results
 
 
-def stream_one(model, tok, speech, args, context_graph):
+PACKET = 10240     # 0.64 s of audio per feed
+
+
+def stream_one(model, tok, wave, args, context_graph):
+    from paper_accurate_fast_cheap_amd.utils.audio_stream import AudioStreamer
     shown = [0]
 
     def on_partial(i, partial, committed):
@@ -95,9 +101,11 @@ def stream_one(model, tok, speech, args, context_graph):
             print(f"window {i:3d}: committed {shown[0]:3d} tokens -> {tok.detokenize(committed[0])[0][-60:]!r}"
                   f"   (1-best now {len(partial[0].tokens)} tokens)")
 
-    with torch.no_grad():
-        results = model.stream_ctc_search(speech, args.stream, mode=args.mode, beam_size=args.beam_size,
-                                          context_graph=context_graph, on_partial=on_partial)
+    streamer = AudioStreamer(model, 1, args.stream, args.mode, beam_size=args.beam_size, context_graph=context_graph,
+                             on_partial=on_partial, max_total_frames=wave.shape[1] // 640 + args.stream)
+    for a in range(0, wave.shape[1], PACKET):
+        streamer.feed(wave[:, a:a + PACKET])
+    results = streamer.finish()
     r = results[0]
     print(f"final: {len(r.tokens)} tokens -> {tok.detokenize(list(r.tokens))[0][:60]!r}")
     if r.times is not None:
