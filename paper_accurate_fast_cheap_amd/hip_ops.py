@@ -1314,6 +1314,22 @@ def _greedy_net(predictor, joint):
     return net, keep
 
 
+def _enc_ffn(joint, as_is: bool = False):
+    """joint.enc_ffn's (weight, bias), detached and contiguous (as_is: detached only, strides as the module holds them)."""
+    ef, fix = joint.enc_ffn, (torch.Tensor.detach if as_is else lambda t: t.detach().contiguous())
+    return fix(ef.weight), None if ef.bias is None else fix(ef.bias)
+
+
+def _enc_project(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """E = enc_ffn(x) for rows x (rows, D) through gemm_f32 / gemm_bf16 by the weight's dtype, (w, b) from _enc_ffn."""
+    return (gemm_f32 if w.dtype == torch.float32 else gemm_bf16)(x, w, b, out=out)
+
+
+def _shape_like(B: int, T: int, D: int, device) -> torch.Tensor:
+    """An expanded view of one element: what the *_unmet checks read of a (B, T, D) buffer, without allocating it."""
+    return torch.empty(1, 1, 1, device=device).expand(B, T, D)
+
+
 def rnnt_greedy_unmet(predictor, joint, encoder_out: torch.Tensor, n_steps: int = 64) -> Optional[str]:
     """The condition the greedy-search kernels (csrc/rnnt_greedy.hip) do not meet for this predictor / joint / encoder output,
     or None.  The kernels take the paper's modules: an LSTM predictor with its projection, a joint with pre-join projections,
@@ -1382,11 +1398,7 @@ def rnnt_greedy_search(predictor, joint, encoder_out: torch.Tensor, encoder_out_
     dev = encoder_out.device
     wdt = joint.ffn_out.weight.dtype
     x = encoder_out.detach().to(wdt).reshape(B * T, D).contiguous()
-    ef = joint.enc_ffn
-    if wdt == torch.float32:
-        E = gemm_f32(x, ef.weight.detach(), None if ef.bias is None else ef.bias.detach())
-    else:
-        E = gemm_bf16(x, ef.weight.detach().contiguous(), None if ef.bias is None else ef.bias.detach().contiguous())
+    E = _enc_project(x, *_enc_ffn(joint, as_is=wdt == torch.float32))      # (the fp32 GEMM takes the weight's own strides)
     lens = encoder_out_lens.detach().to(device=dev, dtype=torch.int64).contiguous()
     if lens.shape != (B,):
         raise _lib.PafcError("rnnt_greedy_search: encoder_out_lens must be (B,)")
@@ -1431,9 +1443,7 @@ def rnnt_greedy_stream_unmet(predictor, joint, B: int, Tmax: int, D: int, device
         return f"Tmax {Tmax}: a chunk must hold at least one frame"
     if B < 1:
         return f"{B} streams: at least one"
-    # (an expanded view of one element: the shape, dtype and device of the chunk buffer without allocating it)
-    like = torch.empty(1, 1, 1, device=device).expand(B, Tmax, D)
-    return rnnt_greedy_unmet(predictor, joint, like, n_steps)
+    return rnnt_greedy_unmet(predictor, joint, _shape_like(B, Tmax, D, device), n_steps)
 
 
 class RnntGreedyStream(_RowStream):
@@ -1464,9 +1474,7 @@ class RnntGreedyStream(_RowStream):
         self.Tmax, self.D, self.n_steps, self.blank, self.chunk = Tmax, D, n_steps, int(blank), chunk
         self.use_graph = use_graph
         self.dtype = joint.ffn_out.weight.dtype
-        ef = joint.enc_ffn
-        self._w = ef.weight.detach().contiguous()
-        self._b = None if ef.bias is None else ef.bias.detach().contiguous()
+        self._w, self._b = _enc_ffn(joint)
         J = joint.ffn_out.in_features
         self._net, self._keep = _greedy_net(predictor, joint)
         self._pnet = ctypes.byref(self._net)
@@ -1489,12 +1497,6 @@ class RnntGreedyStream(_RowStream):
         _lib.check(self._L.pafc_rnnt_greedy_stream_reset(self._pnet, self.B, self.Tmax, self.n_steps, self.blank, mask,
                                                           _lib.ptr(self._ws), self._nbytes, st), "pafc_rnnt_greedy_stream_reset")
 
-    def _project(self):
-        if self.dtype == torch.float32:
-            gemm_f32(self._x, self._w, self._b, out=self._E)
-        else:
-            gemm_bf16(self._x, self._w, self._b, out=self._E)
-
     def _step(self, st):
         _lib.check(self._L.pafc_rnnt_greedy_step(self._pnet, self.B, self.Tmax, self.n_steps, self.blank, _lib.ptr(self._E),
                                                  _lib.ptr(self._ws), self._nbytes, _lib.ptr(self._running), st),
@@ -1503,7 +1505,7 @@ class RnntGreedyStream(_RowStream):
     def _fixed(self, n):
         """The fixed part of a feed of n frames: E projection, feed kernel, n steps."""
         st = _lib.stream_of(self._ws)
-        self._project()
+        _enc_project(self._x, self._w, self._b, out=self._E)
         _lib.check(self._L.pafc_rnnt_greedy_stream_feed(self._pnet, self.B, self.Tmax, self.n_steps, self.blank,
                                                          _lib.ptr(self._nf), _lib.ptr(self._ws), self._nbytes,
                                                          _lib.ptr(self._running), st), "pafc_rnnt_greedy_stream_feed")
@@ -2920,9 +2922,7 @@ class RnntBeamBody:
         self._nbytes = self._L.pafc_rnnt_beam_body_workspace_bytes(self._pnet, B, beam)
         if self._nbytes == 0:
             raise _lib.PafcError("pafc_rnnt_beam_body_workspace_bytes: unsupported dimensions")
-        ef = joint.enc_ffn
-        self._w = ef.weight.detach().contiguous()
-        self._b = None if ef.bias is None else ef.bias.detach().contiguous()
+        self._w, self._b = _enc_ffn(joint)
         self.layers, self.hidden, self.join_dim = predictor.rnn.num_layers, predictor.rnn.hidden_size, joint.ffn_out.in_features
         self.vocab = joint.ffn_out.out_features
         self._ws = torch.empty(self._nbytes, dtype=torch.uint8, device=dev)
@@ -2937,7 +2937,7 @@ class RnntBeamBody:
 
     def project(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """E = enc_ffn(x) for rows x (rows, D) through gemm_f32 / gemm_bf16, as rnnt_greedy_search computes it."""
-        return (gemm_f32 if self.dtype == torch.float32 else gemm_bf16)(x, self._w, self._b, out=out)
+        return _enc_project(x, self._w, self._b, out=out)
 
     def frame(self, E: torch.Tensor, ctc: torch.Tensor, w_rnnt: float, w_ctc: float, last_tok: torch.Tensor, h: torch.Tensor,
               c: torch.Tensor, t: int = 0, t_dev: Optional[torch.Tensor] = None):
@@ -2977,8 +2977,8 @@ def rnnt_beam_frame(predictor, joint, E: torch.Tensor, ctc: torch.Tensor, last_t
     """One frame of the frame-body kernels on explicit tensors (tests and tools): E (B, T, J) = enc_ffn(encoder_out), ctc
     (B, T, V) log-probabilities, last_tok (B * beam), h / c (layers, B * beam, hidden).  Returns (top_val, top_idx, h_new,
     c_new), top_* of (B, beam, beam)."""
-    unmet = rnnt_beam_body_unmet(predictor, joint, torch.empty(1, 1, 1, device=E.device).expand(
-        E.shape[0], E.shape[1], joint.enc_ffn.in_features if getattr(joint, "enc_ffn", None) is not None else 4), beam)
+    D = joint.enc_ffn.in_features if getattr(joint, "enc_ffn", None) is not None else 4
+    unmet = rnnt_beam_body_unmet(predictor, joint, _shape_like(E.shape[0], E.shape[1], D, E.device), beam)
     if unmet is not None:
         raise _lib.PafcError(f"rnnt_beam_frame: {unmet}")
     body = RnntBeamBody(predictor, joint, E.shape[0], beam)

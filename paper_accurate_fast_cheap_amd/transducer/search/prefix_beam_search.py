@@ -41,6 +41,76 @@ class Sequence:
         self.cache = cache   # column of the batched state tensors that holds this beam's LSTM state
 
 
+def _result(nbest: List[List[int]], scores: List[float]) -> DecodeResult:
+    """The DecodeResult of an n-best list in descending score order (empty: a row that holds no hypothesis yet)."""
+    if not nbest:
+        return DecodeResult(tokens=[], score=0.0, nbest=[], nbest_scores=[])
+    return DecodeResult(tokens=nbest[0], score=scores[0], nbest=nbest, nbest_scores=scores)
+
+
+class _ResidentFrames:
+    """The frame of the device-resident search over B x beam fixed slots, with its warm-up, capture and replay: what the
+    offline decode (over the caller's tensors) and BeamStreamer (over its staging buffers) both run.  Every tensor a frame
+    touches has a fixed address and shape and the frame index lives on the device (t_dev), so the frame is captured once and
+    replayed.  slots: hip_ops.RnntBeamState or RnntBeamStream; step(top_val, top_idx, t_dev): the caller's bound step call;
+    src (B, T, D): the encoder rows -- with `body` (hip_ops.RnntBeamBody: the frame as the library's kernels) E = enc_ffn
+    rows (B, T, J) --, ctc (B, T, V); a frame reads row min(t_dev, T - 1) of both.  cache: the LSTM state [h, c], updated in
+    place.  chain_select: the framework body selects the state with the framework chain, not pafc_rnnt_beam_select_state.
+    The object is in no reference cycle (it stores no bound method of its own), so it dies -- and its hipGraph with it -- when
+    its owner drops it, never in a later garbage collection, which could run inside somebody else's stream capture."""
+
+    def __init__(self, bs, slots, step, src, ctc, cache, w_rnnt: float, w_ctc: float, body=None, chain_select: bool = False):
+        from ...hip_ops import rnnt_beam_select_state
+        self.bs, self.slots, self.step, self.src, self.ctc, self.cache, self.body = bs, slots, step, src, ctc, cache, body
+        self.w_rnnt, self.w_ctc, self.chain_select, self._select = w_rnnt, w_ctc, chain_select, rnnt_beam_select_state
+        self.device = src.device
+        self.t_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.graph = False                                 # False: no capture tried; None: the capture was refused
+
+    def frame(self):
+        """One frame for all slots: the kernels body when the engine was given one, else the framework body."""
+        if self.body is None:
+            return self._frame_framework()
+        st, body, (h, c), t_dev = self.slots, self.body, self.cache, self.t_dev
+        body.frame(self.src, self.ctc, self.w_rnnt, self.w_ctc, st.last_tok, h, c, t_dev=t_dev)
+        self.step(body.top_val, body.top_idx, t_dev)
+        self._select(h, c, body.h_new, body.c_new, st.next_idx, st.B, st.beam)
+        body.advance(t_dev)
+
+    def _frame_framework(self):
+        st, cache, t_dev, beam, last = self.slots, self.cache, self.t_dev, self.slots.beam, self.src.shape[1] - 1
+        enc = self.src.index_select(1, t_dev.clamp(max=last)).squeeze(1)
+        enc = enc.repeat_interleave(beam, dim=0).unsqueeze(1)                                    # (n, 1, D)
+        logp, new_cache = self.bs.forward_decoder_one_step(enc, st.last_tok, cache)
+        logp = logp.squeeze(1).squeeze(1)                                                        # (n, V)
+        ctc_t = self.ctc.index_select(1, t_dev.clamp(max=last)).squeeze(1).repeat_interleave(beam, dim=0)
+        logp = torch.log(torch.add(self.w_rnnt * torch.exp(logp), self.w_ctc * torch.exp(ctc_t)))
+        top_val, top_idx = logp.topk(beam)
+        self.step(top_val.float().contiguous(), top_idx.contiguous(), t_dev)
+        if self.chain_select:
+            cache[0].copy_(torch.cat([cache[0], new_cache[0]], dim=1).index_select(1, st.next_idx))
+            cache[1].copy_(torch.cat([cache[1], new_cache[1]], dim=1).index_select(1, st.next_idx))
+        else:
+            self._select(cache[0], cache[1], new_cache[0].contiguous(), new_cache[1].contiguous(), st.next_idx, st.B, st.beam)
+        t_dev.add_(1)
+
+    def capture(self):
+        """Two eager frames on the side stream (they warm every library handle), then the frame captured into a hipGraph.
+        Only a REFUSED capture (an operation the stream capture does not permit in this build) leaves None -- nothing ran
+        during it, so t_dev stands behind the two warm-up frames and run() goes on eagerly; a failing launch or a PafcError
+        inside the frame is a real error and surfaces."""
+        graph_step.on_side_stream(self.device, lambda: (self.frame(), self.frame()))
+        self.graph = graph_step.capture(self.frame, self.device)[0]
+
+    def run(self, k: int):
+        """k frames: replays of the captured graph (their errors are genuine kernel / launch errors: not swallowed), else eager."""
+        for _ in range(k):
+            if self.graph:
+                self.graph.replay()
+            else:
+                self.frame()
+
+
 class PrefixBeamSearch:
     def __init__(self, encoder, predictor, joint, ctc, blank):
         self.encoder = encoder
@@ -101,42 +171,36 @@ class PrefixBeamSearch:
             active = [i for i in range(B) if t < lens[i]]
             if not active:
                 break
-            rows, toks, cols, scores = [], [], [], []
-            for i in active:
-                for s in beams[i]:
-                    rows.append(i)
-                    toks.append(s.hyp[-1])
-                    cols.append(s.cache)
-                    scores.append(s.score)
-            n = len(rows)
-            rows_t = torch.tensor(rows, device=device)
-            cols_t = torch.tensor(cols, device=device)
+            live = [s for i in active for s in beams[i]]
+            n = len(live)
+            rows_t = torch.tensor([i for i in active for _ in beams[i]], device=device)
+            cols_t = torch.tensor([s.cache for s in live], device=device)
             cache = [state[0].index_select(1, cols_t), state[1].index_select(1, cols_t)]
-            enc = encoder_outs[rows_t, t, :].unsqueeze(1)                                  # (n, 1, D)
-            logp, new_cache = self.forward_decoder_one_step(enc, torch.tensor(toks, device=device), cache)
-            logp = logp.squeeze(1).squeeze(1)                                              # (n, V)
-            logp = torch.log(torch.add(transducer_weight * torch.exp(logp),
-                                       ctc_weight * torch.exp(ctc_probs[rows_t, t, :])))
-            top_k_logp, top_k_index = logp.topk(beam_size)                                 # (n, beam)
-            cand = torch.tensor(scores, device=device).unsqueeze(1) + top_k_logp          # float32, as the reference
-            packed = torch.cat([cand.float(), top_k_index.float()], dim=1).cpu()           # ONE device->host copy
-            cand_h = packed[:, :beam_size]
-            idx_h = packed[:, beam_size:].to(torch.int64)
-            # next frame's state pool: old states (kept by blank extensions) then new states
-            state = [torch.cat([cache[0], new_cache[0]], dim=1), torch.cat([cache[1], new_cache[1]], dim=1)]
-
+            cand_h, idx_h, state = self._host_frame(encoder_outs, ctc_probs, rows_t, t, live, cache, transducer_weight,
+                                                    ctc_weight, beam_size)
             cur = 0
             for i in active:
                 nb = len(beams[i])
                 beams[i] = self._walk_row(beams[i], cand_h[cur:cur + nb], idx_h[cur:cur + nb], cur, n, beam_size)
                 cur += nb
 
-        results = []
-        for bs in beams:
-            nbest = [b.hyp[1:] for b in bs]
-            nbest_scores = [b.score for b in bs]
-            results.append(DecodeResult(tokens=nbest[0], score=nbest_scores[0], nbest=nbest, nbest_scores=nbest_scores))
-        return results
+        return [_result([b.hyp[1:] for b in bs], [b.score for b in bs]) for bs in beams]
+
+    def _host_frame(self, enc, ctc, rows_t, t: int, live: List[Sequence], cache, w_rnnt: float, w_ctc: float, beam_size: int):
+        """Frame t of the host loops for the n live beams of the active rows: enc (B, T, D) and ctc (B, T, V), rows_t (n) each
+        beam's utterance, cache its LSTM state ((layers, n, H) twice).  Returns the candidates' scores and tokens on the host,
+        (n, beam_size) each, and next frame's state pool (layers, 2 n, H): old states (kept by blank extensions) then new
+        states.  The rows are gathered here, each where it is used, so that the launches keep the order they always had."""
+        device = enc.device
+        enc_rows = enc[rows_t, t, :].unsqueeze(1)                                          # (n, 1, D)
+        logp, new_cache = self.forward_decoder_one_step(enc_rows, torch.tensor([s.hyp[-1] for s in live], device=device), cache)
+        logp = logp.squeeze(1).squeeze(1)                                                  # (n, V)
+        logp = torch.log(torch.add(w_rnnt * torch.exp(logp), w_ctc * torch.exp(ctc[rows_t, t, :])))
+        top_k_logp, top_k_index = logp.topk(beam_size)                                     # (n, beam)
+        cand = torch.tensor([s.score for s in live], device=device).unsqueeze(1) + top_k_logp   # float32, as the reference
+        packed = torch.cat([cand.float(), top_k_index.float()], dim=1).cpu()               # ONE device->host copy
+        pool = [torch.cat([cache[0], new_cache[0]], dim=1), torch.cat([cache[1], new_cache[1]], dim=1)]
+        return packed[:, :beam_size], packed[:, beam_size:].to(torch.int64), pool
 
     def _walk_row(self, beam: List[Sequence], cand_h: torch.Tensor, idx_h: torch.Tensor, cur: int, n: int,
                   beam_size: int) -> List[Sequence]:
@@ -181,42 +245,20 @@ class PrefixBeamSearch:
         st = RnntBeamState(B, T, beam_size, self.blank, device)
         state = self.predictor.init_state(n, method="zero", device=device)
         cache = [s.to(encoder_outs.dtype).contiguous() for s in state]        # static buffers, updated in place
-        t_dev = torch.zeros(1, dtype=torch.int64, device=device)
-        ctc_probs = ctc_probs.contiguous()
-
-        def frame():
-            # one frame for all B x beam slots; every tensor it touches has a fixed address and shape, and the frame
-            # index lives on the device (t_dev), so the body can be captured once and replayed
-            enc = encoder_outs.index_select(1, t_dev.clamp(max=T - 1)).squeeze(1)
-            enc = enc.repeat_interleave(beam_size, dim=0).unsqueeze(1)                              # (n, 1, D)
-            logp, new_cache = self.forward_decoder_one_step(enc, st.last_tok, cache)
-            logp = logp.squeeze(1).squeeze(1)                                                        # (n, V)
-            ctc_t = ctc_probs.index_select(1, t_dev.clamp(max=T - 1)).squeeze(1).repeat_interleave(beam_size, dim=0)
-            logp = torch.log(torch.add(transducer_weight * torch.exp(logp), ctc_weight * torch.exp(ctc_t)))
-            top_val, top_idx = logp.topk(beam_size)
-            st.step(0, lens64, top_val.float().contiguous(), top_idx.contiguous(), t_dev=t_dev)
-            cache[0].copy_(torch.cat([cache[0], new_cache[0]], dim=1).index_select(1, st.next_idx))
-            cache[1].copy_(torch.cat([cache[1], new_cache[1]], dim=1).index_select(1, st.next_idx))
-            t_dev.add_(1)
-
+        eng = _ResidentFrames(self, st, lambda tv, ti, t_dev: st.step(0, lens64, tv, ti, t_dev=t_dev), encoder_outs,
+                              ctc_probs.contiguous(), cache, transducer_weight, ctc_weight, chain_select=True)
         done = 0
         if self.use_graph and T >= 8:
-            # launch-bound loop (~25 small kernels per frame): two eager frames warm every library handle, then the
-            # body is captured into a hipGraph and replayed for the remaining frames.  MIOpen's RNN call is not
-            # capturable (it sizes its workspace inside the call), so the LSTM runs through the framework's own cell.
+            # launch-bound loop (~25 small kernels per frame): the two warm-up frames are frames 0 and 1, the captured body
+            # is replayed for the remaining ones.  MIOpen's RNN call is not capturable (it sizes its workspace inside the
+            # call), so the LSTM runs through the framework's own cell.  After a refused capture the rest runs eagerly.
             with torch.backends.cudnn.flags(enabled=False):
-                graph_step.on_side_stream(device, lambda: (frame(), frame()))
+                eng.capture()
                 done = 2
-                # only a REFUSED capture (an operation the stream capture does not permit in this build) finishes eagerly --
-                # nothing ran during the failed capture, so t_dev still stands behind the two warm-up frames; a failing
-                # launch or a PafcError inside the frame is a real error and surfaces
-                graph = graph_step.capture(frame, device)[0]
-                if graph is not None:          # errors of the replays are genuine kernel / launch errors: not swallowed
-                    for _ in range(T - done):
-                        graph.replay()
+                if eng.graph is not None:
+                    eng.run(T - done)
                     done = T
-        for _ in range(T - done):
-            frame()
+        eng.run(T - done)
         return self._nbest(st, B, beam_size)
 
     @staticmethod
@@ -226,12 +268,8 @@ class PrefixBeamSearch:
         lens_h, scores_h = lens_n.tolist(), scores.tolist()
         maxlen = max(1, int(lens_n.max()))
         toks_h = toks[:, :, :maxlen].tolist()
-        results = []
-        for b in range(B):
-            nbest = [toks_h[b][k][:lens_h[b][k]] for k in range(beam_size) if lens_h[b][k] >= 0]
-            nsc = [scores_h[b][k] for k in range(beam_size) if lens_h[b][k] >= 0]
-            results.append(DecodeResult(tokens=nbest[0], score=nsc[0], nbest=nbest, nbest_scores=nsc))
-        return results
+        used = [[k for k in range(beam_size) if lens_h[b][k] >= 0] for b in range(B)]
+        return [_result([toks_h[b][k][:lens_h[b][k]] for k in used[b]], [scores_h[b][k] for k in used[b]]) for b in range(B)]
 
     @torch.no_grad()
     def _decode_batch_kernels(self, encoder_outs, encoder_lens, ctc_probs, beam_size: int, ctc_weight: float,
@@ -241,7 +279,7 @@ class PrefixBeamSearch:
         read in place, top-k), the step kernel, pafc_rnnt_beam_select_state and the frame counter's increment -- captured
         once and replayed.  No framework op and no cudnn restriction in the loop; an unmet condition raises PafcError."""
         from ..._lib import PafcError
-        from ...hip_ops import RnntBeamBody, RnntBeamState, rnnt_beam_body_unmet, rnnt_beam_select_state
+        from ...hip_ops import RnntBeamBody, RnntBeamState, rnnt_beam_body_unmet
         if not self.device_resident:
             raise PafcError("frame_body 'kernels': the kernels are the frame of the device-resident search (device_resident is False)")
         unmet = rnnt_beam_body_unmet(self.predictor, self.joint, encoder_outs, beam_size)
@@ -258,26 +296,13 @@ class PrefixBeamSearch:
         ctc_probs = ctc_probs.detach().contiguous()
         lens64 = encoder_lens.to(device=device, dtype=torch.int64).contiguous()
         st = RnntBeamState(B, T, beam_size, self.blank, device)
-        h, c = body.zero_state()
-        t_dev = torch.zeros(1, dtype=torch.int64, device=device)
-
-        def frame():
-            body.frame(E, ctc_probs, transducer_weight, ctc_weight, st.last_tok, h, c, t_dev=t_dev)
-            st.step(0, lens64, body.top_val, body.top_idx, t_dev=t_dev)
-            rnnt_beam_select_state(h, c, body.h_new, body.c_new, st.next_idx, B, beam_size)
-            body.advance(t_dev)
-
+        eng = _ResidentFrames(self, st, lambda tv, ti, t_dev: st.step(0, lens64, tv, ti, t_dev=t_dev), E, ctc_probs,
+                              list(body.zero_state()), transducer_weight, ctc_weight, body=body)
         done = 0
         if self.use_graph and T >= 8:
-            graph_step.on_side_stream(device, lambda: (frame(), frame()))
+            eng.capture()                      # frames 0 and 1; after a refused capture the remainder runs eagerly
             done = 2
-            graph = graph_step.capture(frame, device)[0]      # a refused capture: nothing ran, the frames finish eagerly
-            if graph is not None:
-                for _ in range(T - done):
-                    graph.replay()
-                done = T
-        for _ in range(T - done):
-            frame()
+        eng.run(T - done)
         return self._nbest(st, B, beam_size)
 
 
@@ -286,8 +311,9 @@ class BeamStreamer:
     every stream carried from one feed to the next.  `model` holds predictor, joint and blank (a Transducer or a
     PrefixBeamSearch).  Over a stream, for any cut of its frames into chunks, the n-best token lists and float64 scores
     equal the offline search of the concatenated frames where both sides run the same arithmetic: host loop against
-    prefix_beam_search_decode_batch's, device path against _decode_batch_resident's -- the same frame body on the same
-    B x beam slots and the same candidate walk (csrc/rnnt_beam_frame.inc).
+    prefix_beam_search_decode_batch's (both run _host_frame and _walk_row), device path against _decode_batch_resident's
+    or _decode_batch_kernels' (both run _ResidentFrames on the same B x beam slots, and the candidate walk of
+    csrc/rnnt_beam_frame.inc); only the step call, the frame clamp and where the state lives differ.
 
     feed(encoder_chunk (B, n <= max_frames, D), ctc_chunk (B, n, V) log-probs, nframes=None): row b consumes its first
     nframes[b] frames (default n; 0 = the row sits the chunk out, state unchanged).  Returns per row a partial
@@ -301,10 +327,10 @@ class BeamStreamer:
 
     Device path (GPU tensors, beam_size <= 16; hip_ops.RnntBeamStream, never a fallback): fixed (B, max_frames, D) and
     (B, max_frames, V) staging buffers; the frame body -- predictor step, joint, log-softmax, fusion, top-k, the step
-    kernel, pafc_rnnt_beam_select_state -- reads chunk frame j_dev of them, always under cudnn.flags(enabled=False), and
-    is captured once per streamer into a hipGraph (two eager warm-up frames on a side stream, with no row taking frames,
-    so no state moves) and replayed once per chunk frame: max(nframes) times when the host knows the counts, else n
-    times.  Only a REFUSED capture runs the body eagerly, with the same results.  Host reads per feed: one, the drain
+    kernel, pafc_rnnt_beam_select_state -- reads the chunk frame its device counter names, always under
+    cudnn.flags(enabled=False), and is captured once per streamer into a hipGraph (two eager warm-up frames on a side
+    stream, with no row taking frames, so no state moves) and replayed once per chunk frame: max(nframes) times when the
+    host knows the counts, else n times.  Only a REFUSED capture runs the body eagerly, with the same results.  Host reads per feed: one, the drain
     (none with partials=False); the chunk copies, the frame counts and the `from` offsets go to the device without a
     synchronising call (pass nframes as a device int64 tensor to keep them off the host altogether).
     frame_body "kernels" (default: the model's PrefixBeamSearch.frame_body, "framework"): the device path stages the chunk's
@@ -329,7 +355,7 @@ class BeamStreamer:
         self.committed: List[List[int]] = [[] for _ in range(batch_size)]
         self._device = None
         self._gpu = None                                   # hip_ops.RnntBeamStream, made by the first feed of GPU tensors
-        self._graph = False                                # False: not tried yet; None: the capture was refused
+        self._eng: Optional[_ResidentFrames] = None        # its frames, over the staging buffers
         self._frames = [0] * batch_size                    # frames consumed per row, as far as the host knows
         self._maxlen = [0] * batch_size                    # the longest token list of a row's beam as of the last drain
         self._full = [False] * batch_size
@@ -340,7 +366,7 @@ class BeamStreamer:
     @property
     def graphed(self) -> bool:
         """Whether the device path replays a captured graph."""
-        return bool(self._graph)
+        return bool(self._eng is not None and self._eng.graph)
 
     def reset(self, rows=None):
         rows = list(range(self.B)) if rows is None else [int(b) for b in rows]
@@ -361,8 +387,8 @@ class BeamStreamer:
     def _make_gpu(self, enc: torch.Tensor, ctc: torch.Tensor):
         from ...hip_ops import RnntBeamStream
         dev, B, beam = enc.device, self.B, self.beam
-        self._gpu = RnntBeamStream(B, self.Tmax, beam, self.blank, dev, self.max_total)
-        self._j = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._gpu = st = RnntBeamStream(B, self.Tmax, beam, self.blank, dev, self.max_total)
+        self._body = None
         if self.frame_body == "kernels":
             # the chunk's encoder rows are staged only to be projected: the body reads E = enc_ffn rows and the CTC rows in place
             from ...hip_ops import RnntBeamBody
@@ -371,49 +397,20 @@ class BeamStreamer:
             self._x = torch.zeros(B * self.Tmax, enc.shape[2], dtype=body.dtype, device=dev)
             self._E = torch.zeros(B, self.Tmax, body.join_dim, dtype=body.dtype, device=dev)
             cdt = ctc.dtype if ctc.dtype in (torch.float32, torch.bfloat16) else torch.float32
-            self._ctc = torch.zeros(B, self.Tmax, ctc.shape[2], dtype=cdt, device=dev)
-            return
-        state = self.bs.predictor.init_state(B * beam, method="zero", device=dev)
-        self._cache = [s.to(enc.dtype).contiguous() for s in state]          # static buffers, updated in place
-        self._enc = torch.zeros(B, self.Tmax, enc.shape[2], dtype=enc.dtype, device=dev)
-        self._ctc = torch.zeros(B, self.Tmax, ctc.shape[2], dtype=ctc.dtype, device=dev)
-
-    def _frame_kernels(self):
-        # the frame of PrefixBeamSearch._decode_batch_kernels on chunk frame j_dev of the staged E and CTC rows
-        st, body, (h, c) = self._gpu, self._body, self._cache
-        body.frame(self._E, self._ctc, self.transducer_weight, self.ctc_weight, st.last_tok, h, c, t_dev=self._j)
-        st.step(0, body.top_val, body.top_idx, j_dev=self._j)
-        st.select_state(h, c, body.h_new, body.c_new)
-        body.advance(self._j)
-
-    def _frame(self):
-        # the frame body of PrefixBeamSearch._decode_batch_resident on chunk frame j_dev of the staging buffers; every
-        # tensor it touches has a fixed address and shape, so it can be captured once and replayed
-        if self.frame_body == "kernels":
-            return self._frame_kernels()
-        st, cache, beam, last = self._gpu, self._cache, self.beam, self.Tmax - 1
-        enc = self._enc.index_select(1, self._j.clamp(max=last)).squeeze(1)
-        enc = enc.repeat_interleave(beam, dim=0).unsqueeze(1)                                    # (n, 1, D)
-        logp, new_cache = self.bs.forward_decoder_one_step(enc, st.last_tok, cache)
-        logp = logp.squeeze(1).squeeze(1)                                                        # (n, V)
-        ctc_t = self._ctc.index_select(1, self._j.clamp(max=last)).squeeze(1).repeat_interleave(beam, dim=0)
-        logp = torch.log(torch.add(self.transducer_weight * torch.exp(logp), self.ctc_weight * torch.exp(ctc_t)))
-        top_val, top_idx = logp.topk(beam)
-        st.step(0, top_val.float().contiguous(), top_idx.contiguous(), j_dev=self._j)
-        st.select_state(cache[0], cache[1], new_cache[0].contiguous(), new_cache[1].contiguous())
-        self._j.add_(1)
-
-    def _capture(self):
-        """Once per streamer: two eager frames on a side stream while no row takes frames (they warm every library handle
-        and move no state), then the capture.  A refused capture leaves None: the frames run eagerly."""
-        dev = self._device
-        self._gpu.feed(0)
-        graph_step.on_side_stream(dev, lambda: (self._frame(), self._frame()))
-        self._graph = graph_step.capture(self._frame, dev)[0]
+        else:
+            state = self.bs.predictor.init_state(B * beam, method="zero", device=dev)
+            self._cache = [s.to(enc.dtype).contiguous() for s in state]      # static buffers, updated in place
+            self._enc = torch.zeros(B, self.Tmax, enc.shape[2], dtype=enc.dtype, device=dev)
+            cdt = ctc.dtype
+        self._ctc = torch.zeros(B, self.Tmax, ctc.shape[2], dtype=cdt, device=dev)
+        # chunk frame t_dev of the staging buffers: the frames of the offline decode, the step and the clamp apart
+        self._eng = _ResidentFrames(self.bs, st, lambda tv, ti, j_dev: st.step(0, tv, ti, j_dev=j_dev),
+                                    self._enc if self._body is None else self._E, self._ctc, self._cache,
+                                    self.transducer_weight, self.ctc_weight, body=self._body)
 
     def _feed_gpu(self, enc, ctc, nf, n):
-        st = self._gpu
-        kernels = self.frame_body == "kernels"
+        st, eng = self._gpu, self._eng
+        kernels = self._body is not None
         if n:
             if kernels:
                 self._x.view(self.B, self.Tmax, -1)[:, :n].copy_(enc.detach())
@@ -423,16 +420,12 @@ class BeamStreamer:
             self._ctc[:, :n].copy_(ctc.detach())
         # framework body: MIOpen's RNN call is not capturable; the same cell eagerly.  The kernels need no such restriction.
         with contextlib.nullcontext() if kernels else torch.backends.cudnn.flags(enabled=False):
-            if self.use_graph and self._graph is False:
-                self._capture()
+            if self.use_graph and eng.graph is False:
+                st.feed(0)                                 # once per streamer, while no row takes frames: the warm-up moves no state
+                eng.capture()
             st.feed(nf, n)
-            self._j.zero_()
-            steps = n if isinstance(nf, torch.Tensor) else max(nf)
-            for _ in range(steps):
-                if self._graph:
-                    self._graph.replay()
-                else:
-                    self._frame()
+            eng.t_dev.zero_()
+            eng.run(n if isinstance(nf, torch.Tensor) else max(nf))
 
     def _drain_gpu(self, ld: int) -> List[DecodeResult]:
         """One drain from the committed counts on; full token lists are the committed tokens + the returned tails."""
@@ -449,8 +442,7 @@ class BeamStreamer:
             self._maxlen[b] = max([d["len"][b][k] for k in live], default=0)
             if d["overflow"][b]:
                 self._full[b] = True
-            out.append(DecodeResult(tokens=nbest[0], score=nsc[0], nbest=nbest, nbest_scores=nsc) if nbest
-                       else DecodeResult(tokens=[], score=0.0, nbest=[], nbest_scores=[]))
+            out.append(_result(nbest, nsc))
         self._overflow = d["overflow"]
         return out
 
@@ -468,27 +460,13 @@ class BeamStreamer:
             active = [i for i in range(B) if t < nf[i]]
             if not active:
                 break
-            rows, toks, scores = [], [], []
-            for i in active:
-                for s in beams[i]:
-                    rows.append(i)
-                    toks.append(s.hyp[-1])
-                    scores.append(s.score)
-            n = len(rows)
-            rows_t = torch.tensor(rows, device=device)
+            live = [s for i in active for s in beams[i]]
+            n = len(live)
+            rows_t = torch.tensor([i for i in active for _ in beams[i]], device=device)
             # the live beams' states, utterance by utterance: the columns prefix_beam_search_decode_batch selects
             cache = [torch.cat([self._hstate[i][k] for i in active], dim=1) for k in (0, 1)]
-            enc_t = enc[rows_t, t, :].unsqueeze(1)                                         # (n, 1, D)
-            logp, new_cache = bs.forward_decoder_one_step(enc_t, torch.tensor(toks, device=device), cache)
-            logp = logp.squeeze(1).squeeze(1)                                              # (n, V)
-            logp = torch.log(torch.add(self.transducer_weight * torch.exp(logp),
-                                       self.ctc_weight * torch.exp(ctc[rows_t, t, :])))
-            top_k_logp, top_k_index = logp.topk(beam_size)                                 # (n, beam)
-            cand = torch.tensor(scores, device=device).unsqueeze(1) + top_k_logp          # float32, as the reference
-            packed = torch.cat([cand.float(), top_k_index.float()], dim=1).cpu()           # ONE device->host copy
-            cand_h = packed[:, :beam_size]
-            idx_h = packed[:, beam_size:].to(torch.int64)
-            pool = [torch.cat([cache[0], new_cache[0]], dim=1), torch.cat([cache[1], new_cache[1]], dim=1)]
+            cand_h, idx_h, pool = bs._host_frame(enc, ctc, rows_t, t, live, cache, self.transducer_weight, self.ctc_weight,
+                                                 beam_size)
             cur = 0
             for i in active:
                 nb = len(beams[i])
@@ -500,12 +478,8 @@ class BeamStreamer:
                 cur += nb
 
     def _host_results(self) -> List[DecodeResult]:
-        out = []
-        for b, seqs in enumerate(self._beams):
-            nbest = [s.hyp[1:] for s in seqs]
-            nsc = [s.score for s in seqs]
-            self.committed[b] = list(nbest[0][:_common_prefix_len(nbest)])
-            out.append(DecodeResult(tokens=nbest[0], score=nsc[0], nbest=nbest, nbest_scores=nsc))
+        out = [_result([s.hyp[1:] for s in seqs], [s.score for s in seqs]) for seqs in self._beams]
+        self.committed[:] = [list(r.tokens[:_common_prefix_len(r.nbest)]) for r in out]
         return out
 
     # ---- both --------------------------------------------------------------------------------------------------
@@ -521,8 +495,8 @@ class BeamStreamer:
         on_gpu = encoder_chunk.is_cuda and self.beam <= 16
         if self._device is None:
             if self.frame_body == "kernels":                  # never a fallback: CPU tensors and beam > 16 are named too
-                from ...hip_ops import rnnt_beam_body_unmet
-                like = torch.empty(1, 1, 1, device=encoder_chunk.device).expand(B, self.Tmax, encoder_chunk.shape[2])
+                from ...hip_ops import _shape_like, rnnt_beam_body_unmet
+                like = _shape_like(B, self.Tmax, encoder_chunk.shape[2], encoder_chunk.device)
                 unmet = rnnt_beam_body_unmet(self.bs.predictor, self.bs.joint, like, self.beam)
                 if unmet is not None:
                     raise PafcError(f"BeamStreamer: frame_body 'kernels': {unmet}")

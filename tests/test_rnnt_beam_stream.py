@@ -171,3 +171,30 @@ def test_stream_entry_points_validate_arguments_without_a_gpu():
     assert L.pafc_rnnt_beam_select_state(5, 2, 3, 8, 64, one, one, one, one, one, NULL) == -6
     assert L.pafc_rnnt_beam_select_state(0, 2, 3, 17, 64, one, one, one, one, one, NULL) == -7
     assert L.pafc_rnnt_beam_select_state(0, 0, 3, 8, 64, one, one, one, one, one, NULL) == -2
+
+
+def test_the_frame_engine_dies_with_its_owner_not_in_a_later_collection():
+    """_ResidentFrames holds a hipGraph.  Were it part of a reference cycle, the graph would be destroyed by whichever garbage
+    collection comes next -- possibly inside another stream capture, which the runtime answers with an abort.  So with the
+    collector off, dropping the last reference must free the engine and what it holds."""
+    import gc
+    import weakref
+    from paper_accurate_fast_cheap_amd.transducer.search.prefix_beam_search import _ResidentFrames
+
+    class Slots:
+        B, beam = 1, 1
+
+    for body in (None, object()):
+        was = gc.isenabled()
+        gc.disable()
+        try:
+            slots = Slots()
+            eng = _ResidentFrames(None, slots, lambda tv, ti, t: slots, torch.zeros(1, 2, 4), torch.zeros(1, 2, 3),
+                                  [torch.zeros(1, 1, 2), torch.zeros(1, 1, 2)], 0.7, 0.3, body=body)
+            eng.frame                                                    # looking the frame up must not store it
+            seen = weakref.ref(eng), weakref.ref(slots), weakref.ref(eng.t_dev)
+            del eng, slots
+            assert [r() for r in seen] == [None, None, None]
+        finally:
+            if was:
+                gc.enable()

@@ -7,6 +7,7 @@ overflow, drain with `from`, the state selection against the framework chain, ba
 device path of BeamStreamer against PrefixBeamSearch._decode_batch_resident on the same GPU tensors, bit for bit (both run
 the same frame body on the same B x beam slots, so every GEMM has the same shape), rows that start late and sit chunks
 out, the host reads per feed, and Transducer.stream_beam_search on a reduced causal streaming encoder."""
+import contextlib
 import warnings
 
 import pytest
@@ -317,6 +318,56 @@ def test_row_lifecycle_late_start_and_idle_chunk(hip):
     for r, o in zip(st.results(), _offline_decode(8)):
         assert [list(n) for n in r.nbest] == [list(n) for n in o.nbest]
         assert r.nbest_scores == pytest.approx(o.nbest_scores, abs=2e-3)
+
+
+_HOST = {}
+
+
+def _short(T):
+    """The first T frames of the golden batch with ragged lengths (T, T // 2, 1) -- rows that end inside the two warm-up
+    frames included -- and the host loop's result on them, computed once per T."""
+    w = _world()
+    if T not in _HOST:
+        enc, logp = w["enc"][:, :T].contiguous(), w["logp"][:, :T].contiguous()
+        lens = torch.tensor([T, T // 2, 1], device="cuda")
+        bs = w["bs"]
+        bs.device_resident = False
+        try:
+            with torch.no_grad():
+                host = bs.prefix_beam_search_decode(enc, lens, logp, beam_size=3, ctc_weight=0.3, transducer_weight=0.7)
+        finally:
+            bs.device_resident = True
+        _HOST[T] = (enc, lens, logp, host)
+    return _HOST[T]
+
+
+@pytest.mark.parametrize("frame_body", ["framework", "kernels"])
+def test_offline_warm_up_frames_are_counted_at_every_length(hip, frame_body):
+    """The offline resident decode at the lengths around its `use_graph and T >= 8` rule: T = 1, 2, 7 run eagerly, T = 8 is the
+    two warm-up frames plus six replays, T = 9 the graph path, and T = 9 again without the graph.  Each against the host loop
+    on the same tensors: equal n-best token lists, scores within 2e-3 (test_search's bound for the two paths' differently
+    batched GEMMs).  The graphed and the eager T = 9 results are equal bit for bit (the framework body runs the framework's
+    own LSTM cell under the graph, so its eager run does too)."""
+    bs = _world()["bs"]
+    assert bs.use_graph
+    got = {}
+    try:
+        for T, use_graph in ((1, True), (2, True), (7, True), (8, True), (9, True), (9, False)):
+            enc, lens, logp, host = _short(T)
+            bs.use_graph = use_graph
+            with torch.no_grad(), contextlib.nullcontext() if use_graph else torch.backends.cudnn.flags(enabled=False):
+                res = bs.prefix_beam_search_decode(enc, lens, logp, beam_size=3, ctc_weight=0.3, transducer_weight=0.7,
+                                                   frame_body=frame_body)
+            got[T, use_graph] = res
+            print(frame_body, T, use_graph, [max((abs(a - b) for a, b in zip(r.nbest_scores, h.nbest_scores)), default=0.0)
+                                             for r, h in zip(res, host)])
+            for r, h in zip(res, host):
+                assert [list(n) for n in r.nbest] == [list(n) for n in h.nbest], (T, use_graph)
+                assert r.nbest_scores == pytest.approx(h.nbest_scores, abs=2e-3), (T, use_graph)
+                assert list(r.tokens) == list(h.tokens)
+    finally:
+        bs.use_graph = True
+    _equal(got[9, True], got[9, False])
 
 
 @pytest.mark.parametrize("partials", [True, False])
