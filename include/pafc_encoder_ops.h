@@ -533,6 +533,24 @@ int pafc_multi_transpose_bf16(const void *table, int n, int total_tiles, pafc_st
  * tensor, tile0 counting chunks of 4 096 elements: the bf16 copies of the fp32 master weights, refreshed once per training step. */
 int pafc_multi_cast_bf16(const void *table, int n, int total_chunks, pafc_stream_t stream);
 
+/* Rows of n tensors between a pool of S slots and a dense batch of m rows, each direction ONE launch: the carried encoder state
+ * of the m streams that run a chunk step (encoder.py forward_chunk's caches, one set per stream), brought together before the
+ * step and put back after it.  Table entry i is four longs { pool base, compact base, row bytes, ring bytes }: the pool tensor
+ * has S rows and the compact tensor m rows of `row bytes` each (a multiple of 4, else PAFC_ERR_BAD_DIMS; bases 4-byte aligned,
+ * else PAFC_ERR_ALIGNMENT; 16 bytes per lane are moved where bases and row size are multiples of 16, 4 bytes otherwise).  The
+ * table is passed twice: `table` is the HOST copy, which is validated and sizes the grid (pieces of 16 KiB of the largest row,
+ * m, n), `table_dev` the device copy the kernel reads; the buffers are fixed for the life of a pool, so both are made once.
+ * idx: DEVICE int32 (m), compact row j is pool slot idx[j]; it is read by the kernel only, so a captured launch of fixed m
+ * serves any choice of slots.  idx[j] < 0 is a padding row: gather fills it with zeros, scatter skips it; idx[j] >= S is
+ * skipped by both.  The slots of a scatter must be distinct.
+ * A gather entry with ring bytes > 0 is a ring: its pool rows are `ring bytes` long (a multiple of 4, >= row bytes) and
+ * compact row j receives the `row bytes` that start at byte offs[j] of its slot's ring, wrapping (offs: DEVICE int32 (m), a
+ * multiple of 4) -- the feature window of a stream out of the ring of frames pafc_fbank_stream_rows writes.  Scatter refuses
+ * ring entries (PAFC_ERR_UNSUPPORTED).  Nothing is allocated; asynchronous on `stream`. */
+int pafc_rows_gather(const long *table, const long *table_dev, int n, const int *idx, const int *offs, int m, int S,
+                     pafc_stream_t stream);
+int pafc_rows_scatter(const long *table, const long *table_dev, int n, const int *idx, int m, int S, pafc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,18 @@
  *   on the same stream then moves the last c_next = c + n - 160 * frames samples to the front of carry[b], in place.
  *   frames == 0 launches only that update, n == 0 launches nothing; both launches can be captured.  pafc_fbank_stream_plan is
  *   the arithmetic (frames, c_next) on the host, c_next < 560 always.  dither != 0 is PAFC_ERR_UNSUPPORTED here.
+ *
+ * pafc_fbank_stream_rows: R ragged rows that belong to arbitrary slots of a pool of S independent streams, in one launch
+ *   pair, grid (tiles of the row with the most frames, R).  carry: (S, 560) float32; chunk: (R, ld_chunk >= n_max); row i's
+ *   descriptor is four int32 {slot, c, n, first_frame}: its samples are carry[slot, 0:c] followed by chunk[i, 0:n]
+ *   (0 <= c < 560, 0 <= n <= n_max), and its frame f is written at out[slot, (first_frame + f) mod ring_frames, :]
+ *   (out: (S, ring_frames, num_mel_bins) contiguous, PAFC_F32 or PAFC_BF16; first_frame: the absolute index of the row's first
+ *   new frame).  The table is passed twice: rows is the HOST copy, which is validated and sizes the grid, rows_dev the
+ *   device copy the kernels read (uploaded by the caller on `stream`), so nothing is ever read back.  The slots of a call are
+ *   distinct, and a row completes at most ring_frames frames (the caller cuts a longer packet).  The second kernel moves the
+ *   last c + n - 160 * frames samples of every row with n > 0 to the front of carry[slot].  Rows with n == 0 do nothing; a
+ *   call in which no row completes a frame launches only the carry update; a call without a new sample launches nothing.
+ *   The carries and rings of slots not named are not touched.  dither != 0 is PAFC_ERR_UNSUPPORTED.
  */
 #ifndef PAFC_FBANK_H
 #define PAFC_FBANK_H
@@ -56,6 +68,10 @@ int pafc_fbank_stream(float *carry, int c, const float *chunk, long ld_chunk, lo
                       const float *dft_table, const float *mel_weights, const int *mel_lo, const int *mel_hi, int num_mel_bins,
                       float dither, float preemph, void *out, int out_dtype, long out_row_stride, long first_frame,
                       pafc_stream_t stream);
+int pafc_fbank_stream_rows(float *carry, int S, const int *rows, const int *rows_dev, int R, const float *chunk, long ld_chunk,
+                           long n_max, const float *window, const float *dft_table, const float *mel_weights, const int *mel_lo,
+                           const int *mel_hi, int num_mel_bins, float dither, float preemph, void *out, int out_dtype,
+                           int ring_frames, pafc_stream_t stream);
 
 #ifdef __cplusplus
 }

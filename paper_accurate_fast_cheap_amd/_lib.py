@@ -133,6 +133,8 @@ SIGNATURES = {
     "pafc_silu_dropout": (I, [I, I, G, P, P, P, F, U, U, P]),
     "pafc_multi_transpose_bf16": (I, [P, I, I, P]),
     "pafc_multi_cast_bf16": (I, [P, I, I, P]),
+    "pafc_rows_gather": (I, [P, P, I, P, P, I, I, P]),
+    "pafc_rows_scatter": (I, [P, P, I, P, I, I, P]),
     # include/pafc_fbank.h
     "pafc_fbank_num_frames": (G, [G]),
     "pafc_fbank_tables_cols": (I, []),
@@ -140,6 +142,7 @@ SIGNATURES = {
     "pafc_fbank_batch": (I, [P, G, P, I, G, P, P, P, P, P, I, P, F, F, P, I, P, P]),
     "pafc_fbank_stream_plan": (I, [I, G, P, P]),
     "pafc_fbank_stream": (I, [P, I, P, G, G, I, P, P, P, P, P, I, F, F, P, I, G, G, P]),
+    "pafc_fbank_stream_rows": (I, [P, I, P, P, I, P, G, G, P, P, P, P, P, I, F, F, P, I, I, P]),
     # include/pafc_search.h
     "pafc_ctc_greedy": (I, [I, I, I, I, P, P, I, P, P, P, P, P]),
     "pafc_log_softmax_rows": (I, [I, G, I, P, P, P]),

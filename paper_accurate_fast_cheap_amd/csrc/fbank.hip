@@ -18,7 +18,9 @@
 // emit functor (where the tile's rows go).  Every frame depends on its own 400 samples only -- one wave_sum per frame, one A
 // row per MFMA output row --, so each instantiation gives the same bits per frame: pafc_fbank_f32 (one waveform),
 // pafc_fbank_batch (grid.y = row of a ragged batch; rows past a row's frame count are written as zero) and
-// pafc_fbank_stream (a row's samples are its carried tail followed by the new chunk; a second small kernel moves the carry).
+// pafc_fbank_stream (a row's samples are its carried tail followed by the new chunk; a second small kernel moves the carry)
+// and pafc_fbank_stream_rows (the same per row of a slot pool: every row has its own carry length, sample count and place in
+// its slot's ring of frames, read from a descriptor table in device memory).
 #include "pafc_common.h"
 #include "fbank_host.h"
 
@@ -251,6 +253,66 @@ __global__ __launch_bounds__(256) void fbank_carry_kernel(float *carry, int c, c
     }
 }
 
+// Ragged rows of a slot pool: grid (tiles of the row with the most frames, R).  Row b's descriptor is rows[4 b ..] =
+// {slot, c, n, first_frame}; its frame f goes to out[slot, (first_frame + f) mod ring_frames, :].
+struct SlotRowsParams {
+    const float *carry;       // (S, CARRY)
+    const int *rows;          // (R, 4) device
+    long ld_chunk;
+    void *out;                // (S, ring_frames, nmel)
+    int ring_frames;
+};
+
+template <typename ET>
+__global__ __launch_bounds__(256) void fbank_slot_rows_kernel(const FbankParams p, const SlotRowsParams r) {
+    const int b = blockIdx.y, m0 = blockIdx.x * FPB, tid = threadIdx.x;
+    const int *d = r.rows + 4 * b;
+    const int slot = d[0], c = d[1], n = d[2], first = d[3];
+    const int m = n > 0 ? (int)fbank_host::num_frames((long)c + n) : 0;
+    if (m0 >= m) return;                                        // block-uniform, before any barrier
+    FbankParams q = p;
+    q.m = m;
+    const float *row = p.wave + (long)b * r.ld_chunk;
+    const float *car = r.carry + (long)slot * CARRY;
+    ET *ring = (ET *)r.out + (long)slot * r.ring_frames * p.nmel;
+    const int at = (int)(((long)first + m0) % r.ring_frames);   // ring row of the tile's first frame
+    fbank_tile(q, m0, [&](long s0) { return CarryThenChunk{car, row, c, s0}; }, [&](const float *O, int ldo, int) {
+        const int nvalid = min(FPB, m - m0);
+        for (int i = tid; i < nvalid * q.nmel; i += 256) {
+            const int f = i / q.nmel, k = i % q.nmel;
+            const int at_f = (at + f) % r.ring_frames;          // (a ring shorter than a tile wraps more than once)
+            Elem<ET>::store(ring + (long)at_f * q.nmel + k, O[f * ldo + k]);
+        }
+    });
+}
+
+// fbank_carry_kernel per row of the descriptor table, on carry[slot]; a row without new samples is left alone.
+__global__ __launch_bounds__(256) void fbank_slot_carry_kernel(float *carry, const int *rows, const float *chunk, long ld_chunk) {
+    const int *d = rows + 4 * blockIdx.x;
+    const int slot = d[0], c = d[1], n = d[2];
+    if (n <= 0) return;                                         // block-uniform
+    const int c_next = c + n - SHIFT * (int)fbank_host::num_frames((long)c + n);
+    float *car = carry + (long)slot * CARRY;
+    const float *row = chunk + (long)blockIdx.x * ld_chunk;
+    const int first = c + n - c_next;
+    float v[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int j = threadIdx.x + 256 * q;
+        v[q] = 0.f;
+        if (j < c_next) {
+            const int s = first + j;
+            v[q] = s < c ? car[s] : row[s - c];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int j = threadIdx.x + 256 * q;
+        if (j < c_next) car[j] = v[q];
+    }
+}
+
 size_t tile_lds_bytes(int nmel) {
     const size_t a_bytes = sizeof(float) * FPB * LDA;
     const size_t po_bytes = sizeof(float) * (FPB * LDP + 64 + FPB * (nmel | 1));
@@ -265,6 +327,16 @@ int launch_rows(const FbankParams &p, const RowsParams &r, long tiles, int B, hi
         return PAFC_ERR_LAUNCH;
     hipLaunchKernelGGL((fbank_rows_kernel<ET, STREAM>), dim3((unsigned)tiles, (unsigned)B), dim3(256), tile_lds_bytes(p.nmel),
                        stream, p, r);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+template <typename ET>
+int launch_slot_rows(const FbankParams &p, const SlotRowsParams &r, long tiles, int R, hipStream_t stream) {
+    if (hipFuncSetAttribute((const void *)fbank_slot_rows_kernel<ET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+        hipSuccess)
+        return PAFC_ERR_LAUNCH;
+    hipLaunchKernelGGL((fbank_slot_rows_kernel<ET>), dim3((unsigned)tiles, (unsigned)R), dim3(256), tile_lds_bytes(p.nmel), stream,
+                       p, r);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 
@@ -339,6 +411,30 @@ int pafc_fbank_stream(float *carry, int c, const float *chunk, long ld_chunk, lo
     }
     hipLaunchKernelGGL(pafc::fbank_carry_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, carry, c, chunk, ld_chunk,
                        n, c_next);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+int pafc_fbank_stream_rows(float *carry, int S, const int *rows, const int *rows_dev, int R, const float *chunk, long ld_chunk,
+                           long n_max, const float *window, const float *dft_table, const float *mel_weights, const int *mel_lo,
+                           const int *mel_hi, int num_mel_bins, float dither, float preemph, void *out, int out_dtype,
+                           int ring_frames, pafc_stream_t stream) {
+    long frames = 0;
+    bool any_new = false;
+    int rc = pafc::fbank_host::stream_rows_check(carry, S, rows, rows_dev, R, chunk, ld_chunk, n_max,
+                                                 pafc::fbank_host::tables_null(window, dft_table, mel_weights, mel_lo, mel_hi),
+                                                 num_mel_bins, dither, out, out_dtype, ring_frames, &frames, &any_new);
+    if (rc != PAFC_OK || !any_new) return rc;
+    if (frames > 0) {
+        pafc::FbankParams p{chunk, 0, 0, window, dft_table, mel_weights, mel_lo, mel_hi, num_mel_bins, nullptr, 0.f, preemph,
+                            nullptr};
+        pafc::SlotRowsParams r{carry, rows_dev, ld_chunk, out, ring_frames};
+        const long tiles = (frames + pafc::FPB - 1) / pafc::FPB;
+        rc = out_dtype == PAFC_BF16 ? pafc::launch_slot_rows<pafc::bf16_t>(p, r, tiles, R, (hipStream_t)stream)
+                                    : pafc::launch_slot_rows<float>(p, r, tiles, R, (hipStream_t)stream);
+        if (rc != PAFC_OK) return rc;
+    }
+    hipLaunchKernelGGL(pafc::fbank_slot_carry_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, carry, rows_dev, chunk,
+                       ld_chunk);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 

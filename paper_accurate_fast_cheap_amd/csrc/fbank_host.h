@@ -60,5 +60,37 @@ inline int stream_check(const void *carry, int c, const void *chunk, long ld_chu
     return PAFC_OK;
 }
 
+// Ragged rows of a slot pool: rows is the HOST copy of the (R, 4) int32 descriptor table {slot, c, n, first_frame}.
+// -> PAFC_OK, *max_frames (the most frames a row completes) and *any_new (some row has n > 0), or the error
+inline int stream_rows_check(const void *carry, int S, const int *rows, const void *rows_dev, int R, const void *chunk,
+                             long ld_chunk, long n_max, bool tables_are_null, int nmel, float dither, const void *out,
+                             int out_dtype, int ring_frames, long *max_frames, bool *any_new) {
+    if (!carry || !rows || !rows_dev || tables_are_null) return PAFC_ERR_NULL_POINTER;
+    if (S <= 0 || S > MAXROWS || R <= 0 || R > S || nmel <= 0 || nmel > MAXMEL || n_max < 0 || ring_frames <= 0)
+        return PAFC_ERR_BAD_DIMS;
+    if (dither != 0.f) return PAFC_ERR_UNSUPPORTED;
+    if (out_dtype != PAFC_F32 && out_dtype != PAFC_BF16) return PAFC_ERR_DTYPE;
+    long most = 0;
+    bool fresh = false;
+    for (int i = 0; i < R; ++i) {
+        const int slot = rows[4 * i], c = rows[4 * i + 1], n = rows[4 * i + 2], first = rows[4 * i + 3];
+        if (slot < 0 || slot >= S || n > n_max || first < 0) return PAFC_ERR_BAD_DIMS;
+        for (int j = 0; j < i; ++j)                    // two rows of one slot would race on its carry and its ring
+            if (rows[4 * j] == slot) return PAFC_ERR_BAD_DIMS;
+        long f = 0;
+        const int rc = stream_plan(c, n, &f, nullptr);
+        if (rc != PAFC_OK) return rc;
+        if (n == 0) continue;
+        if (f > ring_frames || first + f > 0x7fffffffL) return PAFC_ERR_BAD_DIMS;
+        fresh = true;
+        most = f > most ? f : most;
+    }
+    if (fresh && (!chunk || ld_chunk < n_max)) return chunk ? PAFC_ERR_BAD_DIMS : PAFC_ERR_NULL_POINTER;
+    if (most > 0 && !out) return PAFC_ERR_NULL_POINTER;
+    *max_frames = most;
+    *any_new = fresh;
+    return PAFC_OK;
+}
+
 }  // namespace fbank_host
 }  // namespace pafc

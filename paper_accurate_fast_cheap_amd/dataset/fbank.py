@@ -231,6 +231,76 @@ class FbankStreamer:
         return out
 
 
+class FbankSlotStreamer:
+    """fbank of `slots` INDEPENDENT streams fed raggedly: a call names any subset of the slots, each with its own number of new
+    samples, and the frames go into a per-slot ring `ring` (slots, ring_frames, num_mel_bins): frame f of a slot's stream lies at
+    ring[slot, f mod ring_frames].  feed_rows(slot_ids, chunk (R, n_max), lengths) -> frames completed per row; row i brings
+    chunk[i, :lengths[i]] to slot slot_ids[i] (distinct slots; lengths None = n_max each).  One launch pair and one small upload
+    of the row descriptors, no wait.  `carry_len[slot]` / `frames_emitted[slot]` mirror the device state on the host (the plan
+    is pure arithmetic), reset(slot) starts a new stream in a slot.  A row may complete at most ring_frames frames per call, and
+    the caller has to have consumed a ring row before the stream comes round to it again.  For any cut of a stream into feeds,
+    interleaved with other streams in any slot order, its frames are bit for bit fbank_batch of its whole audio."""
+
+    def __init__(self, slots: int, ring_frames: int, num_mel_bins: int = 80, out_dtype: torch.dtype = torch.float32, device="cuda",
+                 dither: float = 0.0):
+        if dither != 0.0:
+            raise _lib.PafcError("FbankSlotStreamer: dither is not offered on a stream (dither must be 0)")
+        if slots < 1 or ring_frames < 1:
+            raise _lib.PafcError("FbankSlotStreamer: slots and ring_frames must be >= 1")
+        self.S, self.ring_frames, self.nmel, self.out_dtype = slots, ring_frames, num_mel_bins, out_dtype
+        self._code = _lib.dtype_code(out_dtype)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.PafcError("this op runs on the MI355X only (device is %s); there is no CPU fallback" % self.device)
+        self._L = _lib.lib()
+        self._t = _get_tables(self.device, num_mel_bins)
+        self._carry = torch.zeros((slots, CARRY), dtype=torch.float32, device=self.device)
+        self.ring = torch.zeros((slots, ring_frames, num_mel_bins), dtype=out_dtype, device=self.device)
+        self.carry_len = [0] * slots
+        self.frames_emitted = [0] * slots
+
+    def reset(self, slot: int):
+        self.carry_len[slot] = 0
+        self.frames_emitted[slot] = 0
+
+    def feed_rows(self, slot_ids: Sequence[int], chunk: torch.Tensor, lengths: Optional[Sequence[int]] = None) -> List[int]:
+        chunk = _rows(chunk, "chunk")
+        slot_ids = [int(s) for s in slot_ids]
+        R, n_max = len(slot_ids), chunk.size(1)
+        if R == 0:
+            return []
+        if chunk.size(0) != R or chunk.device != self._carry.device:
+            raise _lib.PafcError(f"FbankSlotStreamer.feed_rows: the chunk must be ({R}, n_max) on {self._carry.device}")
+        lengths = [n_max] * R if lengths is None else [int(v) for v in lengths]
+        if len(lengths) != R or any(not 0 <= s < self.S for s in slot_ids) or len(set(slot_ids)) != R:
+            raise _lib.PafcError(f"FbankSlotStreamer.feed_rows: {R} distinct slots in [0, {self.S}) and {R} lengths")
+        desc, plans = [], []
+        for s, n in zip(slot_ids, lengths):
+            if not 0 <= n <= n_max:
+                raise _lib.PafcError(f"FbankSlotStreamer.feed_rows: slot {s}: length {n} is outside [0, {n_max}]")
+            frames, c_next = stream_plan(self.carry_len[s], n)
+            if frames > self.ring_frames:
+                raise _lib.PafcError(f"FbankSlotStreamer.feed_rows: slot {s}: {frames} frames in one call, the ring holds "
+                                     f"{self.ring_frames} (cut the packet)")
+            desc += [s, self.carry_len[s], n, self.frames_emitted[s]]
+            plans.append((frames, c_next))
+        if not any(lengths):
+            return [0] * R
+        host = (c_int * len(desc))(*desc)
+        dev = torch.tensor(desc, dtype=torch.int32).to(self._carry.device)
+        t = self._t
+        rc = self._L.pafc_fbank_stream_rows(_lib.ptr(self._carry), self.S, host, _lib.ptr(dev), R, _lib.ptr(chunk), _ld(chunk), n_max,
+                                            _lib.ptr(t["window"]), _lib.ptr(t["dft"]), _lib.ptr(t["melw"]), _lib.ptr(t["lo"]),
+                                            _lib.ptr(t["hi"]), self.nmel, 0.0, 0.97, _lib.ptr(self.ring), self._code,
+                                            self.ring_frames, _lib.stream_of(chunk))
+        _lib.check(rc, "pafc_fbank_stream_rows")
+        for s, n, (frames, c_next) in zip(slot_ids, lengths, plans):
+            if n > 0:
+                self.carry_len[s] = c_next
+                self.frames_emitted[s] += frames
+        return [f if n > 0 else 0 for n, (f, _) in zip(lengths, plans)]
+
+
 def compute_fbank(sample: dict, num_mel_bins: int = 23, frame_length: int = 25, frame_shift: int = 10,
                   dither: float = 0.0) -> dict:
     """wenet/dataset/processor.py:343-371: {key, wav (float in [-1, 1)), sample_rate} -> adds 'feat'."""

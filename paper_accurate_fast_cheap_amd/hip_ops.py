@@ -3238,3 +3238,89 @@ def mamba2_finish(y0, y1, xbc, dt_raw, z, dt_bias, D, norm_weight, eps: float, d
                                        _lib.stream_of(xbc))
     _lib.check(rc, "pafc_mamba2_finish")
     return out
+
+
+class RowsTable:
+    """A table of tensors whose rows move between a pool of S slots and a dense batch in ONE launch each way
+    (pafc_rows_gather / pafc_rows_scatter).  entries: [(pool (S, ...), compact (>= m, ...))] with equal row shapes and dtypes,
+    both contiguous; rings: [(ring (S, frames, F), window (>= m, w, F))] -- gather only: compact row j receives the w frames
+    that start at frame offs[j] of its slot's ring, wrapping.  The host copy and the device copy of the table are made once,
+    here: the tensors must stay where they are for the life of the table.  gather(idx, m, offs) / scatter(idx, m): idx device
+    int32 (>= m), compact row j is pool slot idx[j]; idx[j] < 0 is a padding row (gather: zeros, scatter: skipped); offs
+    device int32 (>= m) BYTE offsets into the rings (frame index x frame_bytes).  No wait, nothing allocated: both can be captured."""
+
+    def __init__(self, entries, rings=()):
+        rows, self.S, self.rows_max, dev = [], None, None, None
+        self._frame_bytes = None
+        for ring, (pool, comp) in [(False, e) for e in entries] + [(True, e) for e in rings]:
+            _lib.require_gpu(pool, comp)
+            if pool.device != comp.device or pool.dtype != comp.dtype or pool.dim() < 1 or comp.dim() != pool.dim():
+                raise _lib.PafcError("RowsTable: a pool tensor and its compact tensor must share device, dtype and rank")
+            if dev is None:
+                dev, self.S = pool.device, pool.size(0)
+            if pool.device != dev or pool.size(0) != self.S:
+                raise _lib.PafcError("RowsTable: every pool tensor must have the same number of slots on one device")
+            es = pool.element_size()
+            if ring:
+                if pool.dim() != 3 or pool.size(2) != comp.size(2) or comp.size(1) > pool.size(1):
+                    raise _lib.PafcError("RowsTable: a ring is (S, frames, F) and its window (m, w <= frames, F)")
+                fb = pool.size(2) * es
+                if self._frame_bytes not in (None, fb):
+                    raise _lib.PafcError("RowsTable: the rings of one table must have frames of one size")
+                self._frame_bytes = fb
+                rows.append([pool.data_ptr(), comp.data_ptr(), comp.size(1) * fb, pool.size(1) * fb])
+            else:
+                if pool.shape[1:] != comp.shape[1:]:
+                    raise _lib.PafcError(f"RowsTable: row shapes differ ({tuple(pool.shape[1:])} and {tuple(comp.shape[1:])})")
+                rows.append([pool.data_ptr(), comp.data_ptr(), (pool.numel() // max(self.S, 1)) * es, 0])
+            self.rows_max = comp.size(0) if self.rows_max is None else min(self.rows_max, comp.size(0))
+        if not rows:
+            raise _lib.PafcError("RowsTable: no entries")
+        self.n, self.device = len(rows), dev
+        self._has_ring = any(r[3] for r in rows)
+        flat = [v for r in rows for v in r]
+        self._host = (ctypes.c_long * len(flat))(*flat)
+        self._dev = torch.tensor(flat, dtype=torch.int64).to(dev)
+        self._keep = (list(entries), list(rings))
+        self._L = _lib.lib()
+
+    def _idx(self, idx, m, what):
+        if idx is None or not idx.is_cuda or idx.device != self.device or idx.dtype != torch.int32 or idx.dim() != 1 \
+                or not idx.is_contiguous() or idx.numel() < m:
+            raise _lib.PafcError(f"RowsTable: {what} must be a contiguous int32 tensor of >= {m} elements on {self.device}")
+        return idx
+
+    def _m(self, m):
+        if not 1 <= m <= self.rows_max:
+            raise _lib.PafcError(f"RowsTable: m = {m} rows, the compact tensors hold {self.rows_max}")
+        return int(m)
+
+    def gather(self, idx: torch.Tensor, m: int, offs: Optional[torch.Tensor] = None) -> None:
+        m = self._m(m)
+        self._idx(idx, m, "idx")
+        if self._has_ring:
+            self._idx(offs, m, "offs")
+        rc = self._L.pafc_rows_gather(self._host, _lib.ptr(self._dev), self.n, _lib.ptr(idx),
+                                      _lib.ptr(offs if self._has_ring else None), m, self.S, _lib.stream_of(idx))
+        _lib.check(rc, "pafc_rows_gather")
+
+    def scatter(self, idx: torch.Tensor, m: int) -> None:
+        m = self._m(m)
+        self._idx(idx, m, "idx")
+        rc = self._L.pafc_rows_scatter(self._host, _lib.ptr(self._dev), self.n, _lib.ptr(idx), m, self.S, _lib.stream_of(idx))
+        _lib.check(rc, "pafc_rows_scatter")
+
+    @property
+    def frame_bytes(self) -> int:
+        """Bytes of one ring frame: offs[j] = (frame mod ring frames) * frame_bytes."""
+        return self._frame_bytes or 0
+
+
+def rows_gather(entries, idx: torch.Tensor, m: int, rings=(), offs: Optional[torch.Tensor] = None) -> None:
+    """One-off RowsTable(entries, rings).gather(idx, m, offs) (the table is built and uploaded for this call)."""
+    RowsTable(entries, rings).gather(idx, m, offs)
+
+
+def rows_scatter(entries, idx: torch.Tensor, m: int) -> None:
+    """One-off RowsTable(entries).scatter(idx, m)."""
+    RowsTable(entries).scatter(idx, m)

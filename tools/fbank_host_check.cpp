@@ -100,6 +100,27 @@ int main() {
     CHECK(fh::stream_check(one, 10, one, 100, 100, 2, false, 80, 0.f, nullptr, PAFC_F32, 0, 0, &frames, &c_next) == PAFC_OK && frames == 0 && c_next == 110);
     CHECK(fh::stream_check(one, 10, nullptr, 0, 0, 2, false, 80, 0.f, nullptr, PAFC_F32, 0, 0, &frames, &c_next) == PAFC_OK && frames == 0 && c_next == 10);
 
+    // ragged rows of a slot pool: the host copy of the descriptor table {slot, c, n, first_frame} is read here, all of it
+    long most = -1;
+    bool any_new = false;
+    const int rows[] = {3, 0, 1000, 0, 1, 399, 160, 7, 4, 17, 0, 3};
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, one, 2000, 2000, false, 80, 0.f, one, PAFC_BF16, 96, &most, &any_new) == PAFC_OK);
+    CHECK(most == 4 && any_new);
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, one, 2000, 2000, false, 80, 0.f, nullptr, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_NULL_POINTER);
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, nullptr, 2000, 2000, false, 80, 0.f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_NULL_POINTER);
+    CHECK(fh::stream_rows_check(one, 5, nullptr, one, 3, one, 2000, 2000, false, 80, 0.f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_NULL_POINTER);
+    CHECK(fh::stream_rows_check(one, 4, rows, one, 3, one, 2000, 2000, false, 80, 0.f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_BAD_DIMS);    // slot 4 of 4
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, one, 2000, 999, false, 80, 0.f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_BAD_DIMS);     // n > n_max
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, one, 1999, 2000, false, 80, 0.f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_BAD_DIMS);    // ld_chunk
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, one, 2000, 2000, false, 80, 0.f, one, PAFC_F32, 3, &most, &any_new) == PAFC_ERR_BAD_DIMS);     // 4 frames, ring of 3
+    CHECK(fh::stream_rows_check(one, 5, rows, one, 3, one, 2000, 2000, false, 80, 0.5f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_UNSUPPORTED);
+    const int twice[] = {2, 0, 100, 0, 2, 0, 100, 0};
+    CHECK(fh::stream_rows_check(one, 5, twice, one, 2, one, 100, 100, false, 80, 0.f, one, PAFC_F32, 96, &most, &any_new) == PAFC_ERR_BAD_DIMS);
+    const int idle[] = {0, 17, 0, 3, 4, 0, 0, 0};
+    CHECK(fh::stream_rows_check(one, 5, idle, one, 2, nullptr, 0, 0, false, 80, 0.f, nullptr, PAFC_F32, 96, &most, &any_new) == PAFC_OK && !any_new && most == 0);
+    const int grow[] = {1, 100, 50, 9};                                              // no frame: the carry update alone, no out needed
+    CHECK(fh::stream_rows_check(one, 5, grow, one, 1, one, 50, 50, false, 80, 0.f, nullptr, PAFC_F32, 96, &most, &any_new) == PAFC_OK && any_new && most == 0);
+
     std::puts("fbank host check ok");
     return 0;
 }
