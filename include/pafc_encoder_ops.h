@@ -496,6 +496,25 @@ int pafc_gemm_ph_ex2(long M, int N, int K, int batch, const void *A, long lda, l
                      const void *W, long ldw, long strideW, const void *bias, long strideBias, const void *residual, int res_kind,
                      long ldr, long strideR, void *out, int out_kind, long ldo, long lo_off, long strideO, float alpha, int act,
                      int tile_m, pafc_stream_t stream);
+/* pafc_gemm_ph_ex2 for a split-operand problem with an fp32 output whose last round of one-tile-per-CU work is short (the
+ * N = 512, long-K projections of the 30-minute shape: 352 tiles on 256 CUs): rows [0, split_row) run as pafc_gemm_ph_ex2 runs
+ * them; the 256-row tiles of rows [split_row, M) run once per K slice (slice z = K columns [z K / kslices, (z + 1) K / kslices) of
+ * both planes) into slab z, (M - split_row) x N fp32, of `workspace`; a third launch writes
+ *   out[m][n] = fmaf(slab_0 + slab_1, alpha, bias[n]) + residual[m][n]        for the rows from split_row on
+ * (the order of the pipelined kernel's epilogue; residual may be out).  Three launches on `stream`, no block waits for another,
+ * no atomics: the result does not depend on timing.  Arguments as pafc_gemm_ph_ex2, of which this takes a_split != 0,
+ * out_kind 1, res_kind 0 / 2, act 0, batch 1, tile_m 256, kslices 2 (else PAFC_ERR_UNSUPPORTED); split_row a multiple of 256 in
+ * [0, M), K a multiple of 64 kslices, workspace_bytes >= kslices (M - split_row) N 4 (else PAFC_ERR_BAD_DIMS); workspace
+ * 16-byte aligned.  Nothing is launched when a code other than PAFC_OK / PAFC_ERR_LAUNCH comes back. */
+int pafc_gemm_ph_ktail(long M, int N, int K, int batch, const void *A, long lda, long strideA, int a_split, int a_plane_block,
+                       const void *W, long ldw, long strideW, const void *bias, long strideBias, const void *residual, int res_kind,
+                       long ldr, long strideR, void *out, int out_kind, long ldo, long lo_off, long strideO, float alpha, int act,
+                       int tile_m, void *workspace, size_t workspace_bytes, long split_row, int kslices, pafc_stream_t stream);
+/* The rule that picks (split_row, kslices) for pafc_gemm_ph_ktail: a pure function of the problem and the CU count (cus <= 0:
+ * the current device's).  tiles = 256-row tiles x 256-column tiles, full = the tiles of the whole rounds, tail = the rest;
+ * the plan holds when full > 0, 0 < 2 tail <= cus, the tail is whole row tiles, K / 32 is a multiple of 4, K >= min_k and
+ * batch == 1.  Returns kslices (2) with *split_row set, or 0: no plan.  At most ONE tail round is split, in two. */
+int pafc_gemm_ph_ktail_plan(long M, int N, int K, int batch, int cus, int min_k, long *split_row);
 /* Conv2d(Ci, Co, 3, stride 2) + bias (+ ReLU) of an fp32 model (subsampling.py:187-192) on the same kernel with split
  * operands: in_planes (B, T1, F1, 2 Ci) bf16 = [hi Ci | lo Ci] per pixel of the fp32 image, w3 (9, Co, 3 Ci) = [hi | hi | lo]
  * of the fp32 weight per tap (tap-major, then Co), fp32 bias, out_planes (B, T2, F2, 2 Co) = [hi Co | lo Co] per position.

@@ -128,6 +128,8 @@ SIGNATURES = {
     "pafc_gemm_bf16_ph": (I, [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, I, I, P]),
     "pafc_gemm_ph_ex": (I, [G, I, I, I, P, G, G, I, P, G, G, P, G, P, I, G, G, P, I, G, G, G, F, I, I, P]),
     "pafc_gemm_ph_ex2": (I, [G, I, I, I, P, G, G, I, I, P, G, G, P, G, P, I, G, G, P, I, G, G, G, F, I, I, P]),
+    "pafc_gemm_ph_ktail": (I, [G, I, I, I, P, G, G, I, I, P, G, G, P, G, P, I, G, G, P, I, G, G, G, F, I, I, P, Z, G, I, P]),
+    "pafc_gemm_ph_ktail_plan": (I, [G, I, I, I, I, I, P]),
     "pafc_conv3x3s2_nhwc_split_ph": (I, [I, I, I, I, I, P, P, P, P, I, I, P]),
     "pafc_residual_dropout": (I, [I, I, I, G, P, P, P, F, F, U, U, P]),
     "pafc_silu_dropout": (I, [I, I, G, P, P, P, F, U, U, P]),

@@ -409,6 +409,21 @@ static int ph_tile_m(long M, int N, int K, int batch, int act, bool has_residual
     return best;
 }
 
+// The tail plan of the phase-pipelined kernel (include/pafc_encoder_ops.h; mirrored by hip_ops._ph_ktail_plan): when the last
+// round of 256 x 256 tiles covers at most half of the CUs, its row tiles run twice as wide -- each tile once per half of K
+// (pafc_gemm_ph_ktail) -- so that the launch pays a half-length round for them instead of a whole one.
+extern "C" int pafc_gemm_ph_ktail_plan(long M, int N, int K, int batch, int cus, int min_k, long *split_row) {
+    if (split_row) *split_row = 0;
+    if (M <= 0 || N <= 0 || K <= 0 || batch != 1 || !split_row) return 0;
+    if (cus <= 0) cus = pafc::device_cus();
+    const long ntiles = (N + 255) / 256, tiles = ((M + 255) / 256) * ntiles;
+    const long full = tiles / cus * cus, tail = tiles - full;
+    if (full <= 0 || tail <= 0 || 2 * tail > cus || full % ntiles) return 0;
+    if (K % 128 || K < min_k) return 0;                     // K / 32 steps: an even number of them in each of two slices
+    *split_row = full / ntiles * 256;
+    return 2;
+}
+
 // GLU row order the dispatcher wants for this problem: 64 (the 128 x 128 kernel's blocks) or 32 (the phase-pipelined one's).
 extern "C" int pafc_gemm_bf16_glu_half(long M, int N, int K, int batch) { return ph_tile_m(M, N, K, batch, 4, false) ? 32 : 64; }
 

@@ -167,7 +167,12 @@ constexpr unsigned PH_OOB = 0xC0000000u;       // a byte offset beyond every des
 //       1 = consumer (SiLU or GLU, alpha 1): A is the UN-normalised stream, W / bias are W' / b', the epilogue applies
 //       rstd (acc - mean csum) + b' per row.  The normalised tensor never exists in memory (encoder_layer.py:201-259 writes
 //       and re-reads it once per sub-block).
-template <bool GLU, int ACT, int RES, int OUT, bool CONV = false, int LNF = 0, bool SPL = false>
+// KSL: K slices (SPL, fp32 out, no bias / residual / activation).  Batch entry z multiplies K-steps [z nt, (z + 1) nt) of the
+//      SAME A and W (sA = sW = 0) into its own output slab: the partial products of a tile whose K range is cut up
+//      (pafc_gemm_ph_ktail).  The slice is a wave-uniform K-step offset where a_soff / w_soff are formed, not moved base
+//      pointers: a slice may start in the middle of a plane block.  An instantiation of its own: the code of the others is
+//      what it was without the flag.
+template <bool GLU, int ACT, int RES, int OUT, bool CONV = false, int LNF = 0, bool SPL = false, bool KSL = false>
 __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     constexpr int BN = PBN;
     constexpr int UA = 128 * 128;                 // bytes of an A unit: 128 rows x 64 k
@@ -188,6 +193,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     static_assert(LNF != 2 || RES == 1, "LNF 2: a residual GEMM");
     static_assert(!(GLU && (ACT != 0 || RES != 0)), "GLU excludes an activation and a residual");
     static_assert(!(RES != 0 && ACT != 0), "the layer never pairs a residual with an activation");
+    static_assert(!KSL || (SPL && !CONV && !GLU && ACT == 0 && RES == 0 && OUT == 1), "K slices: fp32 partial products of split operands");
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];   // 2 x STEP + 8 KiB (bias slots) [+ 8 KiB csum slots + 16 KiB row statistics]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -302,6 +308,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
 #ifdef PH_ABL_NODMA
         return;
 #endif
+        if constexpr (KSL) kt += T.z * nt;
 #pragma unroll
         for (int j = 0; j < DA; ++j)
             dma16(T.Ar, a_off[h][j], a_soff(kt), lds + buf * STEP + (h ? OFF_A1 : OFF_A0) + (wave * DA + j) * 1024);
@@ -310,6 +317,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
 #ifdef PH_ABL_NODMA
         return;
 #endif
+        if constexpr (KSL) kt += T.z * nt;
 #pragma unroll
         for (int j = 0; j < DB; ++j)
             dma16(T.Wr, b_off[h][j], w_soff(kt), lds + buf * STEP + (h ? OFF_B1 : OFF_B0) + (wave * DB + j) * 1024);
@@ -760,12 +768,40 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     PH_WAIT(0);                                   // the (empty) prefetch of a tile that does not exist: nothing in flight at exit
 }
 
-template <bool GLU, int ACT, int RES, int OUT, bool CONV = false, int LNF = 0, bool SPL = false>
+// The epilogue of the K-sliced tiles (pafc_gemm_ph_ktail), over rows x N / 4 quads of 16 bytes:
+//   out[m][n] = fmaf(p_0[m][n] + p_1[m][n] (+ ...), alpha, bias[n]) + residual[m][n]
+// with the fma and the residual add in the order of the pipelined kernel's epilogue.  HBM-bound: every slab, the residual and the
+// output cross memory once.  `res` may be `out` (a lane reads its four values before it writes them); bias / res may be null.
+__global__ __launch_bounds__(256) void gemm_ph_ktail_fixup_kernel(const float *__restrict__ part, long slab, int kslices,
+                                                                  const float *__restrict__ bias, const float *res, long ldr,
+                                                                  float *out, long ldo, long rows, int N, float alpha) {
+    const int nq = N >> 2;
+    const long total = rows * nq;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long m = i / nq;
+        const int n = (int)(i - m * nq) << 2;
+        float4 acc = *reinterpret_cast<const float4 *>(part + m * N + n);
+        for (int z = 1; z < kslices; ++z) {
+            const float4 q = *reinterpret_cast<const float4 *>(part + z * slab + m * N + n);
+            acc.x += q.x; acc.y += q.y; acc.z += q.z; acc.w += q.w;
+        }
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (bias) b = *reinterpret_cast<const float4 *>(bias + n);
+        float4 o = make_float4(fmaf(acc.x, alpha, b.x), fmaf(acc.y, alpha, b.y), fmaf(acc.z, alpha, b.z), fmaf(acc.w, alpha, b.w));
+        if (res) {
+            const float4 r = *reinterpret_cast<const float4 *>(res + m * ldr + n);
+            o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
+        }
+        *reinterpret_cast<float4 *>(out + m * ldo + n) = o;
+    }
+}
+
+template <bool GLU, int ACT, int RES, int OUT, bool CONV = false, int LNF = 0, bool SPL = false, bool KSL = false>
 int launch_ph(const PhParams &p, int batch, hipStream_t s) {
     // two K-steps (128 KiB) + a bias slot per wave
     // (LNF 1: + a csum slot per wave + the tile's row statistics = all 160 KiB)
     constexpr size_t lds = 2 * (2 * 128 * 128 + 2 * (PBN / 2) * 128) + 8 * 1024 + (LNF == 1 ? 8 * 1024 + 16 * 1024 : 0);
-    auto kern = gemm_ph_kernel<GLU, ACT, RES, OUT, CONV, LNF, SPL>;
+    auto kern = gemm_ph_kernel<GLU, ACT, RES, OUT, CONV, LNF, SPL, KSL>;
     static bool attr_set[64];                     // per device; a racing first call sets the same attribute twice
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return PAFC_ERR_LAUNCH;
@@ -1015,4 +1051,81 @@ extern "C" int pafc_conv3x3s2_nhwc_bf16_ph(int B, int T1, int F1, int Ci, int Co
 extern "C" int pafc_conv3x3s2_nhwc_split_ph(int B, int T1, int F1, int Ci, int Co, const void *in_planes, const void *w3_tap_co_3ci,
                                             const float *bias, void *out_planes, int relu, int tile_m, pafc_stream_t stream) {
     return conv_ph_launch(B, T1, F1, Ci, Co, in_planes, w3_tap_co_3ci, bias, out_planes, relu, tile_m, 1, stream);
+}
+
+// pafc_gemm_ph_ex2 for a split-operand, fp32-output problem whose last round of 256-row tiles is short (include/
+// pafc_encoder_ops.h): rows [0, split_row) take the pipelined kernel as they always did; the tiles of rows [split_row, M) run
+// `kslices` times as wide -- every tile once per K slice, each slice a K loop of its own into its own fp32 slab of the
+// workspace -- and a third, HBM-bound launch adds the slabs up and applies alpha, bias and the residual.  Three launches in
+// stream order: no block waits for another, no atomics, the sum's order is fixed.  Everything is checked before the first
+// launch.
+extern "C" int pafc_gemm_ph_ktail(long M, int N, int K, int batch, const void *A, long lda, long strideA, int a_split,
+                                  int a_plane_block, const void *W, long ldw, long strideW, const void *bias, long strideBias,
+                                  const void *residual, int res_kind, long ldr, long strideR, void *out, int out_kind, long ldo,
+                                  long lo_off, long strideO, float alpha, int act, int tile_m, void *workspace,
+                                  size_t workspace_bytes, long split_row, int kslices, pafc_stream_t stream) {
+    if (!A || !W || !out || !workspace) return PAFC_ERR_NULL_POINTER;
+    if (M <= 0 || N <= 0 || K <= 0) return PAFC_ERR_BAD_DIMS;
+    if (act < 0 || act > 4 || out_kind < 0 || out_kind > 2 || res_kind < 0 || res_kind > 2) return PAFC_ERR_UNSUPPORTED;
+    // the forms with a tail split: split operands -> fp32 (+ fp32 residual), 256-row tiles, two slices, one batch entry
+    if (!a_split || out_kind != 1 || act != 0 || batch != 1 || tile_m != 256 || kslices != 2) return PAFC_ERR_UNSUPPORTED;
+    if (!pafc::split_shared_fragments()) return PAFC_ERR_UNSUPPORTED;
+    if (!residual) res_kind = 0;
+    else if (res_kind == 0) return PAFC_ERR_BAD_DIMS;
+    else if (res_kind != 2) return PAFC_ERR_UNSUPPORTED;
+    if (split_row < 0 || split_row >= M || split_row % 256) return PAFC_ERR_BAD_DIMS;
+    if (K % (64 * kslices)) return PAFC_ERR_BAD_DIMS;           // K / 32 steps, an even number of them in every slice
+    if (N % 8) return PAFC_ERR_UNSUPPORTED;
+    const long rows = M - split_row;
+    if (workspace_bytes < (size_t)kslices * (size_t)rows * (size_t)N * sizeof(float)) return PAFC_ERR_BAD_DIMS;
+    if (lda < 2 * (long)K || ldw < 3 * (long)K || (residual && ldr < N) || ldo < N) return PAFC_ERR_BAD_DIMS;
+    if ((lda | ldw) % 8 || ldo % 8 || (residual && ldr % 8)) return PAFC_ERR_ALIGNMENT;
+    if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)out | (uintptr_t)residual | (uintptr_t)bias | (uintptr_t)workspace) & 15) != 0)
+        return PAFC_ERR_ALIGNMENT;
+    if ((double)M * lda * 2 >= 2.0e9 || (double)N * ldw * 2 >= 2.0e9 || (double)2 * K * 2 + 64 >= 2.0e9) return PAFC_ERR_UNSUPPORTED;
+    if ((double)256 * ldo * 4 >= 2.0e9 || (residual && (double)256 * ldr * 4 >= 2.0e9)) return PAFC_ERR_UNSUPPORTED;
+    int pb_shift = 30;
+    long pb_bytes = (long)K * 2;
+    if (a_plane_block) {
+        int sh = 0;
+        while ((64 << sh) < a_plane_block) ++sh;
+        if ((64 << sh) != a_plane_block || K % a_plane_block) return PAFC_ERR_UNSUPPORTED;
+        pb_shift = sh + 1;
+        pb_bytes = (long)a_plane_block * 2;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // 1. the full rounds, final epilogue and all
+    if (split_row > 0) {
+        const int rc = pafc_gemm_ph_ex2(split_row, N, K, 1, A, lda, strideA, 1, a_plane_block, W, ldw, strideW, bias, strideBias,
+                                        residual, res_kind, ldr, strideR, out, 1, ldo, lo_off, strideO, alpha, 0, 256, stream);
+        if (rc != PAFC_OK) return rc;
+    }
+    // 2. the tail's tiles, once per K slice (batch entry z = slice z of the same A and W), into slab z of the workspace
+    pafc::PhParams p{};
+    p.A = (const pafc::bf16_t *)A + split_row * lda; p.W = (const pafc::bf16_t *)W; p.out = workspace;
+    p.M = rows; p.N = N; p.K = 3 * K;
+    p.lda = lda; p.ldw = ldw; p.ldo = N;
+    p.sO = rows * N;
+    p.alpha = 1.f;
+    p.nk1 = K / 64;
+    p.pb_shift = pb_shift;                        // (in 32-column steps)
+    p.pb_bytes = pb_bytes;
+    p.nsteps = K / 32 / kslices;
+    p.a_lo = (int)pb_bytes;
+    p.w_lo = 2 * K * 2;
+    p.w_step = 64;
+    p.tm = 256;
+    p.mtiles = (int)((rows + 255) / 256);
+    p.ntiles = (N + 255) / 256;
+    const int rc = pafc::launch_ph<false, 0, 0, 1, false, 0, true, true>(p, kslices, s);
+    if (rc != PAFC_OK) return rc;
+    // 3. slabs -> out
+    const long quads = rows * (N / 4);
+    const long cap = (long)pafc::device_cus() * 32;
+    const long blocks = (quads + 255) / 256;
+    hipLaunchKernelGGL(pafc::gemm_ph_ktail_fixup_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, s,
+                       (const float *)workspace, rows * N, kslices, (const float *)bias,
+                       residual ? (const float *)residual + split_row * ldr : nullptr, ldr, (float *)out + split_row * ldo, ldo, rows, N,
+                       alpha);
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }

@@ -65,12 +65,19 @@ from .utils import graph_step
 #                                   (fused.layer_forward_split) from this many rows on -- since round 6 also below
 #                                   split_gemm_min_rows, where their projections run on the small tiles (a single 2 000-frame
 #                                   window is 499 rows: exact fp32 products on the fp32 matrix cores cost 12-55 us each there)
+#   ktail_min_k              2048  split-operand fp32-output products whose last round of 256 x 256 tiles covers at most half of the
+#                                   CUs run that round's row tiles once per half of K plus a fix-up pass (_ph_ktail_plan,
+#                                   pafc_gemm_ph_ktail) from this K on.  44 998 rows x N = 512 (352 tiles on 256 CUs), one launch
+#                                   -> three, residual form / plain form: K = 1024 162 -> 167 / 134 -> 146 us, 1536 218 -> 214 /
+#                                   189 -> 194, 2048 265 -> 257 / 241 -> 240, 4096 475 -> 447 / 455 -> 430, 9728 1085 -> 963 /
+#                                   1082 -> 952 (profiles/gemm_ph_ktail_shapes.jsonl; DESIGN "K-split of the last partial round")
 # C side (csrc/gemm_bf16.hip): which GEMM family takes a problem is decided by rounds -- the 128-wide kernel while its 128 x 128
 # tiles fit one round of two per CU, the 256-wide phase-pipelined kernel beyond (profiles/r04s_gemm_tile_choice_by_rows.txt);
 # PAFC_PH_MIN_FILL=<percent> (round 3's rule: 256-wide tiles must cover that share of the CUs) and PAFC_GEMM_TILE (force a tile
 # of the small kernel) are A/B switches of the kernels themselves.
 DISPATCH = dict(skinny_max_rows=640, own_gemm_min_rows=1, lds_resident_min_rows=8192, split_gemm_min_rows=1024,
-                ln_fold_min_rows=24576, dwconv_ln_silu_max_rows=24575, split_small_max_rows=8192, split_layers_min_rows=256)
+                ln_fold_min_rows=24576, dwconv_ln_silu_max_rows=24575, split_small_max_rows=8192, split_layers_min_rows=256,
+                ktail_min_k=2048)
 
 
 def _load_dispatch():
@@ -1680,14 +1687,37 @@ def _ph_tile_m(M: int, N: int, batch: int = 1, min_tm: int = 64) -> int:
     return best[1]
 
 
+def _ph_ktail_plan(M: int, N: int, K: int, cus: int, batch: int = 1, min_k: Optional[int] = None):
+    """The tail plan of a split-operand, fp32-output problem on 256-row tiles (as csrc/gemm_bf16.hip:pafc_gemm_ph_ktail_plan):
+    (split_row, kslices = 2) when the last round of one-tile-per-CU work covers at most half of the CUs -- its row tiles then
+    run once per half of K (pafc_gemm_ph_ktail) -- or None.  At most one tail round is split, and in two."""
+    min_k = DISPATCH["ktail_min_k"] if min_k is None else min_k
+    if M <= 0 or N <= 0 or K <= 0 or batch != 1 or cus <= 0:
+        return None
+    ntiles = (N + 255) // 256
+    tiles = ((M + 255) // 256) * ntiles
+    full = tiles // cus * cus
+    tail = tiles - full
+    if full <= 0 or tail <= 0 or 2 * tail > cus or full % ntiles:
+        return None
+    if K % 128 or K < min_k:            # K / 32 steps: an even number of them in each of the two slices
+        return None
+    return full // ntiles * 256, 2
+
+
+_TAIL_AUTO = object()           # tail_split left to _ph_ktail_plan
+
+
 def gemm_ph_ex(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act: str = "none", alpha: float = 1.0,
                residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, a_split: bool = False,
-               out_kind: str = "bf16", tile_m: int = 0, a_plane_block: int = 0) -> torch.Tensor:
+               out_kind: str = "bf16", tile_m: int = 0, a_plane_block: int = 0, tail_split=_TAIL_AUTO) -> torch.Tensor:
     """The phase-pipelined GEMM with every operand form (include/pafc_encoder_ops.h: pafc_gemm_ph_ex).
     a: (M, K) bf16, or with a_split (M, 2K) planes [hi | lo] of an fp32 activation, then w: (N, 3K) = split_planes(W, triple=True);
     out_kind "bf16" | "f32" | "planes" ((M, 2N) bf16 = [hi | lo] of the fp32 result); residual bf16 (out bf16) or fp32 (out f32),
     may be `out`; bias bf16 for out_kind bf16, fp32 otherwise; act as gemm_bf16 (GLU: glu_interleave(w, 32) rows before splitting).
-    a_plane_block: the planes of a split `a` alternate in blocks of that many columns ([hi PB | lo PB] ...; 0: [hi K | lo K])."""
+    a_plane_block: the planes of a split `a` alternate in blocks of that many columns ([hi PB | lo PB] ...; 0: [hi K | lo K]).
+    tail_split: (split_row, kslices) runs the rows from split_row on as K slices + a fix-up pass (pafc_gemm_ph_ktail); None /
+    False: one launch; by default _ph_ktail_plan decides (split operands -> fp32 without an activation, no tile_m given)."""
     _lib.require_gpu(bias)
     for t in (a, w, residual, out):
         if t is not None and (not t.is_cuda or t.stride(-1) != 1):
@@ -1717,7 +1747,7 @@ def gemm_ph_ex(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
     from .profiling import op_timer
     pb_ok = not a_plane_block or (a_split and a_plane_block >= 64 and a_plane_block & (a_plane_block - 1) == 0 and K % a_plane_block == 0)
     if (M <= _SPLIT_SMALL_MAX_ROWS and M * N <= _SPLIT_SMALL_MAX_OUT and ok != 0 and act in ("none", "silu", "tanh", "relu")
-            and pb_ok and not tile_m and K % 64 == 0):
+            and pb_ok and not tile_m and K % 64 == 0 and (tail_split is _TAIL_AUTO or not tail_split)):
         # few rows: the small tiles of csrc/gemm_bf16.hip (same operand forms, same epilogue order)
         nws = L.pafc_gemm_bf16_f32out_workspace_bytes(M, N, K, int(a_split))     # > 0: few rows x long K, K split over blocks
         ws = torch.empty(nws, dtype=torch.uint8, device=a.device) if nws else None
@@ -1727,6 +1757,24 @@ def gemm_ph_ex(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = 
                                             _lib.ptr(out), ok, out.stride(0), No if ok == 2 else 0, float(alpha), _ACTS[act], _lib.ptr(ws),
                                             nws, _lib.stream_of(a))
         _lib.check(rc, "pafc_gemm_bf16_f32out")
+        return out
+    if tail_split is _TAIL_AUTO:
+        tail_split = None
+        if a_split and ok == 1 and act == "none" and not tile_m and os.environ.get("PAFC_SPLIT_WALK") != "hilohi":
+            cus = torch.cuda.get_device_properties(a.device).multi_processor_count
+            tail_split = _ph_ktail_plan(M, N, K, cus)
+    if tail_split:
+        split_row, kslices = tail_split
+        # the slices' partial products: allocated on the current stream (capture-safe, one per call: batches in flight share nothing)
+        nws = max(0, kslices * (M - split_row) * N * 4)
+        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=a.device)
+        with op_timer("gemm%s_%dx%d" % ("3" if a_split else "", K, N), sample=12, flops=2.0 * M * N * K * (3 if a_split else 1)):
+            rc = L.pafc_gemm_ph_ktail(M, N, K, 1, _lib.ptr(a), a.stride(0), 0, int(a_split), int(a_plane_block), _lib.ptr(w),
+                                      w.stride(0), 0, _lib.ptr(bias), 0, _lib.ptr(residual), rk,
+                                      residual.stride(0) if residual is not None else 0, 0, _lib.ptr(out), ok, out.stride(0),
+                                      No if ok == 2 else 0, 0, float(alpha), _ACTS[act], int(tile_m or 256), _lib.ptr(ws), nws,
+                                      int(split_row), int(kslices), _lib.stream_of(a))
+        _lib.check(rc, "pafc_gemm_ph_ktail")
         return out
     with op_timer("gemm%s_%dx%d" % ("3" if a_split else "", K, N), sample=12, flops=2.0 * M * N * K * (3 if a_split else 1)):
         rc = L.pafc_gemm_ph_ex2(M, N, K, 1, _lib.ptr(a), a.stride(0), 0, int(a_split), int(a_plane_block), _lib.ptr(w), w.stride(0), 0,
