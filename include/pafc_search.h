@@ -300,6 +300,41 @@ int pafc_rnnt_greedy_stream_drain(const pafc_rnnt_greedy_net *net, int B, int Tm
                                   size_t workspace_bytes, int ld, int32_t *tokens, int64_t *frames, int32_t *ntok, double *score,
                                   int32_t *running, pafc_stream_t stream);
 
+/* Full-sum transducer score log p(y | x) of n-best lists (the second pass of transducer_attention_rescoring,
+ * wenet/transducer/transducer.py:185-210, without its beam-fold repeat of the encoder output): the hypotheses of one utterance
+ * are scored over the trie of their prefixes.  A lattice column ("arc") of utterance b is (node, label) for every child edge of
+ * a trie node, or (node, none) for a node without children; K_b arcs.  Rows are (b, t, k): r = off_b + t K_b + k, off_b the rows
+ * of the group's earlier utterances.  h_r = bf16(tanh(E[enc_b, t] + Pnode[prow_k])) (add and tanh in fp32, one rounding),
+ * z_r = W h_r + bias accumulated in fp32, never rounded, never stored; per row lse, z[blank] and z[label_k] -- the rounding points
+ * and the kernels (join, stats epilogue, lse) of pafc_rnnt_joint_loss_forward.  Then one block per hypothesis runs that forward's
+ * alpha recurrence (fp32, "log 0" = -1e30, lse2(alpha(t-1, u) + lp_blank, alpha(t, u-1) + lp_label)) with lp_blank / lp_label of
+ * (t, u) read from column col[n][u], and score[n] = alpha(T_b - 1, U_n) + lp_blank(T_b - 1, U_n): bit for bit -nll of
+ * pafc_rnnt_joint_loss_forward fed that hypothesis alone (its encoder rows, its own predictor rows, its labels).  U_n > T_b is fine.
+ * E: (Benc, T, J) bf16 in rows of lde, utterances strideE apart, passed once per utterance.  Pnode: (prows, J) bf16 in rows of
+ * ldp: pred_ffn of the predictor's output after each prefix.  W (V, J), bias (V) or NULL: bf16.  hlens: (Benc) device int32 frames, or
+ * NULL when the caller built the tables from lengths it holds on the host (then T_b is taken as it is).
+ * The tables: one int32 array, given twice -- tab_host for validation and sizing, tab_dev (the same values on the device) for the
+ * kernels, as pafc_fbank_stream_rows takes its rows -- laid out as
+ *   utt_enc (nutt): the row of E / hlens of utterance b (several utterances may share one: every hypothesis its own utterance
+ *     scores without sharing);  utt_T (nutt): its frames T_b;  arc_off, hyp_off (nutt + 1 each): its first arc / hypothesis;
+ *   arc_prow, arc_label (narc each): the row of Pnode of the arc's node, and its label or -1;
+ *   hyp_utt, hyp_len (nhyp each): utterance and U_n;  col_off (nhyp + 1);  col (ncol): col_off[n] + u holds the column, in
+ *     [0, K_b), of position u <= U_n -- for u < U_n the arc (y[:u], y[u]), for u = U_n any arc of node y[:U_n].
+ * One call scores the utterances [utt0, utt1) and writes score[hyp_off[utt0] .. hyp_off[utt1]) of score (nhyp) fp32; the caller
+ * bounds the workspace by cutting the batch into such groups.  Before anything is launched the group's tables are checked on the
+ * host copy: offsets monotonic and inside the arrays, utt_enc in [0, Benc), T_b in [1, T], prow in [0, prows), labels in [-1, V),
+ * columns in [0, K_b) and labelled where u < U_n, else PAFC_ERR_BAD_DIMS.  A hypothesis whose utterance has hlens[enc_b] != T_b on
+ * the device (a length outside E, or not the one the tables were built from) gets NaN.  Limits of the training forward: J % 64 == 0, V % 8 == 0, U_n + 1 <= 2559, nutt <= 65535, else
+ * PAFC_ERR_UNSUPPORTED; lde, strideE, ldp multiples of 8, E / Pnode / W 16-byte and the workspace 256-byte aligned, else
+ * PAFC_ERR_ALIGNMENT.  workspace: pafc_rnnt_score_workspace_bytes(utt1 - utt0, J, V, rows of the group) bytes
+ * (rows x (2 J + 8 ceil(V / 128) + 16) and the offsets).  No float atomics, nothing reads the host or allocates after the checks:
+ * two calls give the same bits. */
+size_t pafc_rnnt_score_workspace_bytes(int nutt, int J, int V, long rows);
+int pafc_rnnt_score(int Benc, int T, int J, int V, const void *E, long lde, long strideE, const void *Pnode, long ldp, long prows,
+                    const void *W, const void *bias, const int32_t *hlens, int nutt, int nhyp, int narc, int ncol,
+                    const int32_t *tab_host, const int32_t *tab_dev, int utt0, int utt1, int blank, float *score, void *workspace,
+                    size_t workspace_bytes, pafc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,8 @@ SIGNATURES = {
     "pafc_rnnt_greedy_stream_reset": (I, [P, I, I, I, I, P, P, Z, P]),
     "pafc_rnnt_greedy_stream_feed": (I, [P, I, I, I, I, P, P, Z, P, P]),
     "pafc_rnnt_greedy_stream_drain": (I, [P, I, I, I, P, Z, I, P, P, P, P, P, P]),
+    "pafc_rnnt_score_workspace_bytes": (Z, [I, I, I, G]),
+    "pafc_rnnt_score": (I, [I, I, I, I, P, G, G, P, G, G, P, P, P, I, I, I, I, P, P, I, I, I, P, P, Z, P]),
     # include/pafc_wkv6.h
     "pafc_abi_version": (I, []),
     "pafc_selftest_lane_ops": (I, [P, P]),

@@ -21,11 +21,16 @@
 //             dW, db += dz^T H (pafc_gemm_tn_bf16, summed over slabs in slab order); dpre = dH (1 - h^2) reduced in a fixed
 //             order into dE[n][t] = sum_u dpre and dP[n][u] = sum_t dpre.
 // No float atomics: forward and backward are bitwise reproducible.
+//
+// pafc_rnnt_score (include/pafc_search.h) scores n-best lists with the same join, stats and lse kernels: its rows are (utterance,
+// frame, arc of the hypotheses' prefix trie) instead of (utterance, frame, label count), and its lattice kernel keeps the alpha
+// pass only.  A hypothesis scored there has the bits of -nll of the training forward fed that hypothesis alone.
 #include <math.h>
 #include <vector>
 
 #include "pafc_common.h"
 #include "../../include/pafc_encoder_ops.h"
+#include "../../include/pafc_search.h"
 
 namespace pafc {
 namespace {
@@ -54,6 +59,21 @@ __device__ __forceinline__ float lse2(float a, float b) {
     return m <= NEG ? NEG : m + logf(expf(a - m) + expf(b - m));
 }
 
+// 8 columns of h = bf16(tanh(e + p)): the add and tanh in fp32, one rounding (the join of the training forward and of the scorer)
+__device__ __forceinline__ uint4 join8(const bf16_t *ep, const bf16_t *pp) {
+    float e[8], p[8], h[8];
+    Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(ep), e);
+    Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(pp), p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = tanhf(e[i] + p[i]);
+    uint4 o;
+    o.x = f32_to_bf16_bits(h[0]) | (f32_to_bf16_bits(h[1]) << 16);
+    o.y = f32_to_bf16_bits(h[2]) | (f32_to_bf16_bits(h[3]) << 16);
+    o.z = f32_to_bf16_bits(h[4]) | (f32_to_bf16_bits(h[5]) << 16);
+    o.w = f32_to_bf16_bits(h[6]) | (f32_to_bf16_bits(h[7]) << 16);
+    return o;
+}
+
 __global__ void rnnt_offsets_kernel(int B, int T, int Up1, int ldy, const int32_t *hlens, const int32_t *ylens, int64_t *off) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int64_t acc = 0;
@@ -78,15 +98,7 @@ __global__ __launch_bounds__(256) void rnnt_join_kernel(long R, int B, int J, co
         const int n = find_utt(off, B, r);
         const int U1 = ylens[n] + 1;
         const long k = r - off[n], t = k / U1, u = k % U1;
-        float e[8], p[8], h[8];
-        Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(E + n * sE + t * lde + c), e);
-        Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(P + n * sP + u * ldp + c), p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i] = tanhf(e[i] + p[i]);
-        o.x = f32_to_bf16_bits(h[0]) | (f32_to_bf16_bits(h[1]) << 16);
-        o.y = f32_to_bf16_bits(h[2]) | (f32_to_bf16_bits(h[3]) << 16);
-        o.z = f32_to_bf16_bits(h[4]) | (f32_to_bf16_bits(h[5]) << 16);
-        o.w = f32_to_bf16_bits(h[6]) | (f32_to_bf16_bits(h[7]) << 16);
+        o = join8(E + n * sE + t * lde + c, P + n * sP + u * ldp + c);
     }
     *reinterpret_cast<uint4 *>(H + r * J + c) = o;
 }
@@ -106,6 +118,8 @@ struct RnntGemm {
     float scale;
     bf16_t *dz;
     long ldz;                     // Vp
+    // stats of the hypothesis scorer (MODE 0): null, or the label of row r, written by its join (-1: the row has none)
+    const int32_t *rowlab;
 };
 
 __device__ __forceinline__ void rdma16(const bf16_t *src, bf16_t *lds_base) {
@@ -125,7 +139,8 @@ __device__ __forceinline__ int row_label(const RnntGemm &p, long r, int *n_out) 
 }
 
 // 256 threads (2 x 2 waves), tile 128 x 128 x 64, MFMA 16x16x32 bf16, two LDS stages filled by LDS-DMA with the XOR swizzle on
-// the source side: the loop of gemm_bf16_kernel<0>.  MODE 0: row statistics epilogue; MODE 1: dz epilogue.
+// the source side: the loop of gemm_bf16_kernel<0>.  MODE 0: row statistics epilogue (the row's label from ys / ylens, or from
+// rowlab when that is given: the arc tables of pafc_rnnt_score); MODE 1: dz epilogue.
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void rnnt_gemm_kernel(const RnntGemm p) {
     extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
@@ -236,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void rnnt_gemm_kernel(const RnntGemm p) {
             const float *full = O + row * LDF;
             if (p.blank >= n0 && p.blank < n0 + RBN) p.zb[r] = full[p.blank - n0];
             int n;
-            const int y = row_label(p, r, &n);
+            const int y = p.rowlab ? p.rowlab[r] : row_label(p, r, &n);
             if (y >= n0 && y < n0 + RBN && y < p.N) p.zy[r] = full[y - n0];
         }
     } else {
@@ -289,7 +304,8 @@ __global__ __launch_bounds__(256, 2) void rnnt_gemm_kernel(const RnntGemm p) {
     }
 }
 
-// lse_r from the tiles' partials; g_B / g_L cleared (the lattice writes the rows of its utterances)
+// lse_r from the tiles' partials; g_B / g_L cleared (the lattice writes the rows of its utterances; null for the scorer, which
+// has no gradients)
 __global__ __launch_bounds__(256) void rnnt_lse_kernel(long R, int ntiles, const float *pmax, const float *psum, float *lse, float *gB,
                                                        float *gL) {
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
@@ -299,8 +315,10 @@ __global__ __launch_bounds__(256) void rnnt_lse_kernel(long R, int ntiles, const
     float s = 0.f;
     for (int nt = 0; nt < ntiles; ++nt) s += psum[(long)nt * R + r] * expf(pmax[(long)nt * R + r] - M);
     lse[r] = M + logf(s);
-    gB[r] = 0.f;
-    gL[r] = 0.f;
+    if (gB) {
+        gB[r] = 0.f;
+        gL[r] = 0.f;
+    }
 }
 
 // one block per utterance, a thread per label count u on each anti-diagonal d = t + u.  LDS: the previous diagonal's alpha,
@@ -517,6 +535,136 @@ int launch_gemm(int mode, const RnntGemm &g, hipStream_t s) {
     return PAFC_OK;
 }
 
+
+// ---- hypothesis scorer (pafc_rnnt_score, include/pafc_search.h) ------------------------------------------------------------------
+// The packed int32 tables of one batch of n-best lists, in this order (transducer/search/rescoring.py builds them).  The same
+// view serves the host copy (validation, sizing) and the device copy (kernels).
+struct ScoreTab {
+    const int32_t *utt_enc, *utt_T;       // (nutt) row of E / hlens, and frames T_b
+    const int32_t *arc_off, *hyp_off;     // (nutt + 1) first arc / first hypothesis of utterance b
+    const int32_t *arc_prow, *arc_label;  // (narc) row of Pnode of the arc's node, its label or -1
+    const int32_t *hyp_utt, *hyp_len;     // (nhyp)
+    const int32_t *col_off;               // (nhyp + 1) first entry of col of hypothesis n
+    const int32_t *col;                   // (ncol) column (arc of its utterance) of position u
+};
+
+inline ScoreTab score_tab(const int32_t *t, int nutt, int nhyp, int narc) {
+    ScoreTab S;
+    S.utt_enc = t; t += nutt;
+    S.utt_T = t; t += nutt;
+    S.arc_off = t; t += nutt + 1;
+    S.hyp_off = t; t += nutt + 1;
+    S.arc_prow = t; t += narc;
+    S.arc_label = t; t += narc;
+    S.hyp_utt = t; t += nhyp;
+    S.hyp_len = t; t += nhyp;
+    S.col_off = t; t += nhyp + 1;
+    S.col = t;
+    return S;
+}
+
+// one thread: off[i] = rows of the utterances [utt0, utt0 + i) of the group, T_b K_b each (the tables' T_b: validated on the host)
+__global__ void rnnt_score_offsets_kernel(ScoreTab S, int utt0, int nu, int64_t *off) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int64_t acc = 0;
+    for (int i = 0; i < nu; ++i) {
+        off[i] = acc;
+        const int b = utt0 + i;
+        const int K = S.arc_off[b + 1] - S.arc_off[b];
+        if (K > 0) acc += (int64_t)S.utt_T[b] * K;
+    }
+    off[nu] = acc;
+}
+
+// rnnt_join_kernel over arcs: row r = off_b + t K_b + k is h = join8(E[enc_b][t], Pnode[prow[k]]); the thread of column 0 also
+// writes the row's label
+__global__ __launch_bounds__(256) void rnnt_score_join_kernel(long R, int utt0, int nu, int J, const bf16_t *E, long lde, long sE,
+                                                              const bf16_t *P, long ldp, ScoreTab S, const int64_t *off, bf16_t *H,
+                                                              int32_t *rowlab) {
+    const int cpr = J / 8;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= R * cpr) return;
+    const long r = q / cpr;
+    const int c = (int)(q % cpr) * 8;
+    uint4 o = make_uint4(0, 0, 0, 0);
+    int lab = -1;
+    if (r < off[nu]) {
+        const int i = find_utt(off, nu, r), b = utt0 + i;
+        const int a0 = S.arc_off[b], K = S.arc_off[b + 1] - a0;
+        const long k = r - off[i], t = k / K;
+        const int a = a0 + (int)(k % K);
+        o = join8(E + S.utt_enc[b] * sE + t * lde + c, P + S.arc_prow[a] * ldp + c);
+        lab = S.arc_label[a];
+    }
+    *reinterpret_cast<uint4 *>(H + r * J + c) = o;
+    if (c == 0) rowlab[r] = lab;
+}
+
+// one block per hypothesis, a thread per label count u on each anti-diagonal d = t + u: the alpha pass of rnnt_lattice_kernel
+// (the same fp32 recurrence, operand order and "log 0") with lp_blank / lp_label read through the hypothesis's columns; nothing
+// but the score is written.  LDS: alpha, lp_blank, lp_label of the previous diagonal indexed by u, two buffers.
+__global__ __launch_bounds__(256) void rnnt_score_lattice_kernel(long R, int Benc, int T, int Umax1, int utt0, int hyp0, ScoreTab S,
+                                                                 const int32_t *hlens, const int64_t *off, const float *zb,
+                                                                 const float *zy, const float *lse, float *score) {
+    extern __shared__ float sh[];                 // [2][3][Umax1 + 1]
+    __shared__ float ll_sh;
+    const int n = hyp0 + blockIdx.x, b = S.hyp_utt[n], Un = S.hyp_len[n];
+    const int Tn = S.utt_T[b], a0 = S.arc_off[b], K = S.arc_off[b + 1] - a0;
+    const long base = off[b - utt0];
+    if ((hlens && hlens[S.utt_enc[b]] != Tn) || Tn < 1 || Tn > T || Un + 1 > Umax1 || base + (long)Tn * K > R) {
+        if (threadIdx.x == 0) score[n] = __int_as_float(0x7fc00000);   // the device length is outside E or not the tables': NaN
+        return;
+    }
+    const int U1 = Un + 1, W = Umax1 + 1;
+    const int32_t *col = S.col + S.col_off[n];
+    for (int d = 0; d < Tn + Un; ++d) {
+        const float *pa = sh + ((d + 1) & 1) * 3 * W, *pb = pa + W, *pl = pb + W;
+        float *ca = sh + (d & 1) * 3 * W, *cb = ca + W, *cl = cb + W;
+        for (int u = threadIdx.x; u < U1; u += blockDim.x) {
+            const int t = d - u;
+            float a = NEG, bl = NEG, l = NEG;
+            if (t >= 0 && t < Tn) {
+                const long r = base + (long)t * K + col[u];
+                const float ls = lse[r];
+                bl = zb[r] - ls;
+                if (u < Un) l = zy[r] - ls;
+                if (d == 0) a = 0.f;
+                else a = lse2(t >= 1 ? pa[u] + pb[u] : NEG, u >= 1 ? pa[u - 1] + pl[u - 1] : NEG);
+                if (t == Tn - 1 && u == Un) ll_sh = a + bl;
+            }
+            ca[u] = a; cb[u] = bl; cl[u] = l;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) score[n] = ll_sh;
+}
+
+struct ScoreLayout {
+    int64_t *off;
+    bf16_t *H;
+    float *pmax, *psum, *zb, *zy, *lse;
+    int32_t *rowlab;
+    size_t bytes;
+};
+
+ScoreLayout score_layout(void *ws, int nu, int J, int V, long R) {
+    ScoreLayout L{};
+    char *p = (char *)ws;
+    size_t o = 0;
+    const int nt = (V + RBN - 1) / RBN;
+    auto take = [&](size_t b) { char *q = p ? p + o : nullptr; o += al256(b); return q; };
+    L.off = (int64_t *)take((size_t)(nu + 1) * sizeof(int64_t));
+    L.H = (bf16_t *)take((size_t)R * J * sizeof(bf16_t));
+    L.pmax = (float *)take((size_t)nt * R * sizeof(float));
+    L.psum = (float *)take((size_t)nt * R * sizeof(float));
+    float **rows[] = {&L.zb, &L.zy, &L.lse};
+    for (float **f : rows) *f = (float *)take((size_t)R * sizeof(float));
+    L.rowlab = (int32_t *)take((size_t)R * sizeof(int32_t));
+    L.bytes = o;
+    return L;
+}
+
+constexpr int kMaxScoreU1 = 2559;     // U + 1: the lattice LDS of the training forward
 }  // namespace
 }  // namespace pafc
 
@@ -638,6 +786,76 @@ int pafc_rnnt_joint_loss_backward(int B, int T, int Up1, int J, int V, const voi
             hipLaunchKernelGGL(rnnt_dP_kernel<bf16_t>, gp, dim3(256), 0, s, u0, Up1, J, hlens, ylens, F.off, row0, rows, S.dH, F.H, (bf16_t *)dP);
         }
     }
+    return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+size_t pafc_rnnt_score_workspace_bytes(int nutt, int J, int V, long rows) {
+    if (nutt <= 0 || J <= 0 || V <= 0 || rows <= 0) return 0;
+    return pafc::score_layout(nullptr, nutt, J, V, rows).bytes;
+}
+
+int pafc_rnnt_score(int Benc, int T, int J, int V, const void *E, long lde, long strideE, const void *Pnode, long ldp, long prows,
+                    const void *W, const void *bias, const int32_t *hlens, int nutt, int nhyp, int narc, int ncol,
+                    const int32_t *tab_host, const int32_t *tab_dev, int utt0, int utt1, int blank, float *score, void *workspace,
+                    size_t workspace_bytes, pafc_stream_t stream) {
+    using namespace pafc;
+    if (!E || !Pnode || !W || !tab_host || !tab_dev || !score || !workspace) return PAFC_ERR_NULL_POINTER;
+    if (Benc <= 0 || T <= 0 || J <= 0 || V <= 0 || prows <= 0 || nutt <= 0 || nutt > kMaxB || nhyp < 0 || narc < 0 || ncol < 0 ||
+        utt0 < 0 || utt1 <= utt0 || utt1 > nutt || lde < J || ldp < J || strideE < (long)(T - 1) * lde + J || blank < 0 || blank >= V)
+        return PAFC_ERR_BAD_DIMS;
+    if (J % 64 || V % 8 || V < 8) return PAFC_ERR_UNSUPPORTED;
+    if ((lde | strideE | ldp) % 8) return PAFC_ERR_ALIGNMENT;
+    if ((((uintptr_t)E | (uintptr_t)Pnode | (uintptr_t)W) & 15) != 0 || ((uintptr_t)workspace & 255) != 0) return PAFC_ERR_ALIGNMENT;
+    // ---- the tables of this group, on the host copy: everything a kernel indexes with is in range ----
+    const ScoreTab S = score_tab(tab_host, nutt, nhyp, narc);
+    long R = 0;
+    int Umax1 = 1;
+    for (int b = utt0; b < utt1; ++b) {
+        const int a0 = S.arc_off[b], a1 = S.arc_off[b + 1], h0 = S.hyp_off[b], h1 = S.hyp_off[b + 1];
+        if (a0 < 0 || a1 < a0 || a1 > narc || h0 < 0 || h1 < h0 || h1 > nhyp) return PAFC_ERR_BAD_DIMS;
+        if ((h1 > h0) != (a1 > a0)) return PAFC_ERR_BAD_DIMS;                 // arcs without hypotheses, or the reverse
+        const int K = a1 - a0;
+        if (K == 0) continue;                                                 // an utterance without hypotheses has no rows
+        if (S.utt_enc[b] < 0 || S.utt_enc[b] >= Benc || S.utt_T[b] < 1 || S.utt_T[b] > T) return PAFC_ERR_BAD_DIMS;
+        for (int a = a0; a < a1; ++a)
+            if (S.arc_prow[a] < 0 || S.arc_prow[a] >= prows || S.arc_label[a] < -1 || S.arc_label[a] >= V) return PAFC_ERR_BAD_DIMS;
+        for (int n = h0; n < h1; ++n) {
+            const int U = S.hyp_len[n], c0 = S.col_off[n];
+            if (S.hyp_utt[n] != b || U < 0 || c0 < 0 || S.col_off[n + 1] - c0 != U + 1 || S.col_off[n + 1] > ncol) return PAFC_ERR_BAD_DIMS;
+            if (U + 1 > kMaxScoreU1) return PAFC_ERR_UNSUPPORTED;
+            for (int u = 0; u <= U; ++u) {
+                const int k = S.col[c0 + u];
+                if (k < 0 || k >= K || (u < U && S.arc_label[a0 + k] < 0)) return PAFC_ERR_BAD_DIMS;
+            }
+            if (U + 1 > Umax1) Umax1 = U + 1;
+        }
+        R += (long)S.utt_T[b] * K;
+    }
+    const int hyp0 = S.hyp_off[utt0], nh = S.hyp_off[utt1] - hyp0, nu = utt1 - utt0;
+    if (nh == 0) return PAFC_OK;                                              // a group without hypotheses has no rows
+    const long mt = (R + RBM - 1) / RBM, ntl = (V + RBN - 1) / RBN;
+    if (mt * ntl > 0x7fffffffL || R * (J / 8) / 256 > 0x7fffffffL) return PAFC_ERR_UNSUPPORTED;
+    if (workspace_bytes < pafc_rnnt_score_workspace_bytes(nu, J, V, R)) return PAFC_ERR_WORKSPACE;
+    // ---- device ----
+    const ScoreTab D = score_tab(tab_dev, nutt, nhyp, narc);
+    const ScoreLayout L = score_layout(workspace, nu, J, V, R);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rnnt_score_offsets_kernel, dim3(1), dim3(64), 0, s, D, utt0, nu, L.off);
+    const long q = R * (J / 8);
+    hipLaunchKernelGGL(rnnt_score_join_kernel, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, s, R, utt0, nu, J, (const bf16_t *)E,
+                       lde, strideE, (const bf16_t *)Pnode, ldp, D, L.off, L.H, L.rowlab);
+    RnntGemm g{};
+    g.A = L.H; g.W = (const bf16_t *)W; g.bias = (const bf16_t *)bias;
+    g.M = R; g.row0 = 0; g.R = R; g.N = V; g.K = J;
+    g.mtiles = (int)mt; g.ntiles = (int)ntl;
+    g.blank = blank; g.rowlab = L.rowlab;
+    g.pmax = L.pmax; g.psum = L.psum; g.zb = L.zb; g.zy = L.zy;
+    if (launch_gemm(0, g, s) != PAFC_OK) return PAFC_ERR_LAUNCH;
+    hipLaunchKernelGGL(rnnt_lse_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, R, g.ntiles, L.pmax, L.psum, L.lse,
+                       (float *)nullptr, (float *)nullptr);
+    hipLaunchKernelGGL(rnnt_score_lattice_kernel, dim3(nh), dim3(Umax1 <= 64 ? 64 : Umax1 <= 128 ? 128 : 256),
+                       (size_t)6 * (Umax1 + 1) * sizeof(float), s, R, Benc, T, Umax1, utt0, hyp0, D, hlens, L.off, L.zb, L.zy, L.lse,
+                       score);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 

@@ -1176,6 +1176,77 @@ def rnnt_joint_loss(enc_proj: torch.Tensor, pred_proj: torch.Tensor, weight: tor
     return _RnntJointLoss.apply(enc_proj, pred_proj, weight, bias, hlens, ys, ylens, blank)
 
 
+# Rows (utterance, frame, arc) one group of rnnt_score_hypotheses may hold.  The workspace takes 2 J + 8 ceil(V / 128) + 16
+# bytes per row: 1 616 at J = 640, V = 5000, so 2^19 rows are 0.85 GB.
+RNNT_SCORE_MAX_ROWS = 1 << 19
+
+
+def rnnt_score_unmet(enc_proj: torch.Tensor, pred_nodes: torch.Tensor, weight: torch.Tensor) -> Optional[str]:
+    """The condition rnnt_score_hypotheses does not meet for these operands, or None: the dims of rnnt_joint_loss_unmet."""
+    if not (enc_proj.is_cuda and pred_nodes.is_cuda and weight.is_cuda):
+        return "the operands are not on the GPU"
+    if enc_proj.dim() != 3 or pred_nodes.dim() < 2:
+        return "enc_proj (B, T, J) and pred_nodes (..., J) are expected"
+    V, J = weight.shape
+    if enc_proj.shape[2] != J or pred_nodes.shape[-1] != J:
+        return "the joint dimension of enc_proj / pred_nodes differs from the output layer's"
+    if J % 64:
+        return f"join_dim {J} is not a multiple of 64"
+    if V % 8:
+        return f"vocab_size {V} is not a multiple of 8"
+    return None
+
+
+def rnnt_score_hypotheses(enc_proj: torch.Tensor, pred_nodes: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                          hlens: Optional[torch.Tensor], tables, blank: int = 0, max_rows: int = RNNT_SCORE_MAX_ROWS) -> torch.Tensor:
+    """log p(y | x) of every hypothesis of a batch of n-best lists, (N,) fp32 on the device, scored over the prefix trie of each
+    list (csrc/rnnt_loss.hip: pafc_rnnt_score, include/pafc_search.h).  enc_proj (B, T, J) = enc_ffn(encoder_out), once per
+    utterance; pred_nodes (N, tables.pred_stride, J) = pred_ffn(predictor(blank-prepended padded hypotheses)); weight (V, J) /
+    bias (V) of ffn_out; hlens (B) frames on the device (a hypothesis of an utterance whose length there is not the tables' gets
+    NaN), or None when the tables were built from lengths the caller holds on the host; tables: transducer.search.rescoring.build_arc_tables of the same lengths.  Casts as
+    _RnntJointLoss.forward does (bf16 operands, the cached bf16 copies of the weights), and a hypothesis gets the bits of
+    -rnnt_joint_loss of that hypothesis alone.  One upload (the packed tables), no read of the host.  The batch runs in groups
+    of whole utterances of at most max_rows rows each, which bounds the workspace (RNNT_SCORE_MAX_ROWS: 0.85 GB at J = 640,
+    V = 5000); an utterance that alone has more rows raises PafcError."""
+    unmet = rnnt_score_unmet(enc_proj, pred_nodes, weight)
+    if unmet is not None:
+        raise _lib.PafcError(f"rnnt_score_hypotheses: {unmet}")
+    B, T, J = enc_proj.shape
+    V = weight.shape[0]
+    dev = enc_proj.device
+    if hlens is not None and hlens.numel() != B:
+        raise _lib.PafcError(f"rnnt_score_hypotheses: {hlens.numel()} lengths for {B} utterances")
+    score = torch.empty(tables.nhyp, dtype=torch.float32, device=dev)
+    if tables.nhyp == 0:
+        return score
+    groups, start, acc = [], 0, 0                      # consecutive whole utterances, at most max_rows rows each
+    for b, r in enumerate(tables.utt_rows):
+        if r > max_rows:
+            raise _lib.PafcError(f"rnnt_score_hypotheses: utterance {b} alone has {r} rows (frames x arcs), more than max_rows = "
+                                 f"{max_rows}")
+        if acc + r > max_rows:
+            groups.append((start, b, acc))
+            start, acc = b, 0
+        acc += r
+    groups.append((start, tables.nutt, acc))
+    groups = [g for g in groups if g[2] > 0]
+    Eb = enc_proj.detach().to(torch.bfloat16).contiguous()
+    Pb = pred_nodes.detach().to(torch.bfloat16).reshape(-1, J).contiguous()
+    wb = _bf16_shadow(weight).detach().contiguous()
+    bb = None if bias is None else _bf16_shadow(bias).detach().contiguous()
+    hl = None if hlens is None else hlens.to(device=dev, dtype=torch.int32).contiguous()
+    tab = tables.packed.to(dev, non_blocking=True)     # the one upload
+    L = _lib.lib()
+    nbytes = max(L.pafc_rnnt_score_workspace_bytes(u1 - u0, J, V, rows) for u0, u1, rows in groups)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for u0, u1, _ in groups:
+        _lib.check(L.pafc_rnnt_score(B, T, J, V, _lib.ptr(Eb), J, T * J, _lib.ptr(Pb), J, Pb.shape[0], _lib.ptr(wb), _lib.ptr(bb),
+                                     _lib.ptr(hl), tables.nutt, tables.nhyp, tables.narc, tables.ncol, _lib.ptr(tables.packed),
+                                     _lib.ptr(tab), u0, u1, int(blank), _lib.ptr(score), _lib.ptr(ws), nbytes, _lib.stream_of(Eb)),
+                   "pafc_rnnt_score")
+    return score
+
+
 RNNT_GREEDY_CHUNK = 32     # lockstep steps between two reads of the running-row count, after the first T steps
 
 

@@ -2,7 +2,9 @@
 RNN predictor + joint, `decode(methods=[...,'rnnt_beam_search', 'rnnt_greedy_search'])` (:695-813), `beam_search_decode`
 (:644-693), `greedy_search` (:427-472), the runtime step API (:474-505) and `stream_greedy_search` /
 `stream_beam_search`: the streaming encoder and the greedy / CTC-fused prefix beam search chunk by chunk with carried
-decoder state.
+decoder state.  Two-pass decoding (transducer_attention_rescoring, :288-425, without the attention term): `score_hypotheses`
+is the full-sum transducer score log p(y | x) of n-best lists (`_cal_transducer_score`, :185-210), and the decode modes
+"ctc_beam_td_rescoring" / "rnnt_beam_td_rescoring" re-rank a first pass with it (search/rescoring.py).
 
 Training objective (forward, :105-175): transducer_weight * RNN-T loss + ctc_weight * CTC loss over the accelerated
 encoder.  The reference's RNN-T loss is the third-party `optimized_transducer.transducer_loss` (transducer.py:506-523;
@@ -17,6 +19,7 @@ from ..transformer.search import DecodeResult
 from .loss import transducer_loss
 from .search.greedy_search import GreedyStreamer, batch_greedy_search
 from .search.prefix_beam_search import BeamStreamer, PrefixBeamSearch
+from .search.rescoring import RESCORING_MODES, build_arc_tables, check_hypotheses, check_score_backend, rescore
 
 IGNORE_ID = -1
 FUSED_JOINT = "fused_joint"
@@ -82,15 +85,7 @@ class Transducer(ASRModel):
         from .. import hip_ops
         from .._lib import PafcError
         j = self.joint
-        unmet = None
-        if not getattr(j, "prejoin_linear", False) or j.enc_ffn is None or j.pred_ffn is None:
-            unmet = "the joint has no pre-join projections (prejoin_linear: false)"
-        elif j.postjoin_linear:
-            unmet = "the joint has a post-join projection (postjoin_linear: true)"
-        elif not isinstance(j.activatoin, torch.nn.Tanh):
-            unmet = "the joint's activation is not tanh"
-        elif getattr(j, "hat_joint", False):
-            unmet = "hat_joint"
+        unmet = self._joint_unmet_for_kernels()
         E = P = None
         if unmet is None:
             E = j.enc_ffn(encoder_out.to(predictor_out.dtype))
@@ -101,6 +96,95 @@ class Transducer(ASRModel):
         nll = hip_ops.rnnt_joint_loss(E, P, j.ffn_out.weight, j.ffn_out.bias, encoder_out_lens, rnnt_text, text_lengths,
                                       self.blank)
         return nll.sum() / encoder_out_lens.sum()
+
+    def _joint_unmet_for_kernels(self) -> Optional[str]:
+        """The condition of the joint the fused kernels do not take (pre-join projections, no post-join, tanh, no hat_joint)."""
+        j = self.joint
+        if not getattr(j, "prejoin_linear", False) or j.enc_ffn is None or j.pred_ffn is None:
+            return "the joint has no pre-join projections (prejoin_linear: false)"
+        if j.postjoin_linear:
+            return "the joint has a post-join projection (postjoin_linear: true)"
+        if not isinstance(j.activatoin, torch.nn.Tanh):
+            return "the joint's activation is not tanh"
+        if getattr(j, "hat_joint", False):
+            return "hat_joint"
+        return None
+
+    @torch.no_grad()
+    def score_hypotheses(self, encoder_out: torch.Tensor, encoder_lens, hyps: List[List[List[int]]],
+                         backend: Optional[str] = None) -> List[List[float]]:
+        """The full-sum transducer score log p(y | x) of every hypothesis: hyps[b] is a list of token lists for utterance b of
+        encoder_out (B, T, D); the result has the same shape.  encoder_lens: (B) tensor or list; lengths on the host spare
+        the kernels backend one read of the device.
+        backend "framework": `_cal_transducer_score` restated (transducer.py:185-210): the encoder rows repeated per hypothesis,
+          predictor(add_blank(...)), joint, transducer_loss(reduction="none") times -1; on the CPU and the GPU.
+        backend "kernels": the prefix trie of every n-best list through hip_ops.rnnt_score_hypotheses -- enc_ffn once per
+          utterance, the predictor teacher-forced once over the padded hypotheses (the reference's own call), one joint row per
+          (frame, trie arc) instead of one per (hypothesis, frame, label count), no logits stored.  It scores with the bf16 joint,
+          the training kernel's contract, also for an fp32 model.  It needs the joint _fused_joint_loss takes (pre-join
+          projections, no post-join projection, tanh, no hat_joint); an unmet condition raises PafcError, never a fallback.
+        None: kernels on the GPU, framework on the CPU.
+        ValueError for a blank inside a hypothesis, a token outside the vocabulary or more than 2558 tokens."""
+        backend = check_score_backend(backend, encoder_out.is_cuda)
+        lens = [int(v) for v in (encoder_lens.tolist() if isinstance(encoder_lens, torch.Tensor) else encoder_lens)]
+        if len(hyps) != encoder_out.size(0) or len(lens) != encoder_out.size(0):
+            raise ValueError(f"{encoder_out.size(0)} utterances, {len(hyps)} n-best lists, {len(lens)} lengths")
+        flat = [h for nbest in hyps for h in nbest]
+        if backend == "framework":
+            check_hypotheses(hyps, self.vocab_size, self.blank)
+            td = self._score_framework(encoder_out, lens, hyps) if flat else []
+        else:
+            td = self._score_kernels(encoder_out, encoder_lens, lens, hyps) if flat else []
+        out, at = [], 0
+        for nbest in hyps:
+            out.append(td[at:at + len(nbest)])
+            at += len(nbest)
+        return out
+
+    def _hyps_pad(self, flat: List[List[int]], device) -> torch.Tensor:
+        umax = max(len(h) for h in flat)
+        pad = torch.full((len(flat), umax), IGNORE_ID, dtype=torch.int64)
+        for n, h in enumerate(flat):
+            pad[n, :len(h)] = torch.tensor(h, dtype=torch.int64)
+        return pad.to(device, non_blocking=True)
+
+    def _score_framework(self, encoder_out, lens: List[int], hyps) -> List[float]:
+        td: List[float] = []
+        for b, nbest in enumerate(hyps):              # one utterance at a time: its hypotheses are the reference's batch
+            if not nbest:
+                continue
+            hyps_pad = self._hyps_pad(nbest, encoder_out.device)
+            predictor_out = self.predictor(add_blank(hyps_pad, self.blank, IGNORE_ID))
+            enc = encoder_out[b:b + 1, :lens[b]].to(predictor_out.dtype).repeat(len(nbest), 1, 1)
+            joint_out = self.joint(enc, predictor_out)                                   # (m, T_b, U + 1, V)
+            us = [len(h) for h in nbest]
+            logits = torch.cat([joint_out[i, :, :u + 1].reshape(-1, joint_out.size(-1)) for i, u in enumerate(us)])
+            rnnt_text = torch.where(hyps_pad == IGNORE_ID, 0, hyps_pad).to(torch.int32)
+            nll = transducer_loss(logits, rnnt_text, torch.tensor([lens[b]] * len(nbest)), torch.tensor(us), self.blank,
+                                  reduction="none")
+            td += (nll * -1).tolist()
+        return td
+
+    def _score_kernels(self, encoder_out, encoder_lens, lens: List[int], hyps) -> List[float]:
+        from .. import hip_ops
+        from .._lib import PafcError
+        j = self.joint
+        unmet = self._joint_unmet_for_kernels()
+        if unmet is None and not encoder_out.is_cuda:
+            unmet = "the operands are not on the GPU"
+        if unmet is not None:
+            raise PafcError(f"score_hypotheses(backend='kernels'): {unmet}")
+        tables = build_arc_tables(hyps, lens, self.vocab_size, self.blank)
+        flat = [h for nbest in hyps for h in nbest]
+        predictor_out = self.predictor(add_blank(self._hyps_pad(flat, encoder_out.device), self.blank, IGNORE_ID))
+        E = j.enc_ffn(encoder_out.to(predictor_out.dtype))
+        P = j.pred_ffn(predictor_out)                                                    # (N, Umax + 1, J): tables.pred_stride
+        unmet = hip_ops.rnnt_score_unmet(E, P, j.ffn_out.weight)
+        if unmet is not None:
+            raise PafcError(f"score_hypotheses(backend='kernels'): {unmet}")
+        hl = encoder_lens if isinstance(encoder_lens, torch.Tensor) and encoder_lens.is_cuda else None
+        score = hip_ops.rnnt_score_hypotheses(E, P, j.ffn_out.weight, j.ffn_out.bias, hl, tables, self.blank)
+        return score.tolist()                                                            # the one read of the device
 
     def init_bs(self):
         if self.bs is None:
@@ -199,14 +283,31 @@ class Transducer(ASRModel):
                decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0,
                transducer_weight: float = 0.0, simulate_streaming: bool = False, reverse_weight: float = 0.0,
                context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0, cat_embs=None,
-               frame_body: Optional[str] = None, **_ignored) -> Dict[str, List[DecodeResult]]:
-        """frame_body: for rnnt_beam_search, the per-frame body of beam_search_decode ("framework" / "kernels")."""
-        rest = [m for m in methods if m not in ("rnnt_beam_search", "rnnt_greedy_search")]
+               frame_body: Optional[str] = None, attn_weight: float = 0.0, search_ctc_weight: float = 0.3,
+               search_transducer_weight: float = 0.7, score_backend: Optional[str] = None, **_ignored
+               ) -> Dict[str, List[DecodeResult]]:
+        """frame_body: for rnnt_beam_search and rnnt_beam_td_rescoring, the per-frame body of beam_search_decode ("framework" /
+        "kernels").
+        Two-pass modes (the reference's rnnt_beam_attn_rescoring / ctc_beam_td_attn_rescoring minus `attn`: the attention
+        decoder was not released, so a non-zero reverse_weight or attn_weight with them is a ValueError):
+          "ctc_beam_td_rescoring": first pass ctc_prefix_beam_search (computed once when that mode is requested too);
+          "rnnt_beam_td_rescoring": first pass beam_search_decode with search_ctc_weight / search_transducer_weight -- the
+            reference's names, but beam_search_decode's defaults 0.3 / 0.7: the reference's 1.0 / 0.0 switch the transducer off.
+        Second pass: final_i = ctc_weight * first_pass_score_i + transducer_weight * td_i, td_i = score_hypotheses (backend:
+        score_backend), ties to the earlier first-pass rank; nbest / nbest_scores / nbest_times re-ordered by final,
+        nbest_td_scores the raw td_i (search/rescoring.py: rescore)."""
+        two_pass = [m for m in methods if m in RESCORING_MODES]
+        if two_pass and (reverse_weight != 0.0 or attn_weight != 0.0):
+            raise ValueError(f"decode mode {two_pass[0]!r} with reverse_weight = {reverse_weight} / attn_weight = {attn_weight}: "
+                             "the attention decoder was not released, there is no attention term to weigh")
+        rest = [m for m in methods if m not in ("rnnt_beam_search", "rnnt_greedy_search") + RESCORING_MODES]
         encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
                                                           num_decoding_left_chunks, simulate_streaming, cat_embs)
         encoder_lens = encoder_mask.squeeze(1).sum(1)
         ctc_probs = self.ctc_logprobs(encoder_out, blank_penalty, blank_id)
         results = {}
+        if "ctc_beam_td_rescoring" in two_pass and "ctc_prefix_beam_search" not in rest:
+            rest = rest + ["ctc_prefix_beam_search"]          # the first pass, not reported under its own name
         for m in rest:
             if m == "ctc_greedy_search":
                 from ..transformer.search import ctc_greedy_search
@@ -222,4 +323,19 @@ class Transducer(ASRModel):
                 ctc_weight=ctc_weight, transducer_weight=transducer_weight, cat_embs=cat_embs, frame_body=frame_body)
         if "rnnt_greedy_search" in methods:
             results["rnnt_greedy_search"] = batch_greedy_search(self, encoder_out, encoder_lens)
+        if two_pass:
+            lens_host = encoder_lens.tolist()
+            for m in two_pass:
+                if m == "ctc_beam_td_rescoring":
+                    first = results["ctc_prefix_beam_search"]
+                else:
+                    first = self.beam_search_decode(
+                        encoder_outs=encoder_out, encoder_lens=encoder_lens, ctc_probs=ctc_probs, beam_size=beam_size,
+                        ctc_weight=search_ctc_weight, transducer_weight=search_transducer_weight, cat_embs=cat_embs,
+                        frame_body=frame_body)
+                hyps = [r.nbest if r.nbest is not None else [r.tokens] for r in first]
+                td = self.score_hypotheses(encoder_out, lens_host, hyps, backend=score_backend)
+                results[m] = rescore(first, td, ctc_weight, transducer_weight)
+            if "ctc_prefix_beam_search" not in methods:
+                results.pop("ctc_prefix_beam_search", None)
         return results

@@ -12,7 +12,8 @@ from ..utils.mask import make_pad_mask
 class DecodeResult:
     def __init__(self, tokens: List[int], score: float = 0.0, confidence: float = 0.0, tokens_confidence=None,
                  times=None, nbest: Optional[List[List[int]]] = None, nbest_scores: Optional[List[float]] = None,
-                 nbest_times=None, end_times=None, tokens_info=None, ok: bool = True):
+                 nbest_times=None, end_times=None, tokens_info=None, ok: bool = True,
+                 nbest_td_scores: Optional[List[float]] = None):
         self.tokens = tokens
         self.score = score
         self.confidence = confidence
@@ -24,6 +25,7 @@ class DecodeResult:
         self.end_times = end_times          # forced alignment: the last frame of every token (times: the first)
         self.tokens_info = tokens_info      # forced alignment: (start, end) seconds per token
         self.ok = ok                        # forced alignment: False when the labels cannot be aligned to the frames
+        self.nbest_td_scores = nbest_td_scores    # transducer rescoring: log p(y | x) of every entry of nbest, in its order
 
 
 def log_add(args: List[float]) -> float:
