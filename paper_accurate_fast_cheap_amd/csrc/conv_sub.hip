@@ -29,8 +29,6 @@ namespace pafc {
 namespace {
 
 constexpr int BK = 64;
-typedef float f32x4c __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
 
 struct ConvParams {
     const bf16_t *in;    // (B, T1, F1, Ci)
@@ -42,11 +40,6 @@ struct ConvParams {
     int relu;
     int mtiles, ntiles;
 };
-
-__device__ __forceinline__ void dma16(const bf16_t *src, bf16_t *lds_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_base, 16, 0, 0);
-}
 
 template <int WM, int WN, int STAGES, int BLOCKS_PER_CU>
 __global__ __launch_bounds__(256, BLOCKS_PER_CU) void conv3x3s2_kernel(const ConvParams p) {
@@ -99,16 +92,16 @@ __global__ __launch_bounds__(256, BLOCKS_PER_CU) void conv3x3s2_kernel(const Con
         bf16_t *A = lds + buf * STAGE;
         bf16_t *Bt = A + BM * BK;
 #pragma unroll
-        for (int j = 0; j < AJ; ++j) dma16(a_src[j] + aoff, A + (wave * (BM / 4) + j * 8) * BK);
+        for (int j = 0; j < AJ; ++j) global_to_lds16(a_src[j] + aoff, A + (wave * (BM / 4) + j * 8) * BK);
 #pragma unroll
-        for (int j = 0; j < BJ; ++j) dma16(b_src[j] + boff, Bt + (wave * (BN / 4) + j * 8) * BK);
+        for (int j = 0; j < BJ; ++j) global_to_lds16(b_src[j] + boff, Bt + (wave * (BN / 4) + j * 8) * BK);
     };
 
-    f32x4c acc[WM][WN];
+    f32x4 acc[WM][WN];
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
-        for (int j = 0; j < WN; ++j) acc[i][j] = f32x4c{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int fr = lane & 15, kq = lane >> 4;
 #pragma unroll
@@ -127,13 +120,13 @@ __global__ __launch_bounds__(256, BLOCKS_PER_CU) void conv3x3s2_kernel(const Con
         // nobody else hides the ds_read latency, and left alone the compiler waits for every fragment it just asked for
         auto ldA = [&](int ks, int i) {
             const int row = wm * (16 * WM) + i * 16 + fr;
-            return *reinterpret_cast<const bf16x8c *>(A + row * BK + (((ks * 4 + kq) ^ (row & 7)) * 8));
+            return *reinterpret_cast<const bf16x8 *>(A + row * BK + (((ks * 4 + kq) ^ (row & 7)) * 8));
         };
         auto ldB = [&](int ks, int j) {
             const int row = wn * (16 * WN) + j * 16 + fr;
-            return *reinterpret_cast<const bf16x8c *>(Bt + row * BK + (((ks * 4 + kq) ^ (row & 7)) * 8));
+            return *reinterpret_cast<const bf16x8 *>(Bt + row * BK + (((ks * 4 + kq) ^ (row & 7)) * 8));
         };
-        bf16x8c bq[2][WN], aq[2];
+        bf16x8 bq[2][WN], aq[2];
 #pragma unroll
         for (int j = 0; j < WN; ++j) bq[0][j] = ldB(0, j);
         aq[0] = ldA(0, 0);
@@ -441,17 +434,17 @@ __global__ __launch_bounds__(256, 1) void conv3x3s2_split_kernel(const ConvSplit
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int rowbase = (wave * 32 + j * 8) * BK;
-            dma16(p.in_hi + a_off[j] + aoff, S + rowbase);
-            dma16(p.in_lo + a_off[j] + aoff, S + TILE + rowbase);
-            dma16(p.wt_hi + b_off[j] + boff, S + 2 * TILE + rowbase);
-            dma16(p.wt_lo + b_off[j] + boff, S + 3 * TILE + rowbase);
+            global_to_lds16(p.in_hi + a_off[j] + aoff, S + rowbase);
+            global_to_lds16(p.in_lo + a_off[j] + aoff, S + TILE + rowbase);
+            global_to_lds16(p.wt_hi + b_off[j] + boff, S + 2 * TILE + rowbase);
+            global_to_lds16(p.wt_lo + b_off[j] + boff, S + 3 * TILE + rowbase);
         }
     };
-    f32x4c acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4c{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, kq = lane >> 4;
     issue(0, 0);
     for (int it = 0; it < iters; ++it) {
@@ -461,20 +454,20 @@ __global__ __launch_bounds__(256, 1) void conv3x3s2_split_kernel(const ConvSplit
         const bf16_t *S = lds + (it & 1) * STAGE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            bf16x8c ah[4], al[4], bh[4], bl[4];
+            bf16x8 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int row = wm * 64 + i * 16 + fr;
                 const int o = row * BK + (((ks * 4 + kq) ^ (row & 7)) * 8);
-                ah[i] = *reinterpret_cast<const bf16x8c *>(S + o);
-                al[i] = *reinterpret_cast<const bf16x8c *>(S + TILE + o);
+                ah[i] = *reinterpret_cast<const bf16x8 *>(S + o);
+                al[i] = *reinterpret_cast<const bf16x8 *>(S + TILE + o);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int row = wn * 64 + j * 16 + fr;
                 const int o = row * BK + (((ks * 4 + kq) ^ (row & 7)) * 8);
-                bh[j] = *reinterpret_cast<const bf16x8c *>(S + 2 * TILE + o);
-                bl[j] = *reinterpret_cast<const bf16x8c *>(S + 3 * TILE + o);
+                bh[j] = *reinterpret_cast<const bf16x8 *>(S + 2 * TILE + o);
+                bl[j] = *reinterpret_cast<const bf16x8 *>(S + 3 * TILE + o);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)

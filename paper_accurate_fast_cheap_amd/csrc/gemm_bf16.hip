@@ -27,8 +27,6 @@ namespace pafc {
 namespace {
 
 constexpr int GBM = 128, GBN = 128, GBK = 64;
-typedef float f32x4g __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8g __attribute__((ext_vector_type(8)));
 
 struct GemmParams {
     const bf16_t *A, *W, *bias, *res;
@@ -50,20 +48,6 @@ struct GemmParams {
     // SAME operands and leaves a raw fp32 partial (EPI 3 with alpha 1, no bias, no residual) at out + z * sO
     int ksplit;
 };
-
-__device__ __forceinline__ void gdma16(const bf16_t *src, bf16_t *lds_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == 1) return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));
-    if (act == 2) {   // tanh(v) = 1 - 2 / (exp(2v) + 1); saturates correctly at +-inf
-        return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * v) + 1.f);
-    }
-    if (act == 3) return fmaxf(v, 0.f);
-    return v;
-}
 
 // EPI: 0 = plain (bf16 staging), 1 = residual (fp32 staging), 2 = GLU (the tile's columns [0, 64) are values, [64, 128)
 // the gates of the same 64 output channels; the output has N / 2 columns)
@@ -136,16 +120,16 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmParams p) {
                 koffA = (seg == 1 ? p.K1 : 0) + k0;
         }
 #pragma unroll
-        for (int j = 0; j < MI; ++j) gdma16(a_src[j] + koffA, A + (wave * (BM / 4) + j * 8) * GBK);
+        for (int j = 0; j < MI; ++j) global_to_lds16(a_src[j] + koffA, A + (wave * (BM / 4) + j * 8) * GBK);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) gdma16(w_src[j] + koff, Wt + (wave * (BN / 4) + j * 8) * GBK);
+        for (int j = 0; j < NI; ++j) global_to_lds16(w_src[j] + koff, Wt + (wave * (BN / 4) + j * 8) * GBK);
     };
 
-    f32x4g acc[MI][NI];
+    f32x4 acc[MI][NI];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = f32x4g{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int fr = lane & 15, kq = lane >> 4;
     issue(0, 0);
@@ -184,16 +168,16 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmParams p) {
         const bf16_t *Wt = A + BM * GBK;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            bf16x8g af[MI], wf[NI];
+            bf16x8 af[MI], wf[NI];
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int row = wm * (BM / 2) + i * 16 + fr;
-                af[i] = *reinterpret_cast<const bf16x8g *>(A + row * GBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
+                af[i] = *reinterpret_cast<const bf16x8 *>(A + row * GBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
             }
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const int row = wn * (BN / 2) + j * 16 + fr;
-                wf[j] = *reinterpret_cast<const bf16x8g *>(Wt + row * GBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
+                wf[j] = *reinterpret_cast<const bf16x8 *>(Wt + row * GBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
             }
 #pragma unroll
             for (int i = 0; i < MI; ++i)
@@ -219,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmParams p) {
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    O[(wm * (BM / 2) + i * 16 + 4 * kq + g) * LDF + col] = apply_act(fmaf(acc[i][j][g], p.alpha, bv), p.act);
+                    O[(wm * (BM / 2) + i * 16 + 4 * kq + g) * LDF + col] = epilogue_act(fmaf(acc[i][j][g], p.alpha, bv), p.act);
         }
         __syncthreads();
         if constexpr (EPI == 3) {
@@ -274,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmParams p) {
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    O[(wm * (BM / 2) + i * 16 + 4 * kq + g) * LDF + col] = apply_act(fmaf(acc[i][j][g], p.alpha, bv), p.act);
+                    O[(wm * (BM / 2) + i * 16 + 4 * kq + g) * LDF + col] = epilogue_act(fmaf(acc[i][j][g], p.alpha, bv), p.act);
         }
         __syncthreads();
         const bf16_t *Rz = p.res + z * p.sR;
@@ -355,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmParams p) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
                     O[(wm * (BM / 2) + i * 16 + 4 * kq + g) * LDO + col] =
-                        (bf16_t)f32_to_bf16_bits(apply_act(fmaf(acc[i][j][g], p.alpha, bv), p.act));
+                        (bf16_t)f32_to_bf16_bits(epilogue_act(fmaf(acc[i][j][g], p.alpha, bv), p.act));
         }
         __syncthreads();
         constexpr int CPR = BN / 8, RPP = 256 / CPR;
@@ -517,7 +501,7 @@ __global__ __launch_bounds__(256) void gemm_ksplit_reduce_kernel(long M, int N, 
     }
     float o[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = apply_act(fmaf(o[e], alpha, bias ? bias[c + e] : 0.f), act);
+    for (int e = 0; e < 4; ++e) o[e] = epilogue_act(fmaf(o[e], alpha, bias ? bias[c + e] : 0.f), act);
     if (res) {
         const float4 r = *reinterpret_cast<const float4 *>(res + m * ldr + c);
         o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w;

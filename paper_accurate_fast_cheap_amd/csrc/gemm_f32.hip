@@ -30,7 +30,6 @@ namespace pafc {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));   // (HIP's float4 is a struct: selects and array elements of it go through memory)
 
 // K-step KS (32 for the 128 x 128 tiles, 64 for the 64 x 64 ones: a block of few-rows problems has the CU to itself, and every
 // K-step exposes a global-load round trip of ~1 us behind only 16 MFMAs per wave -- half as many, twice as long steps);
@@ -45,7 +44,7 @@ struct GemmF32Params {
     float alpha;
 };
 
-__device__ __forceinline__ float act_apply(float v, int act) {
+__device__ __forceinline__ float act_apply(float v, int act) {   // exact tanhf and true division on purpose, not epilogue_act
     switch (act) {
         case 1: return v / (1.f + __expf(-v));                     // SiLU
         case 2: return tanhf(v);

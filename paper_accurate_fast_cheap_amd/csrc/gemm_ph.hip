@@ -61,10 +61,6 @@
 namespace pafc {
 namespace {
 
-typedef float f32x4p __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8p __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4p __attribute__((ext_vector_type(4)));
-
 struct PhParams {
     const bf16_t *A, *W;
     const void *bias;                 // bf16 (OUT 0) or fp32 (OUT 1, 2)
@@ -121,20 +117,6 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lane
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, long bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)(bytes > 0x7fffffffL ? 0x7fffffffL : bytes), 0x00020000);
-}
-
-typedef float f32x2p __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2p __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {     // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2p{lo, hi}, bf16x2p));
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_apply(float v) {
-    if constexpr (ACT == 1) return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));
-    if constexpr (ACT == 2) return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * v) + 1.f);   // saturates correctly at +-inf
-    if constexpr (ACT == 3) return fmaxf(v, 0.f);
-    return v;
 }
 
 // cache policy of the output stores (buffer_store aux bits: 1 = sc0, 2 = nt, 16 = sc1).  Measured with nt = non-temporal (round 4,
@@ -329,7 +311,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     const unsigned la = wr * (64 * 128) + frag;                              // + i * 2048 inside a unit
     const unsigned lb = wc * (32 * 128) + frag;                              // + j * 2048
 
-    bf16x8p af[4][2], bf0[TN][2], bf1[TN][2];
+    bf16x8 af[4][2], bf0[TN][2], bf1[TN][2];
     auto read_a = [&](int h, int buf) {
 #ifdef PH_ABL_NOREAD
         return;
@@ -337,19 +319,19 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
         const unsigned char *base = lds + buf * STEP + (h ? OFF_A1 : OFF_A0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            af[i][0] = *reinterpret_cast<const bf16x8p *>(base + la + i * 2048);
-            af[i][1] = *reinterpret_cast<const bf16x8p *>(base + (la ^ 64) + i * 2048);
+            af[i][0] = *reinterpret_cast<const bf16x8 *>(base + la + i * 2048);
+            af[i][1] = *reinterpret_cast<const bf16x8 *>(base + (la ^ 64) + i * 2048);
         }
     };
-    auto read_b = [&](int h, int buf, bf16x8p (&dst)[TN][2]) {
+    auto read_b = [&](int h, int buf, bf16x8 (&dst)[TN][2]) {
 #ifdef PH_ABL_NOREAD
         return;
 #endif
         const unsigned char *base = lds + buf * STEP + (h ? OFF_B1 : OFF_B0);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            dst[j][0] = *reinterpret_cast<const bf16x8p *>(base + lb + j * 2048);
-            dst[j][1] = *reinterpret_cast<const bf16x8p *>(base + (lb ^ 64) + j * 2048);
+            dst[j][0] = *reinterpret_cast<const bf16x8 *>(base + lb + j * 2048);
+            dst[j][1] = *reinterpret_cast<const bf16x8 *>(base + (lb ^ 64) + j * 2048);
         }
     };
 
@@ -409,7 +391,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
         }
     }
 
-    f32x4p acc[2][2][4][TN];
+    f32x4 acc[2][2][4][TN];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -417,9 +399,9 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[a][b][i][j] = f32x4p{0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < TN; ++j) acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    auto mma = [&](int mi, int nj, const bf16x8p (&bqf)[TN][2]) {
+    auto mma = [&](int mi, int nj, const bf16x8 (&bqf)[TN][2]) {
         __builtin_amdgcn_s_setprio(1);
 #ifdef PH_ABL_NOMFMA
         if (false) {
@@ -542,12 +524,6 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     int etid = tid;
     asm volatile("" : "+v"(etid));               // epilogue addresses are formed here, per tile, not hoisted out of the tile loop
     const int efr = etid & 15, ekq = (etid >> 4) & 3;
-    auto unpack8 = [&](const u32x4p &q, float (&f)[8]) {
-        f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = __uint_as_float(q.x & 0xffff0000u);
-        f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = __uint_as_float(q.y & 0xffff0000u);
-        f[4] = bf16_bits_to_f32(q.z & 0xffffu); f[5] = __uint_as_float(q.z & 0xffff0000u);
-        f[6] = bf16_bits_to_f32(q.w & 0xffffu); f[7] = __uint_as_float(q.w & 0xffff0000u);
-    };
     const int ncol = GLU ? p.N / 2 : p.N;
     const int nrt = (cur.vr + 15) >> 4;           // 16-row groups with a valid row
     // descriptors start at the tile's first row: offsets stay small whatever the size of the tensors
@@ -565,11 +541,11 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = 0.f;
         } else if constexpr (BIASF32) {
-            const u32x4p q0 = *reinterpret_cast<const u32x4p *>(slot), q1 = *reinterpret_cast<const u32x4p *>(slot + 16);
+            const u32x4 q0 = *reinterpret_cast<const u32x4 *>(slot), q1 = *reinterpret_cast<const u32x4 *>(slot + 16);
             f[0] = __uint_as_float(q0.x); f[1] = __uint_as_float(q0.y); f[2] = __uint_as_float(q0.z); f[3] = __uint_as_float(q0.w);
             f[4] = __uint_as_float(q1.x); f[5] = __uint_as_float(q1.y); f[6] = __uint_as_float(q1.z); f[7] = __uint_as_float(q1.w);
         } else {
-            unpack8(*reinterpret_cast<const u32x4p *>(slot), f);
+            Elem<bf16_t>::unpack(*reinterpret_cast<const u32x4 *>(slot), f);
         }
     };
     // store the lane's 8 consecutive values o[] of (row, col): bf16 one 16-byte store, fp32 two, hi | lo planes two
@@ -577,26 +553,27 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
         const bool ok = row < cur.vr && col < ncol;
         const unsigned off = ok ? (unsigned)(((long)row * p.ldo + col) * OSZ) : PH_OOB;
         if constexpr (OUT == 0) {
-            u32x4p w{0u, 0u, 0u, 0u};
-            if (live) w = u32x4p{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])};
+            u32x4 w{0u, 0u, 0u, 0u};
+            if (live) w = u32x4{pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]), pack_bf16_rne(o[6], o[7])};
             __builtin_amdgcn_raw_buffer_store_b128(w, Or, off, 0, PH_ST_AUX);
         } else if constexpr (OUT == 1) {
-            u32x4p w0{0u, 0u, 0u, 0u}, w1{0u, 0u, 0u, 0u};
+            u32x4 w0{0u, 0u, 0u, 0u}, w1{0u, 0u, 0u, 0u};
             if (live) {
-                w0 = u32x4p{__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
-                w1 = u32x4p{__float_as_uint(o[4]), __float_as_uint(o[5]), __float_as_uint(o[6]), __float_as_uint(o[7])};
+                w0 = u32x4{__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
+                w1 = u32x4{__float_as_uint(o[4]), __float_as_uint(o[5]), __float_as_uint(o[6]), __float_as_uint(o[7])};
             }
             __builtin_amdgcn_raw_buffer_store_b128(w0, Or, off, 0, PH_ST_AUX);
             __builtin_amdgcn_raw_buffer_store_b128(w1, Or, ok ? off + 16 : PH_OOB, 0, PH_ST_AUX);
         } else {
-            u32x4p wh{0u, 0u, 0u, 0u}, wl{0u, 0u, 0u, 0u};
+            u32x4 wh{0u, 0u, 0u, 0u}, wl{0u, 0u, 0u, 0u};
             if (live) {
                 float lo[8], hf[8];
-                wh = u32x4p{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])};
-                unpack8(wh, hf);
+                wh = u32x4{pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]), pack_bf16_rne(o[6], o[7])};
+                Elem<bf16_t>::unpack(wh, hf);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) lo[e] = o[e] - hf[e];
-                wl = u32x4p{pack_bf16(lo[0], lo[1]), pack_bf16(lo[2], lo[3]), pack_bf16(lo[4], lo[5]), pack_bf16(lo[6], lo[7])};
+                wl = u32x4{pack_bf16_rne(lo[0], lo[1]), pack_bf16_rne(lo[2], lo[3]), pack_bf16_rne(lo[4], lo[5]),
+                           pack_bf16_rne(lo[6], lo[7])};
             }
             __builtin_amdgcn_raw_buffer_store_b128(wh, Or, off, 0, PH_ST_AUX);
             __builtin_amdgcn_raw_buffer_store_b128(wl, Or, ok ? off + (unsigned)(p.lo_off * 2) : PH_OOB, 0, PH_ST_AUX);
@@ -609,12 +586,12 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     // consumer: a row's eight pairs from the LDS copy (no cross-lane traffic) -> rstd, -mean * rstd.  Software-pipelined over
     // the row groups: a group's pairs are read while the previous group's values are computed (a group is one scheduling
     // region: read and used inside it, every group would expose an LDS round trip and the rsqrt chain)
-    auto row_read = [&](int g, u32x4p (&v)[4]) {
+    auto row_read = [&](int g, u32x4 (&v)[4]) {
         const unsigned char *rp = lds + 2 * STEP + 16 * 1024 + (wr * 128 + g * 16 + efr) * 64;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const u32x4p *>(rp + q * 16);
+        for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const u32x4 *>(rp + q * 16);
     };
-    auto row_norm = [&](const u32x4p (&v)[4], float &rstd, float &nm) {
+    auto row_norm = [&](const u32x4 (&v)[4], float &rstd, float &nm) {
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -628,7 +605,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     };
     auto csum8 = [&](int nj, float (&f)[8]) {     // the lane's 8 columns of column half nj, from the wave's csum slot
         const unsigned char *slot = lds + 2 * STEP + 8 * 1024 + wave * 1024 + (wc * 64 + nj * 32 + ekq * 8) * 4;
-        const u32x4p q0 = *reinterpret_cast<const u32x4p *>(slot), q1 = *reinterpret_cast<const u32x4p *>(slot + 16);
+        const u32x4 q0 = *reinterpret_cast<const u32x4 *>(slot), q1 = *reinterpret_cast<const u32x4 *>(slot + 16);
         f[0] = __uint_as_float(q0.x); f[1] = __uint_as_float(q0.y); f[2] = __uint_as_float(q0.z); f[3] = __uint_as_float(q0.w);
         f[4] = __uint_as_float(q1.x); f[5] = __uint_as_float(q1.y); f[6] = __uint_as_float(q1.z); f[7] = __uint_as_float(q1.w);
     };
@@ -640,14 +617,14 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
     if constexpr (LNF == 1) {
         csum8(0, lcs[0]); csum8(LNF == 1 ? 1 : 0, lcs[LNF == 1 ? 1 : 0]);
         bias8(0, lbv[0]); bias8(LNF == 1 ? 1 : 0, lbv[LNF == 1 ? 1 : 0]);
-        u32x4p v0[4];
+        u32x4 v0[4];
         row_read(0, v0);
         row_norm(v0, nx_rstd, nx_nm);
     }
     float gst1[LNF == 2 ? 8 : 1], gst2[LNF == 2 ? 8 : 1];      // LNF 2: this lane's share of each row group's (sum, sum of squares)
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
-        u32x4p rr[RES != 0 ? 4 : 1][2][RLD];
+        u32x4 rr[RES != 0 ? 4 : 1][2][RLD];
         if constexpr (RES != 0) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -668,7 +645,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
             const bool live = wr * 8 + g < nrt;   // wave-uniform: a row group beyond the tile's rows computes nothing
             const int row = wr * 128 + g * 16 + efr;
             const float ln_rstd = nx_rstd, ln_nm = nx_nm;
-            u32x4p vn[4];
+            u32x4 vn[4];
             if constexpr (LNF == 1) row_read(g < 7 ? g + 1 : 7, vn);      // the next group's pairs: in flight under this group's values
             if constexpr (GLU) {
                 float o[8];
@@ -714,10 +691,10 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
                         for (int j = 0; j < TN; ++j)
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
-                                o[j * 4 + e] = act_apply<ACT>(fmaf(acc[mi][nj][i][j][e], sc, bv[j * 4 + e]));
+                                o[j * 4 + e] = epilogue_act<ACT>(fmaf(acc[mi][nj][i][j][e], sc, bv[j * 4 + e]));
                         if constexpr (RES == 1) {
                             float rv[8];
-                            unpack8(rr[i][nj][0], rv);
+                            Elem<bf16_t>::unpack(rr[i][nj][0], rv);
 #pragma unroll
                             for (int e = 0; e < 8; ++e) o[e] += rv[e];
                         } else if constexpr (RES == 2) {
@@ -730,7 +707,8 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
                             // statistics of the row AS STORED (rounded to bf16, the very conversion store8 performs): the
                             // consumer multiplies the stored rows, and mean / rstd must be those of what it multiplies
                             float q[8];
-                            unpack8(u32x4p{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])}, q);
+                            Elem<bf16_t>::unpack(u32x4{pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]),
+                                                       pack_bf16_rne(o[6], o[7])}, q);
 #pragma unroll
                             for (int e = 0; e < 8; ++e) { st1 += q[e]; st2 = fmaf(q[e], q[e], st2); }
                         }
@@ -750,13 +728,12 @@ __global__ __launch_bounds__(512, 2) void gemm_ph_kernel(const PhParams p) {
         for (int g = 0; g < 8; ++g) { gst1[g] += __shfl_xor(gst1[g], 16, 64); gst2[g] += __shfl_xor(gst2[g], 16, 64); }
 #pragma unroll
         for (int g = 0; g < 8; ++g) { gst1[g] += __shfl_xor(gst1[g], 32, 64); gst2[g] += __shfl_xor(gst2[g], 32, 64); }
-        typedef unsigned u32x2p __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
             const int row = wr * 128 + g * 16 + efr;
             const bool ok = ekq == 0 && row < cur.vr;
             const unsigned off = ok ? (unsigned)(row * 64 + ((cur.n0 >> 8) * 4 + wc) * 8) : PH_OOB;
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2p{__float_as_uint(gst1[g]), __float_as_uint(gst2[g])}, Sr, off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(gst1[g]), __float_as_uint(gst2[g])}, Sr, off, 0, 0);
         }
     }
     __builtin_amdgcn_sched_barrier(0);

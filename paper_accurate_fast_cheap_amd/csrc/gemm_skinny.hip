@@ -34,9 +34,6 @@
 namespace pafc {
 namespace {
 
-typedef float f32x4s __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
-
 struct SkParams {
     const bf16_t *A, *W, *bias, *res;
     bf16_t *out;
@@ -62,21 +59,6 @@ struct SkParams {
     int K1;
 };
 
-__device__ __forceinline__ float sk_act(float v, int act) {
-    if (act == 1) return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));
-    if (act == 2) return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * v) + 1.f);
-    if (act == 3) return fmaxf(v, 0.f);
-    return v;
-}
-__device__ __forceinline__ void sk_unpack(const uint4 q, float (&f)[8]) {
-    f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = __uint_as_float(q.x & 0xffff0000u);
-    f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = __uint_as_float(q.y & 0xffff0000u);
-    f[4] = bf16_bits_to_f32(q.z & 0xffffu); f[5] = __uint_as_float(q.z & 0xffff0000u);
-    f[6] = bf16_bits_to_f32(q.w & 0xffffu); f[7] = __uint_as_float(q.w & 0xffff0000u);
-}
-__device__ __forceinline__ unsigned sk_pack(float lo, float hi) {   // both already bf16 values
-    return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
-}
 
 // MT: 16-row tiles per block (rows beyond M are clamped on load and skipped on store); GLU doubles the weight fragments and
 // accumulators; NWV waves split K; MIX: the A fragments are formed from x, its predecessor row and maa_x.
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const SkParams p)
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 float f[8];
-                sk_unpack(*reinterpret_cast<const uint4 *>(arow[i] + ks * 32), f);
+                Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(arow[i] + ks * 32), f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { q1[i] += f[e]; q2[i] = fmaf(f[e], f[e], q2[i]); }
             }
@@ -161,7 +143,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const SkParams p)
         long r = m0 + r16;
         if (r > p.M - 1) r = p.M - 1;
         const bf16_t *xrow = p.lora_x + r * p.ldx + 8 * qq;
-        f32x4s a1[4] = {f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}, f32x4s{0.f, 0.f, 0.f, 0.f}};
+        f32x4 a1[4] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         for (int kb = k0; kb < k1; kb += 4) {            // four K-steps' operands in flight together
             uint4 xf[4], wf1[4][4];
 #pragma unroll
@@ -177,8 +159,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const SkParams p)
                 if (kb + s_ < k1) {
 #pragma unroll
                     for (int tau = 0; tau < 4; ++tau)
-                        a1[tau] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, wf1[s_][tau]),
-                                                                          __builtin_bit_cast(bf16x8s, xf[s_]), a1[tau], 0, 0, 0);
+                        a1[tau] = mfma_bf16_packed(wf1[s_][tau], xf[s_], a1[tau]);
                 }
         }
 #pragma unroll
@@ -194,19 +175,19 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const SkParams p)
                 float sum = 0.f;
 #pragma unroll
                 for (int w = 0; w < NWV; ++w) sum += s_lor[w][tau][e][lane];
-                v[e] = round_bf16(sk_act(sum, 2));
+                v[e] = round_bf16(epilogue_act(sum, 2));
             }
-            *reinterpret_cast<uint2 *>(&s_hid[r16][16 * tau + 4 * qq]) = uint2{sk_pack(v[0], v[1]), sk_pack(v[2], v[3])};
+            *reinterpret_cast<uint2 *>(&s_hid[r16][16 * tau + 4 * qq]) = uint2{pack_bf16_exact(v[0], v[1]), pack_bf16_exact(v[2], v[3])};
         }
         __syncthreads();
     }
-    f32x4s acc[MT][NB];
+    f32x4 acc[MT][NB];
     float ls1[MT], ls2[MT];
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         ls1[i] = 0.f; ls2[i] = 0.f;
 #pragma unroll
-        for (int g = 0; g < NB; ++g) acc[i][g] = f32x4s{0.f, 0.f, 0.f, 0.f};
+        for (int g = 0; g < NB; ++g) acc[i][g] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const bool self_stats = p.ln_self != 0;
 
@@ -240,34 +221,35 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const SkParams p)
                 uint4 a = af[s][i];
                 if constexpr (MIX) {             // xxx = x + (x_prev - x) * maa_x, each op rounded as the reference's op chain does
                     float xc[8], xn[8], mm[8], o[8];
-                    sk_unpack(a, xc); sk_unpack(nf[s][i], xn); sk_unpack(mf[s], mm);
+                    Elem<bf16_t>::unpack(a, xc); Elem<bf16_t>::unpack(nf[s][i], xn); Elem<bf16_t>::unpack(mf[s], mm);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float xx = round_bf16((has_nb[i] ? xn[e] : 0.f) - xc[e]);
                         o[e] = round_bf16(xc[e] + round_bf16(xx * mm[e]));
                     }
-                    a = uint4{sk_pack(o[0], o[1]), sk_pack(o[2], o[3]), sk_pack(o[4], o[5]), sk_pack(o[6], o[7])};
+                    a = uint4{pack_bf16_exact(o[0], o[1]), pack_bf16_exact(o[2], o[3]), pack_bf16_exact(o[4], o[5]),
+                              pack_bf16_exact(o[6], o[7])};
                 }
                 if constexpr (NRM) {             // silu(bf16(LN(a))), rounded again: the two kernels' roundings
                     float xc[8], gg[8], bb[8], o[8];
-                    sk_unpack(a, xc); sk_unpack(mf[s], gg); sk_unpack(bfq[s], bb);
+                    Elem<bf16_t>::unpack(a, xc); Elem<bf16_t>::unpack(mf[s], gg); Elem<bf16_t>::unpack(bfq[s], bb);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float y = round_bf16(fmaf(fmaf(xc[e], n_rstd[i], n_nm[i]), gg[e], bb[e]));
                         o[e] = round_bf16(y * __builtin_amdgcn_rcpf(1.f + __expf(-y)));
                     }
-                    a = uint4{sk_pack(o[0], o[1]), sk_pack(o[2], o[3]), sk_pack(o[4], o[5]), sk_pack(o[6], o[7])};
+                    a = uint4{pack_bf16_exact(o[0], o[1]), pack_bf16_exact(o[2], o[3]), pack_bf16_exact(o[4], o[5]),
+                              pack_bf16_exact(o[6], o[7])};
                 }
                 if (self_stats) {
                     float f[8];
-                    sk_unpack(a, f);
+                    Elem<bf16_t>::unpack(a, f);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { ls1[i] += f[e]; ls2[i] = fmaf(f[e], f[e], ls2[i]); }
                 }
 #pragma unroll
                 for (int g = 0; g < NB; ++g)
-                    acc[i][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8s, wf[s][g]),
-                                                                        __builtin_bit_cast(bf16x8s, a), acc[i][g], 0, 0, 0);
+                    acc[i][g] = mfma_bf16_packed(wf[s][g], a, acc[i][g]);
             }
     };
     int ks = ks0;
@@ -356,7 +338,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const SkParams p)
                 v[0][2] += bf16_bits_to_f32(q.y & 0xffffu); v[0][3] += __uint_as_float(q.y & 0xffff0000u);
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = sk_act(v[0][e], p.act);
+            for (int e = 0; e < 4; ++e) o[e] = epilogue_act(v[0][e], p.act);
         }
         const unsigned short h0 = f32_to_bf16_bits(o[0]), h1 = f32_to_bf16_bits(o[1]), h2 = f32_to_bf16_bits(o[2]),
                              h3 = f32_to_bf16_bits(o[3]);

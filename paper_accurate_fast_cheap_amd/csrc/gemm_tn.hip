@@ -38,8 +38,6 @@ constexpr int TN_NST = 4;                      // LDS stages of 32 KiB
 constexpr int TN_STAGE = 2 * TBK * TBM;        // bf16 elements per stage
 constexpr int TN_DMA_PER_STAGE = 4;            // LDS-DMA instructions per lane and stage
 constexpr int TN_EPI_FLOATS = TBM * (TBN + 4) + TBM;   // one K group's fp32 tile [128][132] + its 128 column sums of dY
-typedef float f32x4t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8t __attribute__((ext_vector_type(8)));
 typedef short s16x4t __attribute__((ext_vector_type(4)));
 typedef short s16x8t __attribute__((ext_vector_type(8)));
 
@@ -51,11 +49,6 @@ struct TnParams {
     long sA, sB;             // batch strides of dY and X (elements); the partials of entry z start at part + z * S * M * N
     int M, N, mtiles, ntiles, S, batch;
 };
-
-__device__ __forceinline__ void tdma16(const bf16_t *src, bf16_t *lds_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_base, 16, 0, 0);
-}
 
 // Eight transposing LDS reads (ds_read_b64_tr_b16: the lane supplies the address of 4 columns of one row and receives
 // 4 rows of one column) as inline assembly.  The intrinsic form (__builtin_amdgcn_ds_read_tr16_b64_v4i16) carries no memory
@@ -108,24 +101,24 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(const TnParams p) {
         for (int j = 0; j < 2; ++j) {
             const long r = min(kb + d_row[j], k_end - 1);
             const int base = (j * 8 + wave) * 4 * TBM;
-            tdma16(Ab + r * p.lda + a_col[j], At + base);
-            tdma16(Bb + r * p.ldb + b_col[j], Bt + base);
+            global_to_lds16(Ab + r * p.lda + a_col[j], At + base);
+            global_to_lds16(Bb + r * p.ldb + b_col[j], Bt + base);
         }
     };
 
-    f32x4t acc[4][4];
+    f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4t{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // bias gradient = column sums of dY: one more MFMA per dY operand against a block of ones, in the blocks of the
     // first N-tile only (wave column 0), instead of a separate reduction pass over dY
     const bool want_bias = p.bias_part != nullptr && nt == 0 && wn == 0;   // wave-uniform
-    f32x4t accb[4];
+    f32x4 accb[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) accb[i] = f32x4t{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < 4; ++i) accb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     const s16x8t ones_bits = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
-    const bf16x8t ones = __builtin_bit_cast(bf16x8t, ones_bits);
+    const bf16x8 ones = __builtin_bit_cast(bf16x8, ones_bits);
 
     // transposing reads: lane 4 q + pp of 16-lane group g supplies the address of row (8 g + 4 h + q), columns
     // 16 blk + 4 pp .. + 3 and receives column (lane & 15) of the four rows.  Byte offsets inside a stage, [2 i + h]:
@@ -181,11 +174,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_kernel(const TnParams p) {
         asm volatile("s_barrier" ::: "memory");
         if (it + TN_NST < iters) issue(it + TN_NST, it % TN_NST);
         if (it + 1 < iters) read_frags(it + 1, na, nb);
-        bf16x8t af[4], bfr[4];
+        bf16x8 af[4], bfr[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            af[i] = __builtin_bit_cast(bf16x8t, __builtin_shufflevector(ca[2 * i], ca[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7));
-            bfr[i] = __builtin_bit_cast(bf16x8t, __builtin_shufflevector(cb[2 * i], cb[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7));
+            af[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(ca[2 * i], ca[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7));
+            bfr[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(cb[2 * i], cb[2 * i + 1], 0, 1, 2, 3, 4, 5, 6, 7));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)

@@ -22,28 +22,6 @@ namespace {
 constexpr int VEC = 8;       // channels per lane per iteration
 constexpr int MAXIT = 2;     // => C <= 64 * 8 * 2 = 1024
 
-template <typename ET> __device__ __forceinline__ void load8(const ET *p, float *f);
-template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t *p, float *f) {
-    Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(p), f);
-}
-template <> __device__ __forceinline__ void load8<float>(const float *p, float *f) {
-    const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename ET> __device__ __forceinline__ void store8(ET *p, const float *f);
-template <> __device__ __forceinline__ void store8<bf16_t>(bf16_t *p, const float *f) {
-    uint4 q;
-    q.x = f32_to_bf16_bits(f[0]) | (f32_to_bf16_bits(f[1]) << 16);
-    q.y = f32_to_bf16_bits(f[2]) | (f32_to_bf16_bits(f[3]) << 16);
-    q.z = f32_to_bf16_bits(f[4]) | (f32_to_bf16_bits(f[5]) << 16);
-    q.w = f32_to_bf16_bits(f[6]) | (f32_to_bf16_bits(f[7]) << 16);
-    *reinterpret_cast<uint4 *>(p) = q;
-}
-template <> __device__ __forceinline__ void store8<float>(float *p, const float *f) {
-    reinterpret_cast<float4 *>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-    reinterpret_cast<float4 *>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-}
-
 // An fp32 value as two bf16 planes, hi = bf16(x), lo = bf16(x - hi): 16 significant bits, the form the phase-pipelined GEMM
 // takes as the A operand of an fp32 model (csrc/gemm_ph.hip).  Output "dtype" PAFC_SPLIT_BF16: a row is [hi (C) | lo (C)].
 __device__ __forceinline__ void store8_split(bf16_t *hi_p, bf16_t *lo_p, const float *f) {
@@ -275,8 +253,6 @@ __global__ __launch_bounds__(256) void tmix_mix4_kernel(int T, int C, long rows,
 // columns; the MFMA is issued with M = output column, N = time row, so each lane ends up with 4 consecutive columns
 // of ITS row per MFMA and, with the column slots of two MFMAs interleaved, 8 = one 16-byte store.
 //   x: (rows, C); t: (ndir, rows, 128); w2t: (ndir, 4, C, 32) (W2 with K innermost); maa: (ndir, 4, C); z: (4, ndir, rows, C)
-typedef float f32x4g __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8g __attribute__((ext_vector_type(8)));
 template <bool LDSW, bool FULLROW = false>
 __global__ __launch_bounds__(256) void tmix_lora_mix4_kernel(int T, int C, long rows, int ndir, int rev0,
                                                              const bf16_t *__restrict__ x, const bf16_t *__restrict__ t,
@@ -288,7 +264,7 @@ __global__ __launch_bounds__(256) void tmix_lora_mix4_kernel(int T, int C, long 
     const long row = ((long)blockIdx.x * 4 + wave) * 16 + r16;
     const long rowc = row < rows ? row : rows - 1;     // clamp (every lane takes part in the MFMAs), skip the store
     const int tt = (int)(rowc % T);
-    const f32x4g zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     // the MFMA leaves a lane with 8 columns of ITS row; through LDS the tile goes back to whole 128-byte row
     // segments per 8 lanes, so z is stored in full lines
     constexpr int LDZ = 64 + 8;
@@ -343,10 +319,8 @@ __global__ __launch_bounds__(256) void tmix_lora_mix4_kernel(int T, int C, long 
                     a1 = *reinterpret_cast<const uint4 *>(wq + (size_t)colA * 32);
                     a2 = *reinterpret_cast<const uint4 *>(wq + (size_t)(colA + 4) * 32);
                 }
-                const f32x4g m1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, a1),
-                                                                         __builtin_bit_cast(bf16x8g, tb[q]), zero, 0, 0, 0);
-                const f32x4g m2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, a2),
-                                                                         __builtin_bit_cast(bf16x8g, tb[q]), zero, 0, 0, 0);
+                const f32x4 m1 = mfma_bf16_packed(a1, tb[q], zero);
+                const f32x4 m2 = mfma_bf16_packed(a2, tb[q], zero);
                 float av[VEC], o[VEC];
                 load8<bf16_t>(maa + ((size_t)d * 4 + q) * C + col, av);
 #pragma unroll
@@ -391,7 +365,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
     const int cy = blockIdx.y * WCOLS + wave % WCOLS, d = blockIdx.z;
     const int wrow = wave / WCOLS;
     const bool rev = (d == 0) ? (rev0 != 0) : true;
-    const f32x4g zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     constexpr int LDZ = 64 + 8;
     __shared__ __attribute__((aligned(16))) bf16_t s_z[NW][16][LDZ];
     const int colslot = 8 * (r16 >> 2) + (r16 & 3);
@@ -432,10 +406,8 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int cbi = 0; cbi < 2; ++cbi) {
-                const f32x4g m1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, a1[q][cbi]),
-                                                                         __builtin_bit_cast(bf16x8g, tb[q]), zero, 0, 0, 0);
-                const f32x4g m2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, a2[q][cbi]),
-                                                                         __builtin_bit_cast(bf16x8g, tb[q]), zero, 0, 0, 0);
+                const f32x4 m1 = mfma_bf16_packed(a1[q][cbi], tb[q], zero);
+                const f32x4 m2 = mfma_bf16_packed(a2[q][cbi], tb[q], zero);
                 const unsigned aw[4] = {av[q][cbi].x, av[q][cbi].y, av[q][cbi].z, av[q][cbi].w};
                 float o[VEC];
 #pragma unroll
@@ -471,18 +443,6 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
 // with the k-slots of a step taken as (4 of tile 2p | 4 of tile 2p+1), and w leaves through a per-wave LDS tile in full
 // lines.  The 64-wide hidden tensor never exists in memory and z_w / w cross HBM once each (two library-shaped GEMMs: 83 us
 // for 206 MB at the 30-minute shape).
-typedef unsigned int u32x4g __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float tanh_as_gemm_epilogue(float v) {   // the form gemm_bf16.hip / gemm_ph.hip apply (act 2)
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(__expf(2.f * v) + 1.f);
-}
-__device__ __forceinline__ unsigned pack_bf16_rne(float lo, float hi) {     // round to nearest even and pack: one v_cvt_pk_bf16_f32
-    typedef float f32x2r __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2r __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2r{lo, hi}, bf16x2r));
-}
-__device__ __forceinline__ unsigned pack_bf16_exact(float lo, float hi) {   // both already bf16 values
-    return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
-}
 constexpr int DL_C = 512, DL_H = 64;      // model width and LoRA width this kernel is built for (checked on the host)
 constexpr int DL_WAVES = 8;
 __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, int ndir, const bf16_t *__restrict__ zw,
@@ -492,7 +452,7 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
     constexpr int C = DL_C;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, qq = lane >> 4;
-    const f32x4g zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     constexpr int LDZ = 64 + 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char dl_lds[];
     uint4 *s_d1 = reinterpret_cast<uint4 *>(dl_lds);                       // [ks 16][tau 4][lane 64]   64 KiB
@@ -520,34 +480,31 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
             uint4 zf[16];
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) zf[ks] = *reinterpret_cast<const uint4 *>(zr + 32 * ks);
-            f32x4g acc1[4] = {zero, zero, zero, zero};
+            f32x4 acc1[4] = {zero, zero, zero, zero};
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks)
 #pragma unroll
                 for (int tau = 0; tau < 4; ++tau)
-                    acc1[tau] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, s_d1[(ks * 4 + tau) * 64 + lane]),
-                                                                         __builtin_bit_cast(bf16x8g, zf[ks]), acc1[tau], 0, 0, 0);
+                    acc1[tau] = mfma_bf16_packed(s_d1[(ks * 4 + tau) * 64 + lane], zf[ks], acc1[tau]);
             // tanh + rounding; k-step p of the second product takes n1 = 32 p + 4 qq + e (e < 4) | 32 p + 16 + 4 qq + e - 4
-            u32x4g b2[2];
+            u32x4 b2[2];
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 float v[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = round_bf16(tanh_as_gemm_epilogue(acc1[2 * p + (e >> 2)][e & 3]));
-                b2[p] = u32x4g{pack_bf16_exact(v[0], v[1]), pack_bf16_exact(v[2], v[3]),
-                               pack_bf16_exact(v[4], v[5]), pack_bf16_exact(v[6], v[7])};
+                for (int e = 0; e < 8; ++e) v[e] = round_bf16(epilogue_act<2>(acc1[2 * p + (e >> 2)][e & 3]));
+                b2[p] = u32x4{pack_bf16_exact(v[0], v[1]), pack_bf16_exact(v[2], v[3]),
+                              pack_bf16_exact(v[4], v[5]), pack_bf16_exact(v[6], v[7])};
             }
             for (int cy = 0; cy < C / 64; ++cy) {
 #pragma unroll
                 for (int cbi = 0; cbi < 2; ++cbi) {
                     const int cb = cy * 2 + cbi;
-                    f32x4g o[2];
+                    f32x4 o[2];
 #pragma unroll
                     for (int a = 0; a < 2; ++a) {
-                        o[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, s_d2[((cb * 2 + a) * 2 + 0) * 64 + lane]),
-                                                                       __builtin_bit_cast(bf16x8g, b2[0]), zero, 0, 0, 0);
-                        o[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8g, s_d2[((cb * 2 + a) * 2 + 1) * 64 + lane]),
-                                                                       __builtin_bit_cast(bf16x8g, b2[1]), o[a], 0, 0, 0);
+                        o[a] = mfma_bf16_packed(s_d2[((cb * 2 + a) * 2 + 0) * 64 + lane], b2[0], zero);
+                        o[a] = mfma_bf16_packed(s_d2[((cb * 2 + a) * 2 + 1) * 64 + lane], b2[1], o[a]);
                     }
                     float ov[VEC];
 #pragma unroll
@@ -593,7 +550,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
     constexpr int C = LD_C;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, qq = lane >> 4;
-    const f32x4g zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     extern __shared__ __attribute__((aligned(16))) unsigned char dl_lds[];
     uint4 *s_w1 = reinterpret_cast<uint4 *>(dl_lds);                       // [ks 16][np 4][a 2][lane 64]   128 KiB
     const int colslot = 8 * (r16 >> 2) + (r16 & 3);
@@ -613,7 +570,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
         const bool has_nb = in_seq || (prev != nullptr && !rev);       // prev: (B, C) the frame before each sequence, or null
         const bf16_t *nbrow = in_seq ? x + (rev ? rowc + 1 : rowc - 1) * C : (has_nb ? prev + (rowc / T) * C : x + rowc * C);
         const bf16_t *xr = x + rowc * C + 8 * qq, *xnr = nbrow + 8 * qq, *mr = maa_x + (size_t)d * C + 8 * qq;
-        f32x4g acc[4][2];
+        f32x4 acc[4][2];
 #pragma unroll
         for (int np = 0; np < 4; ++np) { acc[np][0] = zero; acc[np][1] = zero; }
 #pragma unroll 1
@@ -630,8 +587,8 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
                 const float xx = round_bf16((has_nb ? xn[e] : 0.f) - xc[e]);
                 o[e] = xc[e] + round_bf16(xx * mm[e]);              // (rounded by the packing conversion below: one v_cvt_pk per pair)
             }
-            const u32x4g bq = {pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]),
-                               pack_bf16_rne(o[6], o[7])};
+            const u32x4 bq = {pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]),
+                              pack_bf16_rne(o[6], o[7])};
             // the K-step's products at raised wave priority: a wave that has formed its operand (115 VALU instructions per K-step)
             // gets the matrix pipe ahead of the waves still forming theirs (8 waves per block: 49.0 -> 43.5 us; 16: 47.6 -> 45.3)
             __builtin_amdgcn_s_setprio(1);
@@ -639,9 +596,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
             for (int np = 0; np < 4; ++np)
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
-                    acc[np][a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        __builtin_bit_cast(bf16x8g, s_w1[((ks * 4 + np) * 2 + a) * 64 + lane]), __builtin_bit_cast(bf16x8g, bq),
-                        acc[np][a], 0, 0, 0);
+                    acc[np][a] = mfma_bf16_packed(s_w1[((ks * 4 + np) * 2 + a) * 64 + lane], bq, acc[np][a]);
             __builtin_amdgcn_s_setprio(0);
         }
         if (row < rows) {
@@ -649,7 +604,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
             for (int np = 0; np < 4; ++np) {
                 float o[VEC];
 #pragma unroll
-                for (int e = 0; e < VEC; ++e) o[e] = tanh_as_gemm_epilogue(e < 4 ? acc[np][0][e] : acc[np][1][e - 4]);
+                for (int e = 0; e < VEC; ++e) o[e] = epilogue_act<2>(e < 4 ? acc[np][0][e] : acc[np][1][e - 4]);
                 store8<bf16_t>(tout + ((size_t)d * rows + row) * LD_N + 32 * np + 8 * qq, o);
             }
         }

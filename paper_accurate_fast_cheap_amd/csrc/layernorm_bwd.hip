@@ -18,28 +18,6 @@ constexpr int LVEC = 8;        // channels per lane per iteration
 constexpr int LMAXIT = 2;      // => C <= 64 * 8 * 2 = 1024, as the forward kernel
 constexpr int ROWS_PER_BLOCK = 16;   // 4 rows per wave: ~4 blocks per CU in flight at the c4 shape (16 000 rows)
 
-template <typename ET> __device__ __forceinline__ void ld8(const ET *p, float *f);
-template <> __device__ __forceinline__ void ld8<bf16_t>(const bf16_t *p, float *f) {
-    Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(p), f);
-}
-template <> __device__ __forceinline__ void ld8<float>(const float *p, float *f) {
-    const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename ET> __device__ __forceinline__ void st8(ET *p, const float *f);
-template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t *p, const float *f) {
-    uint4 q;
-    q.x = f32_to_bf16_bits(f[0]) | (f32_to_bf16_bits(f[1]) << 16);
-    q.y = f32_to_bf16_bits(f[2]) | (f32_to_bf16_bits(f[3]) << 16);
-    q.z = f32_to_bf16_bits(f[4]) | (f32_to_bf16_bits(f[5]) << 16);
-    q.w = f32_to_bf16_bits(f[6]) | (f32_to_bf16_bits(f[7]) << 16);
-    *reinterpret_cast<uint4 *>(p) = q;
-}
-template <> __device__ __forceinline__ void st8<float>(float *p, const float *f) {
-    reinterpret_cast<float4 *>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-    reinterpret_cast<float4 *>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-}
-
 // EX: dtype of x, gamma and dx; ED: dtype of dy
 template <typename EX, typename ED>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(long rows, int C, const EX *__restrict__ x,
@@ -54,7 +32,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(long rows, int C, co
         const int c = (it * 64 + lane) * LVEC;
 #pragma unroll
         for (int e = 0; e < LVEC; ++e) { gm[it][e] = 0.f; ag[it][e] = 0.f; ab[it][e] = 0.f; }
-        if (c < C) ld8<EX>(gamma + c, gm[it]);
+        if (c < C) load8<EX>(gamma + c, gm[it]);
     }
     const long r_end = min(rows, ((long)blockIdx.x + 1) * ROWS_PER_BLOCK);
     for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < r_end; row += 4) {
@@ -64,8 +42,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(long rows, int C, co
         for (int it = 0; it < LMAXIT; ++it) {
             const int c = (it * 64 + lane) * LVEC;
             if (c < C) {
-                ld8<EX>(x + (size_t)row * C + c, xv[it]);
-                ld8<ED>(dy + (size_t)row * C + c, gv[it]);
+                load8<EX>(x + (size_t)row * C + c, xv[it]);
+                load8<ED>(dy + (size_t)row * C + c, gv[it]);
 #pragma unroll
                 for (int e = 0; e < LVEC; ++e) sum += xv[it][e];
             }
@@ -111,11 +89,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(long rows, int C, co
                 for (int e = 0; e < LVEC; ++e) o[e] = rstd * (gv[it][e] - s1 - xv[it][e] * s2);
                 if (dx_add != nullptr) {     // the gradient that reaches x past the norm (the residual path of a pre-norm branch)
                     float av[LVEC];
-                    ld8<EX>(dx_add + (size_t)row * C + c, av);
+                    load8<EX>(dx_add + (size_t)row * C + c, av);
 #pragma unroll
                     for (int e = 0; e < LVEC; ++e) o[e] += av[e];
                 }
-                st8<EX>(dx + (size_t)row * C + c, o);
+                store8<EX>(dx + (size_t)row * C + c, o);
             }
         }
     }
@@ -173,7 +151,7 @@ __global__ __launch_bounds__(256) void ln_silu_fwd_kernel(long rows, int C, cons
         const int c = (it * 64 + lane) * LVEC;
 #pragma unroll
         for (int e = 0; e < LVEC; ++e) { gm[it][e] = 0.f; bt[it][e] = 0.f; }
-        if (c < C) { ld8<EG>(gamma + c, gm[it]); ld8<EG>(beta + c, bt[it]); }
+        if (c < C) { load8<EG>(gamma + c, gm[it]); load8<EG>(beta + c, bt[it]); }
     }
     const long r_end = min(rows, ((long)blockIdx.x + 1) * ROWS_PER_BLOCK);
     for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < r_end; row += 4) {
@@ -183,7 +161,7 @@ __global__ __launch_bounds__(256) void ln_silu_fwd_kernel(long rows, int C, cons
         for (int it = 0; it < LMAXIT; ++it) {
             const int c = (it * 64 + lane) * LVEC;
             if (c < C) {
-                ld8<EX>(x + (size_t)row * C + c, xv[it]);
+                load8<EX>(x + (size_t)row * C + c, xv[it]);
 #pragma unroll
                 for (int e = 0; e < LVEC; ++e) sum += xv[it][e];
             }
@@ -209,7 +187,7 @@ __global__ __launch_bounds__(256) void ln_silu_fwd_kernel(long rows, int C, cons
                     const float z = fmaf((xv[it][e] - mean) * rstd, gm[it][e], bt[it][e]);
                     o[e] = z / (1.f + __expf(-z));
                 }
-                st8<EX>(y + (size_t)row * C + c, o);
+                store8<EX>(y + (size_t)row * C + c, o);
             }
         }
     }
@@ -227,7 +205,7 @@ __global__ __launch_bounds__(256) void ln_silu_bwd_kernel(long rows, int C, cons
         const int c = (it * 64 + lane) * LVEC;
 #pragma unroll
         for (int e = 0; e < LVEC; ++e) { gm[it][e] = 0.f; bt[it][e] = 0.f; ag[it][e] = 0.f; ab[it][e] = 0.f; }
-        if (c < C) { ld8<EG>(gamma + c, gm[it]); ld8<EG>(beta + c, bt[it]); }
+        if (c < C) { load8<EG>(gamma + c, gm[it]); load8<EG>(beta + c, bt[it]); }
     }
     const long r_end = min(rows, ((long)blockIdx.x + 1) * ROWS_PER_BLOCK);
     for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < r_end; row += 4) {
@@ -237,8 +215,8 @@ __global__ __launch_bounds__(256) void ln_silu_bwd_kernel(long rows, int C, cons
         for (int it = 0; it < LMAXIT; ++it) {
             const int c = (it * 64 + lane) * LVEC;
             if (c < C) {
-                ld8<EX>(x + (size_t)row * C + c, xv[it]);
-                ld8<EX>(dy + (size_t)row * C + c, gv[it]);
+                load8<EX>(x + (size_t)row * C + c, xv[it]);
+                load8<EX>(dy + (size_t)row * C + c, gv[it]);
 #pragma unroll
                 for (int e = 0; e < LVEC; ++e) sum += xv[it][e];
             }
@@ -284,7 +262,7 @@ __global__ __launch_bounds__(256) void ln_silu_bwd_kernel(long rows, int C, cons
                 float o[LVEC];
 #pragma unroll
                 for (int e = 0; e < LVEC; ++e) o[e] = rstd * (gv[it][e] - s1 - xv[it][e] * s2);
-                st8<EX>(dx + (size_t)row * C + c, o);
+                store8<EX>(dx + (size_t)row * C + c, o);
             }
         }
     }

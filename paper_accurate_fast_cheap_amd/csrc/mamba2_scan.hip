@@ -53,7 +53,7 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
     __shared__ __attribute__((aligned(16))) bf16_t s_x[(WRITE_Y && Y16) ? SBL : 1][SP + 8];   // x of the block, [step][channel], for the skip term
 
     // 0/1 selection operands of the layout-changing MFMAs (as in wkv6_mfma.inc)
-    su32x4 selA = {0u, 0u, 0u, 0u}, selB = {0u, 0u, 0u, 0u};
+    u32x4 selA = {0u, 0u, 0u, 0u}, selB = {0u, 0u, 0u, 0u};
     {
         const int e = t16 - 4 * q;
         const unsigned one_lo = 0x3f80u, one_hi = 0x3f800000u;
@@ -62,10 +62,10 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
         if (e == 2) { selA[1] = one_lo; selB[3] = one_lo; }
         if (e == 3) { selA[1] = one_hi; selB[3] = one_hi; }
     }
-    const sf32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     const size_t seq = (size_t)b * p.H + h;
-    sf32x4 S[8][4];
+    f32x4 S[8][4];
     {
         const float *src = (WRITE_Y && p.NC > 1) ? p.ws_state + (seq * p.NC + c) * (size_t)(SN * SP) : nullptr;
         if constexpr (STATE) {
@@ -125,50 +125,50 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
         const float e15 = __expf(c15);
 
         // ---- x re-laid out with time as the contraction index (lane = channel, slot = step): selection MFMAs ------
-        su32x4 xT[4];
+        u32x4 xT[4];
 #pragma unroll
         for (int ip = 0; ip < 4; ip += 2) {
-            const su32x4 vh = {xr[ip].x, xr[ip].y, xr[ip + 1].x, xr[ip + 1].y};
-            const sf32x4 t0 = smfma(vh, selA, zero4), t1 = smfma(vh, selB, zero4);
-            xT[ip] = su32x4{spack_exact(t0[0], t0[1]), spack_exact(t0[2], t0[3]), 0u, 0u};
-            xT[ip + 1] = su32x4{spack_exact(t1[0], t1[1]), spack_exact(t1[2], t1[3]), 0u, 0u};
+            const u32x4 vh = {xr[ip].x, xr[ip].y, xr[ip + 1].x, xr[ip + 1].y};
+            const f32x4 t0 = mfma_bf16_packed(vh, selA, zero4), t1 = mfma_bf16_packed(vh, selB, zero4);
+            xT[ip] = u32x4{pack_bf16_exact(t0[0], t0[1]), pack_bf16_exact(t0[2], t0[3]), 0u, 0u};
+            xT[ip + 1] = u32x4{pack_bf16_exact(t1[0], t1[1]), pack_bf16_exact(t1[2], t1[3]), 0u, 0u};
         }
 
         if constexpr (WRITE_Y) {
             // ---- (C B^T)[s][t], exact: A rows = B_s, B columns = C_t, K = the 128 state dimensions -----------------
-            sf32x4 G = zero4;
+            f32x4 G = zero4;
 #pragma unroll
             for (int pr = 0; pr < 8; pr += 2) {
-                const su32x4 a = {Br[pr].x, Br[pr].y, Br[pr + 1].x, Br[pr + 1].y};
-                const su32x4 bq = {Cr[pr].x, Cr[pr].y, Cr[pr + 1].x, Cr[pr + 1].y};
-                G = smfma(a, bq, G);
+                const u32x4 a = {Br[pr].x, Br[pr].y, Br[pr + 1].x, Br[pr + 1].y};
+                const u32x4 bq = {Cr[pr].x, Cr[pr].y, Cr[pr + 1].x, Cr[pr + 1].y};
+                G = mfma_bf16_packed(a, bq, G);
             }
             // M[s][t] = G e^{cum_t - cum_s} dt_s for s <= t (this lane: t = t16, s = 4 q + g), split hi + lo
             float Mv[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) Mv[g] = (4 * q + g <= t16) ? G[g] * __expf(cum - cs[g]) * ds[g] : 0.f;
-            su32x4 Mh = {0u, 0u, 0u, 0u}, Ml = {0u, 0u, 0u, 0u};
-            { const SHiLo u = ssplit_pk(Mv[0], Mv[1]); Mh[0] = u.hi; Ml[0] = u.lo; }
-            { const SHiLo u = ssplit_pk(Mv[2], Mv[3]); Mh[1] = u.hi; Ml[1] = u.lo; }
+            u32x4 Mh = {0u, 0u, 0u, 0u}, Ml = {0u, 0u, 0u, 0u};
+            { const Bf16HiLo u = split_bf16_hilo(Mv[0], Mv[1]); Mh[0] = u.hi; Ml[0] = u.lo; }
+            { const Bf16HiLo u = split_bf16_hilo(Mv[2], Mv[3]); Mh[1] = u.hi; Ml[1] = u.lo; }
             // ---- y_t = e^{cum_t} C_t . H (split state) + sum_s M[s][t] x_s ----------------------------------------
 #pragma unroll
             for (int in = 0; in < 4; ++in) {
-                sf32x4 Y = zero4;
+                f32x4 Y = zero4;
 #pragma unroll
                 for (int pr = 0; pr < 8; pr += 2) {
-                    const su32x4 a = {Cr[pr].x, Cr[pr].y, Cr[pr + 1].x, Cr[pr + 1].y};
-                    su32x4 sh, sl;
-                    { const SHiLo u = ssplit_pk(S[pr][in][0], S[pr][in][1]); sh[0] = u.hi; sl[0] = u.lo; }
-                    { const SHiLo u = ssplit_pk(S[pr][in][2], S[pr][in][3]); sh[1] = u.hi; sl[1] = u.lo; }
-                    { const SHiLo u = ssplit_pk(S[pr + 1][in][0], S[pr + 1][in][1]); sh[2] = u.hi; sl[2] = u.lo; }
-                    { const SHiLo u = ssplit_pk(S[pr + 1][in][2], S[pr + 1][in][3]); sh[3] = u.hi; sl[3] = u.lo; }
-                    Y = smfma(a, sh, Y);
-                    Y = smfma(a, sl, Y);
+                    const u32x4 a = {Cr[pr].x, Cr[pr].y, Cr[pr + 1].x, Cr[pr + 1].y};
+                    u32x4 sh, sl;
+                    { const Bf16HiLo u = split_bf16_hilo(S[pr][in][0], S[pr][in][1]); sh[0] = u.hi; sl[0] = u.lo; }
+                    { const Bf16HiLo u = split_bf16_hilo(S[pr][in][2], S[pr][in][3]); sh[1] = u.hi; sl[1] = u.lo; }
+                    { const Bf16HiLo u = split_bf16_hilo(S[pr + 1][in][0], S[pr + 1][in][1]); sh[2] = u.hi; sl[2] = u.lo; }
+                    { const Bf16HiLo u = split_bf16_hilo(S[pr + 1][in][2], S[pr + 1][in][3]); sh[3] = u.hi; sl[3] = u.lo; }
+                    Y = mfma_bf16_packed(a, sh, Y);
+                    Y = mfma_bf16_packed(a, sl, Y);
                 }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) Y[g] *= __expf(cs[g]);       // rows of the C/D layout are t = 4 q + g
-                Y = smfma(Mh, xT[in], Y);
-                Y = smfma(Ml, xT[in], Y);
+                Y = mfma_bf16_packed(Mh, xT[in], Y);
+                Y = mfma_bf16_packed(Ml, xT[in], Y);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) s_y[4 * q + g][16 * in + t16] = Y[g];
             }
@@ -180,29 +180,29 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
         const float csc = __expf(c15 - cum) * dt_own;            // this lane's row s = t16
 #pragma unroll
         for (int pr = 0; pr < 8; pr += 2) {
-            su32x4 kh, kl;
+            u32x4 kh, kl;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const uint2 r = Br[pr + e];
                 const float b0 = bf16_bits_to_f32(r.x & 0xffffu) * csc, b1 = __uint_as_float(r.x & 0xffff0000u) * csc;
                 const float b2 = bf16_bits_to_f32(r.y & 0xffffu) * csc, b3 = __uint_as_float(r.y & 0xffff0000u) * csc;
-                const SHiLo u0 = ssplit_pk(b0, b1), u1 = ssplit_pk(b2, b3);
+                const Bf16HiLo u0 = split_bf16_hilo(b0, b1), u1 = split_bf16_hilo(b2, b3);
                 kh[2 * e] = u0.hi; kh[2 * e + 1] = u1.hi; kl[2 * e] = u0.lo; kl[2 * e + 1] = u1.lo;
             }
-            const sf32x4 h0 = smfma(kh, selA, zero4), h1 = smfma(kh, selB, zero4);
-            const sf32x4 l0 = smfma(kl, selA, zero4), l1 = smfma(kl, selB, zero4);
-            const su32x4 ah0 = {spack_exact(h0[0], h0[1]), spack_exact(h0[2], h0[3]), 0u, 0u};
-            const su32x4 ah1 = {spack_exact(h1[0], h1[1]), spack_exact(h1[2], h1[3]), 0u, 0u};
-            const su32x4 al0 = {spack_exact(l0[0], l0[1]), spack_exact(l0[2], l0[3]), 0u, 0u};
-            const su32x4 al1 = {spack_exact(l1[0], l1[1]), spack_exact(l1[2], l1[3]), 0u, 0u};
+            const f32x4 h0 = mfma_bf16_packed(kh, selA, zero4), h1 = mfma_bf16_packed(kh, selB, zero4);
+            const f32x4 l0 = mfma_bf16_packed(kl, selA, zero4), l1 = mfma_bf16_packed(kl, selB, zero4);
+            const u32x4 ah0 = {pack_bf16_exact(h0[0], h0[1]), pack_bf16_exact(h0[2], h0[3]), 0u, 0u};
+            const u32x4 ah1 = {pack_bf16_exact(h1[0], h1[1]), pack_bf16_exact(h1[2], h1[3]), 0u, 0u};
+            const u32x4 al0 = {pack_bf16_exact(l0[0], l0[1]), pack_bf16_exact(l0[2], l0[3]), 0u, 0u};
+            const u32x4 al1 = {pack_bf16_exact(l1[0], l1[1]), pack_bf16_exact(l1[2], l1[3]), 0u, 0u};
 #pragma unroll
             for (int in = 0; in < 4; ++in) {
                 S[pr][in] *= e15;
                 S[pr + 1][in] *= e15;
-                S[pr][in] = smfma(ah0, xT[in], S[pr][in]);
-                S[pr + 1][in] = smfma(ah1, xT[in], S[pr + 1][in]);
-                S[pr][in] = smfma(al0, xT[in], S[pr][in]);
-                S[pr + 1][in] = smfma(al1, xT[in], S[pr + 1][in]);
+                S[pr][in] = mfma_bf16_packed(ah0, xT[in], S[pr][in]);
+                S[pr + 1][in] = mfma_bf16_packed(ah1, xT[in], S[pr + 1][in]);
+                S[pr][in] = mfma_bf16_packed(al0, xT[in], S[pr][in]);
+                S[pr + 1][in] = mfma_bf16_packed(al1, xT[in], S[pr + 1][in]);
             }
         }
 
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_kernel(const SsdParams p) {
                         const float o2 = fmaf(dk, bf16_bits_to_f32(xq.y & 0xffffu), v.z);
                         const float o3 = fmaf(dk, __uint_as_float(xq.y & 0xffff0000u), v.w);
                         *reinterpret_cast<uint2 *>(p.y16 + ((size_t)b * p.L + trow) * p.d_inner + h * SP + col) =
-                            make_uint2(scvt_pk(o0, o1), scvt_pk(o2, o3));
+                            make_uint2(pack_bf16_rne(o0, o1), pack_bf16_rne(o2, o3));
                     } else {
                         *reinterpret_cast<float4 *>(p.y + ((size_t)b * p.L + trow) * p.d_inner + h * SP + col) = v;
                     }

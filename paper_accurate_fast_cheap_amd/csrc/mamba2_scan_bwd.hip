@@ -43,9 +43,9 @@ struct SsdBwdParams {
     float *dla;            // [B][L][H]: C . gC - B . gB
 };
 
-__device__ __forceinline__ void sel_operands(int t16, int q, su32x4 &selA, su32x4 &selB) {
-    selA = su32x4{0u, 0u, 0u, 0u};
-    selB = su32x4{0u, 0u, 0u, 0u};
+__device__ __forceinline__ void sel_operands(int t16, int q, u32x4 &selA, u32x4 &selB) {
+    selA = u32x4{0u, 0u, 0u, 0u};
+    selB = u32x4{0u, 0u, 0u, 0u};
     const int e = t16 - 4 * q;
     const unsigned one_lo = 0x3f80u, one_hi = 0x3f800000u;
     if (e == 0) { selA[0] = one_lo; selB[2] = one_lo; }
@@ -58,15 +58,15 @@ struct SSplit4 { unsigned h0, h1, l0, l1; };
 __device__ __forceinline__ SSplit4 scale_split(uint2 r, float f) {
     const float b0 = bf16_bits_to_f32(r.x & 0xffffu) * f, b1 = __uint_as_float(r.x & 0xffff0000u) * f;
     const float b2 = bf16_bits_to_f32(r.y & 0xffffu) * f, b3 = __uint_as_float(r.y & 0xffff0000u) * f;
-    const SHiLo u0 = ssplit_pk(b0, b1), u1 = ssplit_pk(b2, b3);
+    const Bf16HiLo u0 = split_bf16_hilo(b0, b1), u1 = split_bf16_hilo(b2, b3);
     return SSplit4{u0.hi, u1.hi, u0.lo, u1.lo};
 }
 // two rows-by-time tiles (Lt layout, exact bf16) -> time-by-channel operands (lane = channel, slot = step)
-__device__ __forceinline__ void transpose_pair(su32x4 v, su32x4 selA, su32x4 selB, su32x4 &o0, su32x4 &o1) {
-    const sf32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const sf32x4 t0 = smfma(v, selA, zero4), t1 = smfma(v, selB, zero4);
-    o0 = su32x4{spack_exact(t0[0], t0[1]), spack_exact(t0[2], t0[3]), 0u, 0u};
-    o1 = su32x4{spack_exact(t1[0], t1[1]), spack_exact(t1[2], t1[3]), 0u, 0u};
+__device__ __forceinline__ void transpose_pair(u32x4 v, u32x4 selA, u32x4 selB, u32x4 &o0, u32x4 &o1) {
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 t0 = mfma_bf16_packed(v, selA, zero4), t1 = mfma_bf16_packed(v, selB, zero4);
+    o0 = u32x4{pack_bf16_exact(t0[0], t0[1]), pack_bf16_exact(t0[2], t0[3]), 0u, 0u};
+    o1 = u32x4{pack_bf16_exact(t1[0], t1[1]), pack_bf16_exact(t1[2], t1[3]), 0u, 0u};
 }
 __device__ __forceinline__ float dot4(float4 a, uint2 b) {
     return a.x * bf16_bits_to_f32(b.x & 0xffffu) + a.y * __uint_as_float(b.x & 0xffff0000u)
@@ -88,12 +88,12 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_h_kernel(const SsdBwdPar
     __shared__ float s_cum[SBL], s_dt[SBL];
     __shared__ __attribute__((aligned(16))) float s_o[EMIT ? SBL : 1][SN + 4];
 
-    su32x4 selA, selB;
+    u32x4 selA, selB;
     sel_operands(t16, q, selA, selB);
-    const sf32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     const size_t seq = (size_t)b * p.H + h;
-    sf32x4 T[4][8];
+    f32x4 T[4][8];
     {
         const float *src = (EMIT && p.NC > 1) ? p.ws_h + (seq * p.NC + c) * (size_t)(SN * SP) : nullptr;
 #pragma unroll
@@ -142,56 +142,56 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_h_kernel(const SsdBwdPar
         const float cs[4] = {cs4.x, cs4.y, cs4.z, cs4.w}, ds[4] = {ds4.x, ds4.y, ds4.z, ds4.w};
         const float e15 = __expf(c15);
 
-        su32x4 xT[4];                                             // lane (i, qq): x[s = 4 qq + g][p = 16 ip + i]
-        transpose_pair(su32x4{xr[0].x, xr[0].y, xr[1].x, xr[1].y}, selA, selB, xT[0], xT[1]);
-        transpose_pair(su32x4{xr[2].x, xr[2].y, xr[3].x, xr[3].y}, selA, selB, xT[2], xT[3]);
+        u32x4 xT[4];                                             // lane (i, qq): x[s = 4 qq + g][p = 16 ip + i]
+        transpose_pair(u32x4{xr[0].x, xr[0].y, xr[1].x, xr[1].y}, selA, selB, xT[0], xT[1]);
+        transpose_pair(u32x4{xr[2].x, xr[2].y, xr[3].x, xr[3].y}, selA, selB, xT[2], xT[3]);
 
         if constexpr (EMIT) {
-            su32x4 gh[2], gl[2];                                  // gy_t as a row operand over p, split
+            u32x4 gh[2], gl[2];                                  // gy_t as a row operand over p, split
 #pragma unroll
             for (int kp = 0; kp < 2; ++kp) {
-                const SHiLo u0 = ssplit_pk(gyr[2 * kp].x, gyr[2 * kp].y), u1 = ssplit_pk(gyr[2 * kp].z, gyr[2 * kp].w);
-                const SHiLo u2 = ssplit_pk(gyr[2 * kp + 1].x, gyr[2 * kp + 1].y), u3 = ssplit_pk(gyr[2 * kp + 1].z, gyr[2 * kp + 1].w);
-                gh[kp] = su32x4{u0.hi, u1.hi, u2.hi, u3.hi};
-                gl[kp] = su32x4{u0.lo, u1.lo, u2.lo, u3.lo};
+                const Bf16HiLo u0 = split_bf16_hilo(gyr[2 * kp].x, gyr[2 * kp].y), u1 = split_bf16_hilo(gyr[2 * kp].z, gyr[2 * kp].w);
+                const Bf16HiLo u2 = split_bf16_hilo(gyr[2 * kp + 1].x, gyr[2 * kp + 1].y), u3 = split_bf16_hilo(gyr[2 * kp + 1].z, gyr[2 * kp + 1].w);
+                gh[kp] = u32x4{u0.hi, u1.hi, u2.hi, u3.hi};
+                gl[kp] = u32x4{u0.lo, u1.lo, u2.lo, u3.lo};
             }
             // (x gy^T)[s][t]: A rows = x_s (exact), B columns = gy_t, K = the 64 head channels
-            sf32x4 Gm = zero4;
+            f32x4 Gm = zero4;
 #pragma unroll
             for (int kp = 0; kp < 2; ++kp) {
-                const su32x4 a = {xr[2 * kp].x, xr[2 * kp].y, xr[2 * kp + 1].x, xr[2 * kp + 1].y};
-                Gm = smfma(a, gh[kp], Gm);
-                Gm = smfma(a, gl[kp], Gm);
+                const u32x4 a = {xr[2 * kp].x, xr[2 * kp].y, xr[2 * kp + 1].x, xr[2 * kp + 1].y};
+                Gm = mfma_bf16_packed(a, gh[kp], Gm);
+                Gm = mfma_bf16_packed(a, gl[kp], Gm);
             }
             float Mv[4];                                          // this lane: t = t16, s = 4 q + g
 #pragma unroll
             for (int g = 0; g < 4; ++g) Mv[g] = (4 * q + g <= t16) ? Gm[g] * __expf(cum - cs[g]) * ds[g] : 0.f;
-            su32x4 Mh = {0u, 0u, 0u, 0u}, Ml = {0u, 0u, 0u, 0u};
-            { const SHiLo u = ssplit_pk(Mv[0], Mv[1]); Mh[0] = u.hi; Ml[0] = u.lo; }
-            { const SHiLo u = ssplit_pk(Mv[2], Mv[3]); Mh[1] = u.hi; Ml[1] = u.lo; }
+            u32x4 Mh = {0u, 0u, 0u, 0u}, Ml = {0u, 0u, 0u, 0u};
+            { const Bf16HiLo u = split_bf16_hilo(Mv[0], Mv[1]); Mh[0] = u.hi; Ml[0] = u.lo; }
+            { const Bf16HiLo u = split_bf16_hilo(Mv[2], Mv[3]); Mh[1] = u.hi; Ml[1] = u.lo; }
 #pragma unroll
             for (int jp = 0; jp < 8; jp += 2) {
-                su32x4 BT[2];                                     // lane (i, qq): B[s = 4 qq + g][n = 16 jn + i], exact
-                transpose_pair(su32x4{Br[jp].x, Br[jp].y, Br[jp + 1].x, Br[jp + 1].y}, selA, selB, BT[0], BT[1]);
+                u32x4 BT[2];                                     // lane (i, qq): B[s = 4 qq + g][n = 16 jn + i], exact
+                transpose_pair(u32x4{Br[jp].x, Br[jp].y, Br[jp + 1].x, Br[jp + 1].y}, selA, selB, BT[0], BT[1]);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const int jn = jp + e;
-                    sf32x4 Y = zero4;
+                    f32x4 Y = zero4;
 #pragma unroll
                     for (int kp = 0; kp < 2; ++kp) {
-                        su32x4 sh, sl;
-                        { const SHiLo u = ssplit_pk(T[2 * kp][jn][0], T[2 * kp][jn][1]); sh[0] = u.hi; sl[0] = u.lo; }
-                        { const SHiLo u = ssplit_pk(T[2 * kp][jn][2], T[2 * kp][jn][3]); sh[1] = u.hi; sl[1] = u.lo; }
-                        { const SHiLo u = ssplit_pk(T[2 * kp + 1][jn][0], T[2 * kp + 1][jn][1]); sh[2] = u.hi; sl[2] = u.lo; }
-                        { const SHiLo u = ssplit_pk(T[2 * kp + 1][jn][2], T[2 * kp + 1][jn][3]); sh[3] = u.hi; sl[3] = u.lo; }
-                        Y = smfma(gh[kp], sh, Y);
-                        Y = smfma(gh[kp], sl, Y);
-                        Y = smfma(gl[kp], sh, Y);
+                        u32x4 sh, sl;
+                        { const Bf16HiLo u = split_bf16_hilo(T[2 * kp][jn][0], T[2 * kp][jn][1]); sh[0] = u.hi; sl[0] = u.lo; }
+                        { const Bf16HiLo u = split_bf16_hilo(T[2 * kp][jn][2], T[2 * kp][jn][3]); sh[1] = u.hi; sl[1] = u.lo; }
+                        { const Bf16HiLo u = split_bf16_hilo(T[2 * kp + 1][jn][0], T[2 * kp + 1][jn][1]); sh[2] = u.hi; sl[2] = u.lo; }
+                        { const Bf16HiLo u = split_bf16_hilo(T[2 * kp + 1][jn][2], T[2 * kp + 1][jn][3]); sh[3] = u.hi; sl[3] = u.lo; }
+                        Y = mfma_bf16_packed(gh[kp], sh, Y);
+                        Y = mfma_bf16_packed(gh[kp], sl, Y);
+                        Y = mfma_bf16_packed(gl[kp], sh, Y);
                     }
 #pragma unroll
                     for (int g = 0; g < 4; ++g) Y[g] *= __expf(cs[g]);   // rows of the C/D layout are t = 4 q + g
-                    Y = smfma(Mh, BT[e], Y);
-                    Y = smfma(Ml, BT[e], Y);
+                    Y = mfma_bf16_packed(Mh, BT[e], Y);
+                    Y = mfma_bf16_packed(Ml, BT[e], Y);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) s_o[4 * q + g][16 * jn + t16] = Y[g];
                 }
@@ -205,18 +205,18 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_h_kernel(const SsdBwdPar
 #pragma unroll
         for (int pr = 0; pr < 8; pr += 2) {
             const SSplit4 k0 = scale_split(Br[pr], csc), k1 = scale_split(Br[pr + 1], csc);
-            const su32x4 kh = {k0.h0, k0.h1, k1.h0, k1.h1}, kl = {k0.l0, k0.l1, k1.l0, k1.l1};
-            su32x4 ah0, ah1, al0, al1;
+            const u32x4 kh = {k0.h0, k0.h1, k1.h0, k1.h1}, kl = {k0.l0, k0.l1, k1.l0, k1.l1};
+            u32x4 ah0, ah1, al0, al1;
             transpose_pair(kh, selA, selB, ah0, ah1);
             transpose_pair(kl, selA, selB, al0, al1);
 #pragma unroll
             for (int ip = 0; ip < 4; ++ip) {
                 T[ip][pr] *= e15;
                 T[ip][pr + 1] *= e15;
-                T[ip][pr] = smfma(xT[ip], ah0, T[ip][pr]);
-                T[ip][pr + 1] = smfma(xT[ip], ah1, T[ip][pr + 1]);
-                T[ip][pr] = smfma(xT[ip], al0, T[ip][pr]);
-                T[ip][pr + 1] = smfma(xT[ip], al1, T[ip][pr + 1]);
+                T[ip][pr] = mfma_bf16_packed(xT[ip], ah0, T[ip][pr]);
+                T[ip][pr + 1] = mfma_bf16_packed(xT[ip], ah1, T[ip][pr + 1]);
+                T[ip][pr] = mfma_bf16_packed(xT[ip], al0, T[ip][pr]);
+                T[ip][pr + 1] = mfma_bf16_packed(xT[ip], al1, T[ip][pr + 1]);
             }
         }
 
@@ -257,15 +257,15 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_h_kernel(const SsdBwdPar
 }
 
 // gy of this lane's step as a row operand over the head channels p, split (a padded step reads a valid row and gets zero)
-__device__ __forceinline__ void load_gy_split(const float *gyrow, int q, bool live, su32x4 (&gh)[2], su32x4 (&gl)[2]) {
+__device__ __forceinline__ void load_gy_split(const float *gyrow, int q, bool live, u32x4 (&gh)[2], u32x4 (&gl)[2]) {
 #pragma unroll
     for (int kp = 0; kp < 2; ++kp) {
         float4 a = *reinterpret_cast<const float4 *>(gyrow + 32 * kp + 4 * q);
         float4 c = *reinterpret_cast<const float4 *>(gyrow + 32 * kp + 16 + 4 * q);
         if (!live) { a = make_float4(0.f, 0.f, 0.f, 0.f); c = a; }
-        const SHiLo u0 = ssplit_pk(a.x, a.y), u1 = ssplit_pk(a.z, a.w), u2 = ssplit_pk(c.x, c.y), u3 = ssplit_pk(c.z, c.w);
-        gh[kp] = su32x4{u0.hi, u1.hi, u2.hi, u3.hi};
-        gl[kp] = su32x4{u0.lo, u1.lo, u2.lo, u3.lo};
+        const Bf16HiLo u0 = split_bf16_hilo(a.x, a.y), u1 = split_bf16_hilo(a.z, a.w), u2 = split_bf16_hilo(c.x, c.y), u3 = split_bf16_hilo(c.z, c.w);
+        gh[kp] = u32x4{u0.hi, u1.hi, u2.hi, u3.hi};
+        gl[kp] = u32x4{u0.lo, u1.lo, u2.lo, u3.lo};
     }
 }
 
@@ -284,12 +284,12 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
     __shared__ __attribute__((aligned(16))) bf16_t s_b[EMIT ? SBL : 1][SN + 8], s_c[EMIT ? SBL : 1][SN + 8];   // B, C rows [step][n]
     __shared__ __attribute__((aligned(16))) bf16_t s_x[EMIT ? SBL : 1][SP + 8];                                // x rows [step][p]
 
-    su32x4 selA, selB;
+    u32x4 selA, selB;
     sel_operands(t16, q, selA, selB);
-    const sf32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     const size_t seq = (size_t)b * p.H + h;
-    sf32x4 S[8][4];
+    f32x4 S[8][4];
     {
         const float *src = (EMIT && p.NC > 1) ? p.ws_g + (seq * p.NC + c) * (size_t)(SN * SP) : nullptr;
 #pragma unroll
@@ -354,24 +354,24 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
         auto rowX = [&](int ip) { return *reinterpret_cast<const uint2 *>(&s_x[EMIT ? t16 : 0][EMIT ? 16 * ip + 4 * q : 0]); };
         auto rowC = [&](int jm) { return EMIT ? *reinterpret_cast<const uint2 *>(&s_c[EMIT ? t16 : 0][EMIT ? 16 * jm + 4 * q : 0]) : Cr[jm]; };
 
-        sf32x4 U[EMIT ? 4 : 1];
+        f32x4 U[EMIT ? 4 : 1];
         if constexpr (EMIT) {
-            su32x4 Vh = {0u, 0u, 0u, 0u}, Vl = {0u, 0u, 0u, 0u};
+            u32x4 Vh = {0u, 0u, 0u, 0u}, Vl = {0u, 0u, 0u, 0u};
             {
-                su32x4 gh[2], gl[2];
+                u32x4 gh[2], gl[2];
                 load_gy_split(gyrow, q, live, gh, gl);
-                sf32x4 Vm = zero4;                                // (gy x^T)[s][t]
+                f32x4 Vm = zero4;                                // (gy x^T)[s][t]
 #pragma unroll
                 for (int kp = 0; kp < 2; ++kp) {
                     const uint2 x0 = rowX(2 * kp), x1 = rowX(2 * kp + 1);
-                    const su32x4 bq = {x0.x, x0.y, x1.x, x1.y};
-                    Vm = smfma(gh[kp], bq, Vm);
-                    Vm = smfma(gl[kp], bq, Vm);
+                    const u32x4 bq = {x0.x, x0.y, x1.x, x1.y};
+                    Vm = mfma_bf16_packed(gh[kp], bq, Vm);
+                    Vm = mfma_bf16_packed(gl[kp], bq, Vm);
                 }
                 float d[4];
                 decay_mask(d);
-                { const SHiLo u = ssplit_pk(Vm[0] * d[0], Vm[1] * d[1]); Vh[0] = u.hi; Vl[0] = u.lo; }
-                { const SHiLo u = ssplit_pk(Vm[2] * d[2], Vm[3] * d[3]); Vh[1] = u.hi; Vl[1] = u.lo; }
+                { const Bf16HiLo u = split_bf16_hilo(Vm[0] * d[0], Vm[1] * d[1]); Vh[0] = u.hi; Vl[0] = u.lo; }
+                { const Bf16HiLo u = split_bf16_hilo(Vm[2] * d[2], Vm[3] * d[3]); Vh[1] = u.hi; Vl[1] = u.lo; }
             }
             float er[4];
             row_decay(er);
@@ -382,50 +382,50 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
 #pragma unroll
             for (int jp = 0; jp < 8; jp += 2) {
                 const uint2 b0 = rowB(jp), b1 = rowB(jp + 1);
-                const su32x4 aB = {b0.x, b0.y, b1.x, b1.y};
-                sf32x4 Z[2] = {zero4, zero4};                     // gB tiles jn = jp, jp + 1
+                const u32x4 aB = {b0.x, b0.y, b1.x, b1.y};
+                f32x4 Z[2] = {zero4, zero4};                     // gB tiles jn = jp, jp + 1
 #pragma unroll
                 for (int kp = 0; kp < 2; ++kp) {
-                    SHiLo u[2][2][2];                             // [jn - jp][in - 2 kp][register pair]
+                    Bf16HiLo u[2][2][2];                             // [jn - jp][in - 2 kp][register pair]
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
                         for (int ii = 0; ii < 2; ++ii) {
-                            u[jj][ii][0] = ssplit_pk(S[jp + jj][2 * kp + ii][0], S[jp + jj][2 * kp + ii][1]);
-                            u[jj][ii][1] = ssplit_pk(S[jp + jj][2 * kp + ii][2], S[jp + jj][2 * kp + ii][3]);
+                            u[jj][ii][0] = split_bf16_hilo(S[jp + jj][2 * kp + ii][0], S[jp + jj][2 * kp + ii][1]);
+                            u[jj][ii][1] = split_bf16_hilo(S[jp + jj][2 * kp + ii][2], S[jp + jj][2 * kp + ii][3]);
                         }
 #pragma unroll
                     for (int ii = 0; ii < 2; ++ii) {              // B_t . X: K = n over the tiles jp, jp + 1
-                        const su32x4 sh = {u[0][ii][0].hi, u[0][ii][1].hi, u[1][ii][0].hi, u[1][ii][1].hi};
-                        const su32x4 sl = {u[0][ii][0].lo, u[0][ii][1].lo, u[1][ii][0].lo, u[1][ii][1].lo};
-                        U[2 * kp + ii] = smfma(aB, sh, U[2 * kp + ii]);
-                        U[2 * kp + ii] = smfma(aB, sl, U[2 * kp + ii]);
+                        const u32x4 sh = {u[0][ii][0].hi, u[0][ii][1].hi, u[1][ii][0].hi, u[1][ii][1].hi};
+                        const u32x4 sl = {u[0][ii][0].lo, u[0][ii][1].lo, u[1][ii][0].lo, u[1][ii][1].lo};
+                        U[2 * kp + ii] = mfma_bf16_packed(aB, sh, U[2 * kp + ii]);
+                        U[2 * kp + ii] = mfma_bf16_packed(aB, sl, U[2 * kp + ii]);
                     }
                     const uint2 x0 = rowX(2 * kp), x1 = rowX(2 * kp + 1);
-                    const su32x4 xa = {x0.x, x0.y, x1.x, x1.y};
+                    const u32x4 xa = {x0.x, x0.y, x1.x, x1.y};
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj) {              // X x_t: the tiles (jn, 2 kp), (jn, 2 kp + 1) transposed, K = p
-                        const su32x4 sh = {u[jj][0][0].hi, u[jj][0][1].hi, u[jj][1][0].hi, u[jj][1][1].hi};
-                        const su32x4 sl = {u[jj][0][0].lo, u[jj][0][1].lo, u[jj][1][0].lo, u[jj][1][1].lo};
-                        const sf32x4 h0 = smfma(sh, selA, zero4), h1 = smfma(sh, selB, zero4);
-                        const sf32x4 l0 = smfma(sl, selA, zero4), l1 = smfma(sl, selB, zero4);
-                        const su32x4 bh = {spack_exact(h0[0], h0[1]), spack_exact(h0[2], h0[3]), spack_exact(h1[0], h1[1]), spack_exact(h1[2], h1[3])};
-                        const su32x4 bl = {spack_exact(l0[0], l0[1]), spack_exact(l0[2], l0[3]), spack_exact(l1[0], l1[1]), spack_exact(l1[2], l1[3])};
-                        Z[jj] = smfma(xa, bh, Z[jj]);
-                        Z[jj] = smfma(xa, bl, Z[jj]);
+                        const u32x4 sh = {u[jj][0][0].hi, u[jj][0][1].hi, u[jj][1][0].hi, u[jj][1][1].hi};
+                        const u32x4 sl = {u[jj][0][0].lo, u[jj][0][1].lo, u[jj][1][0].lo, u[jj][1][1].lo};
+                        const f32x4 h0 = mfma_bf16_packed(sh, selA, zero4), h1 = mfma_bf16_packed(sh, selB, zero4);
+                        const f32x4 l0 = mfma_bf16_packed(sl, selA, zero4), l1 = mfma_bf16_packed(sl, selB, zero4);
+                        const u32x4 bh = {pack_bf16_exact(h0[0], h0[1]), pack_bf16_exact(h0[2], h0[3]), pack_bf16_exact(h1[0], h1[1]), pack_bf16_exact(h1[2], h1[3])};
+                        const u32x4 bl = {pack_bf16_exact(l0[0], l0[1]), pack_bf16_exact(l0[2], l0[3]), pack_bf16_exact(l1[0], l1[1]), pack_bf16_exact(l1[2], l1[3])};
+                        Z[jj] = mfma_bf16_packed(xa, bh, Z[jj]);
+                        Z[jj] = mfma_bf16_packed(xa, bl, Z[jj]);
                         __builtin_amdgcn_sched_barrier(0);        // (one tile group's operands at a time: the registers are full)
                     }
                 }
                 // gB_t = dt_t [ e^{cum_15 - cum_t} X x_t + sum_s V[s][t] C_s ]
                 const uint2 c0 = rowC(jp), c1 = rowC(jp + 1);
-                su32x4 CT[2];                                     // lane (i, qq): C[s = 4 qq + g][n = 16 jn + i], exact
-                transpose_pair(su32x4{c0.x, c0.y, c1.x, c1.y}, selA, selB, CT[0], CT[1]);
+                u32x4 CT[2];                                     // lane (i, qq): C[s = 4 qq + g][n = 16 jn + i], exact
+                transpose_pair(u32x4{c0.x, c0.y, c1.x, c1.y}, selA, selB, CT[0], CT[1]);
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g) Z[jj][g] *= er[g];
-                    Z[jj] = smfma(Vh, CT[jj], Z[jj]);
-                    Z[jj] = smfma(Vl, CT[jj], Z[jj]);
+                    Z[jj] = mfma_bf16_packed(Vh, CT[jj], Z[jj]);
+                    Z[jj] = mfma_bf16_packed(Vl, CT[jj], Z[jj]);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) s_o[4 * q + g][16 * (jp + jj) + t16] = Z[jj][g] * s_dt[4 * q + g];
                 }
@@ -435,9 +435,9 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
             lsum += c15;
         }
 
-        su32x4 gTh[4], gTl[4];                                    // lane (i, qq): gy[s = 4 qq + g][p = 16 in + i], split
+        u32x4 gTh[4], gTl[4];                                    // lane (i, qq): gy[s = 4 qq + g][p = 16 in + i], split
         {
-            su32x4 gh[2], gl[2];
+            u32x4 gh[2], gl[2];
             load_gy_split(gyrow, q, live, gh, gl);
             transpose_pair(gh[0], selA, selB, gTh[0], gTh[1]);
             transpose_pair(gh[1], selA, selB, gTh[2], gTh[3]);
@@ -446,25 +446,25 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
         }
         if constexpr (EMIT) {
             // gxu_t = e^{cum_15 - cum_t} B_t . X + sum_s W[s][t] gy_s,  W[s][t] = e^{cum_s - cum_t} (C_s . B_t), C B^T exact
-            sf32x4 Wm = zero4;
+            f32x4 Wm = zero4;
 #pragma unroll
             for (int pr = 0; pr < 8; pr += 2) {
                 const uint2 c0 = rowC(pr), c1 = rowC(pr + 1), b0 = rowB(pr), b1 = rowB(pr + 1);
-                Wm = smfma(su32x4{c0.x, c0.y, c1.x, c1.y}, su32x4{b0.x, b0.y, b1.x, b1.y}, Wm);
+                Wm = mfma_bf16_packed(u32x4{c0.x, c0.y, c1.x, c1.y}, u32x4{b0.x, b0.y, b1.x, b1.y}, Wm);
             }
-            su32x4 Wh = {0u, 0u, 0u, 0u}, Wl = {0u, 0u, 0u, 0u};
+            u32x4 Wh = {0u, 0u, 0u, 0u}, Wl = {0u, 0u, 0u, 0u};
             float d[4], er[4];
             decay_mask(d);
             row_decay(er);
-            { const SHiLo u = ssplit_pk(Wm[0] * d[0], Wm[1] * d[1]); Wh[0] = u.hi; Wl[0] = u.lo; }
-            { const SHiLo u = ssplit_pk(Wm[2] * d[2], Wm[3] * d[3]); Wh[1] = u.hi; Wl[1] = u.lo; }
+            { const Bf16HiLo u = split_bf16_hilo(Wm[0] * d[0], Wm[1] * d[1]); Wh[0] = u.hi; Wl[0] = u.lo; }
+            { const Bf16HiLo u = split_bf16_hilo(Wm[2] * d[2], Wm[3] * d[3]); Wh[1] = u.hi; Wl[1] = u.lo; }
 #pragma unroll
             for (int in = 0; in < 4; ++in) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) U[in][g] *= er[g];
-                U[in] = smfma(Wh, gTh[in], U[in]);
-                U[in] = smfma(Wh, gTl[in], U[in]);
-                U[in] = smfma(Wl, gTh[in], U[in]);
+                U[in] = mfma_bf16_packed(Wh, gTh[in], U[in]);
+                U[in] = mfma_bf16_packed(Wh, gTl[in], U[in]);
+                U[in] = mfma_bf16_packed(Wl, gTh[in], U[in]);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) s_u[4 * q + g][16 * in + t16] = U[in][g];
             }
@@ -475,20 +475,20 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
 #pragma unroll
         for (int pr = 0; pr < 8; pr += 2) {
             const SSplit4 k0 = scale_split(rowC(pr), csc), k1 = scale_split(rowC(pr + 1), csc);
-            const su32x4 kh = {k0.h0, k0.h1, k1.h0, k1.h1}, kl = {k0.l0, k0.l1, k1.l0, k1.l1};
-            su32x4 ah0, ah1, al0, al1;
+            const u32x4 kh = {k0.h0, k0.h1, k1.h0, k1.h1}, kl = {k0.l0, k0.l1, k1.l0, k1.l1};
+            u32x4 ah0, ah1, al0, al1;
             transpose_pair(kh, selA, selB, ah0, ah1);
             transpose_pair(kl, selA, selB, al0, al1);
 #pragma unroll
             for (int in = 0; in < 4; ++in) {
                 S[pr][in] *= e15;
                 S[pr + 1][in] *= e15;
-                S[pr][in] = smfma(ah0, gTh[in], S[pr][in]);
-                S[pr + 1][in] = smfma(ah1, gTh[in], S[pr + 1][in]);
-                S[pr][in] = smfma(ah0, gTl[in], S[pr][in]);
-                S[pr + 1][in] = smfma(ah1, gTl[in], S[pr + 1][in]);
-                S[pr][in] = smfma(al0, gTh[in], S[pr][in]);
-                S[pr + 1][in] = smfma(al1, gTh[in], S[pr + 1][in]);
+                S[pr][in] = mfma_bf16_packed(ah0, gTh[in], S[pr][in]);
+                S[pr + 1][in] = mfma_bf16_packed(ah1, gTh[in], S[pr + 1][in]);
+                S[pr][in] = mfma_bf16_packed(ah0, gTl[in], S[pr][in]);
+                S[pr + 1][in] = mfma_bf16_packed(ah1, gTl[in], S[pr + 1][in]);
+                S[pr][in] = mfma_bf16_packed(al0, gTh[in], S[pr][in]);
+                S[pr + 1][in] = mfma_bf16_packed(al1, gTh[in], S[pr + 1][in]);
             }
         }
 
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(64, 2) void mamba2_ssd_bwd_g_kernel(const SsdBwdPar
                     const float4 v = *reinterpret_cast<const float4 *>(&s_u[tt][col]);
                     const float d = s_dt[tt];
                     *reinterpret_cast<uint2 *>(p.g_xbc + ((size_t)b * p.L + trow) * p.ldg + h * SP + col) =
-                        make_uint2(scvt_pk(v.x * d, v.y * d), scvt_pk(v.z * d, v.w * d));
+                        make_uint2(pack_bf16_rne(v.x * d, v.y * d), pack_bf16_rne(v.z * d, v.w * d));
                 }
             }
 #pragma unroll
@@ -572,7 +572,7 @@ __global__ __launch_bounds__(256) void mamba2_ssd_bwd_reduce_kernel(const SsdBwd
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
     *reinterpret_cast<uint2 *>(p.g_xbc + r * p.ldg + p.d_inner + (k < 32 ? 0 : SN) + col) =
-        make_uint2(scvt_pk(acc.x, acc.y), scvt_pk(acc.z, acc.w));
+        make_uint2(pack_bf16_rne(acc.x, acc.y), pack_bf16_rne(acc.z, acc.w));
 }
 
 // g_la = suffix sum over the recurrence's steps of dla: one wave per (batch, head), 64 steps at a time from the last step

@@ -31,10 +31,6 @@
 namespace pafc {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWaves = 4;          // waves per gemm block: they split the k-chunks
 constexpr int kMaxSlots = 4096;    // B x beam
 constexpr int kMaxBeam = 16;
@@ -69,11 +65,9 @@ template <> struct Frag<bf16_t> {
         v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
     }
     static __device__ __forceinline__ f32x4 mma(const Frag &a, const Frag &b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a.v), __builtin_bit_cast(bf16x8, b.v), c, 0, 0, 0);
+        return mfma_bf16_packed(a.v, b.v, c);
     }
 };
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ long frame_of(int t, const int64_t *t_dev, int T) {
     long tt = t_dev ? (long)*t_dev : (long)t;

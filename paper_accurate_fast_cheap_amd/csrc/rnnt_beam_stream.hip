@@ -144,8 +144,6 @@ __global__ __launch_bounds__(64) void rnnt_beam_stream_drain_kernel(const RnntDr
 // utterance b; a thread owns one V-wide column of one layer of one tensor for ALL the utterance's slots: it loads the `beam`
 // source vectors into registers, then stores them.  Sources are slots of the same utterance, so nobody else writes what a
 // thread reads, and no barrier or LDS staging is needed.
-typedef unsigned int vec16 __attribute__((ext_vector_type(4)));     // 16- and 8-byte vectors the compiler keeps in registers
-typedef unsigned int vec8 __attribute__((ext_vector_type(2)));
 
 template <typename V>
 __global__ __launch_bounds__(256) void rnnt_beam_select_state_kernel(int L, int B, int beam, int rowv, V *h, V *c, const V *hn,
@@ -260,8 +258,8 @@ extern "C" int pafc_rnnt_beam_select_state(int dtype, int num_layers, int B, int
     // the widest vector that divides a row and every base address
     const uintptr_t bits = (uintptr_t)h | (uintptr_t)c | (uintptr_t)h_new | (uintptr_t)c_new | (uintptr_t)row_bytes;
     hipStream_t s = (hipStream_t)stream;
-    if (bits % 16 == 0) pafc::launch_select<pafc::vec16>(num_layers, B, beam, row_bytes, h, c, h_new, c_new, next_idx, s);
-    else if (bits % 8 == 0) pafc::launch_select<pafc::vec8>(num_layers, B, beam, row_bytes, h, c, h_new, c_new, next_idx, s);
+    if (bits % 16 == 0) pafc::launch_select<pafc::u32x4>(num_layers, B, beam, row_bytes, h, c, h_new, c_new, next_idx, s);
+    else if (bits % 8 == 0) pafc::launch_select<pafc::u32x2>(num_layers, B, beam, row_bytes, h, c, h_new, c_new, next_idx, s);
     else if (bits % 4 == 0) pafc::launch_select<uint32_t>(num_layers, B, beam, row_bytes, h, c, h_new, c_new, next_idx, s);
     else if (bits % 2 == 0) pafc::launch_select<uint16_t>(num_layers, B, beam, row_bytes, h, c, h_new, c_new, next_idx, s);
     else return PAFC_ERR_ALIGNMENT;

@@ -37,8 +37,7 @@ __device__ __forceinline__ void ld4(const float *p, float *f) {
 }
 __device__ __forceinline__ void ld4(const bf16_t *p, float *f) {
     const uint2 q = *reinterpret_cast<const uint2 *>(p);
-    f[0] = bf16_bits_to_f32(q.x & 0xffffu); f[1] = __uint_as_float(q.x & 0xffff0000u);
-    f[2] = bf16_bits_to_f32(q.y & 0xffffu); f[3] = __uint_as_float(q.y & 0xffff0000u);
+    Elem<bf16_t>::unpack4(q, f);
 }
 template <typename T> __device__ __forceinline__ float ld1(const T *p) { return Elem<T>::load(p); }
 
@@ -50,8 +49,6 @@ __device__ __forceinline__ float dot4(float w0, float w1, float w2, float w3, fl
     return fmaf(w3, x3, fmaf(w2, x2, fmaf(w1, x1, w0 * x0)));
 }
 __device__ __forceinline__ float dot4(const float *w, const float *x) { return dot4(w[0], w[1], w[2], w[3], x[0], x[1], x[2], x[3]); }
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 // device state, one layout for every kernel (B rows, L layers)
 struct GState {

@@ -37,8 +37,6 @@ namespace {
 
 constexpr int RBM = 128, RBN = 128, RBK = 64;
 constexpr float NEG = -1e30f;     // "log 0", finite as in ctc_loss.hip
-typedef float f32x4r __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8r __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ bool utt_ok(int Tn, int Un, int T, int Up1, int ldy) {
     return Tn >= 1 && Tn <= T && Un >= 0 && Un + 1 <= Up1 && Un <= ldy;
@@ -122,11 +120,6 @@ struct RnntGemm {
     const int32_t *rowlab;
 };
 
-__device__ __forceinline__ void rdma16(const bf16_t *src, bf16_t *lds_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_base, 16, 0, 0);
-}
-
 // label of lattice row r (global), or -1 when the row has none (u = U_n) or lies beyond the lattice
 __device__ __forceinline__ int row_label(const RnntGemm &p, long r, int *n_out) {
     *n_out = -1;
@@ -179,16 +172,16 @@ __global__ __launch_bounds__(256, 2) void rnnt_gemm_kernel(const RnntGemm p) {
         bf16_t *Wt = A + RBM * RBK;
         const int koff = it * RBK;
 #pragma unroll
-        for (int j = 0; j < MI; ++j) rdma16(a_src[j] + koff, A + (wave * (RBM / 4) + j * 8) * RBK);
+        for (int j = 0; j < MI; ++j) global_to_lds16(a_src[j] + koff, A + (wave * (RBM / 4) + j * 8) * RBK);
 #pragma unroll
-        for (int j = 0; j < NI; ++j) rdma16(w_src[j] + koff, Wt + (wave * (RBN / 4) + j * 8) * RBK);
+        for (int j = 0; j < NI; ++j) global_to_lds16(w_src[j] + koff, Wt + (wave * (RBN / 4) + j * 8) * RBK);
     };
 
-    f32x4r acc[MI][NI];
+    f32x4 acc[MI][NI];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < NI; ++j) acc[i][j] = f32x4r{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int fr = lane & 15, kq = lane >> 4;
     issue(0, 0);
     for (int it = 0; it < iters; ++it) {
@@ -199,16 +192,16 @@ __global__ __launch_bounds__(256, 2) void rnnt_gemm_kernel(const RnntGemm p) {
         const bf16_t *Wt = A + RBM * RBK;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            bf16x8r af[MI], wf[NI];
+            bf16x8 af[MI], wf[NI];
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int row = wm * (RBM / 2) + i * 16 + fr;
-                af[i] = *reinterpret_cast<const bf16x8r *>(A + row * RBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
+                af[i] = *reinterpret_cast<const bf16x8 *>(A + row * RBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
             }
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
                 const int row = wn * (RBN / 2) + j * 16 + fr;
-                wf[j] = *reinterpret_cast<const bf16x8r *>(Wt + row * RBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
+                wf[j] = *reinterpret_cast<const bf16x8 *>(Wt + row * RBK + (((ks * 4 + kq) ^ (row & 7)) * 8));
             }
 #pragma unroll
             for (int i = 0; i < MI; ++i)

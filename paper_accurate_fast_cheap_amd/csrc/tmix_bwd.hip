@@ -25,28 +25,6 @@ constexpr int TV = 8;            // channels per lane per iteration
 constexpr int TMAXIT = 2;        // C <= 1024
 constexpr int TROWS = 16;        // rows per block (4 per wave)
 
-template <typename ET> __device__ __forceinline__ void tl8(const ET *p, float *f);
-template <> __device__ __forceinline__ void tl8<bf16_t>(const bf16_t *p, float *f) {
-    Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(p), f);
-}
-template <> __device__ __forceinline__ void tl8<float>(const float *p, float *f) {
-    const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <typename ET> __device__ __forceinline__ void ts8(ET *p, const float *f);
-template <> __device__ __forceinline__ void ts8<bf16_t>(bf16_t *p, const float *f) {
-    uint4 q;
-    q.x = f32_to_bf16_bits(f[0]) | (f32_to_bf16_bits(f[1]) << 16);
-    q.y = f32_to_bf16_bits(f[2]) | (f32_to_bf16_bits(f[3]) << 16);
-    q.z = f32_to_bf16_bits(f[4]) | (f32_to_bf16_bits(f[5]) << 16);
-    q.w = f32_to_bf16_bits(f[6]) | (f32_to_bf16_bits(f[7]) << 16);
-    *reinterpret_cast<uint4 *>(p) = q;
-}
-template <> __device__ __forceinline__ void ts8<float>(float *p, const float *f) {
-    reinterpret_cast<float4 *>(p)[0] = make_float4(f[0], f[1], f[2], f[3]);
-    reinterpret_cast<float4 *>(p)[1] = make_float4(f[4], f[5], f[6], f[7]);
-}
-
 struct MixBwdArgs {
     const void *x, *m, *maa;          // x (rows, C); m (NQ, rows, C) or null; maa (NQ, C)
     const void *dz[4];                // NQ incoming gradients (rows, C)
@@ -82,8 +60,8 @@ __global__ __launch_bounds__(256) void tmix_mix_bwd_kernel(const MixBwdArgs a) {
             const int c = (it * 64 + lane) * TV;
             if (c < C) {
                 float xc[TV], xp[TV], xx[TV], sum_dz[TV], dxx[TV], dxx_n[TV];
-                tl8<ET>(x + row * C + c, xc);
-                tl8<ET>(x + (has_prev ? prow : row) * C + c, xp);
+                load8<ET>(x + row * C + c, xc);
+                load8<ET>(x + (has_prev ? prow : row) * C + c, xp);
 #pragma unroll
                 for (int e = 0; e < TV; ++e) {
                     xx[e] = (has_prev ? xp[e] : 0.f) - xc[e];
@@ -93,12 +71,12 @@ __global__ __launch_bounds__(256) void tmix_mix_bwd_kernel(const MixBwdArgs a) {
                 for (int q = 0; q < NQ; ++q) {
                     float g[TV], gn[TV], mq[TV], mn[TV], av[TV];
                     const ET *dzq = (const ET *)a.dz[q];
-                    tl8<ET>(dzq + row * C + c, g);
-                    tl8<ET>(dzq + (has_next ? nrow : row) * C + c, gn);
-                    tl8<ET>((const ET *)a.maa + (size_t)q * C + c, av);
+                    load8<ET>(dzq + row * C + c, g);
+                    load8<ET>(dzq + (has_next ? nrow : row) * C + c, gn);
+                    load8<ET>((const ET *)a.maa + (size_t)q * C + c, av);
                     if (NQ > 1) {
-                        tl8<ET>((const ET *)a.m + ((size_t)q * a.rows + row) * C + c, mq);
-                        tl8<ET>((const ET *)a.m + ((size_t)q * a.rows + (has_next ? nrow : row)) * C + c, mn);
+                        load8<ET>((const ET *)a.m + ((size_t)q * a.rows + row) * C + c, mq);
+                        load8<ET>((const ET *)a.m + ((size_t)q * a.rows + (has_next ? nrow : row)) * C + c, mn);
                     }
                     float dmq[TV];
 #pragma unroll
@@ -111,12 +89,12 @@ __global__ __launch_bounds__(256) void tmix_mix_bwd_kernel(const MixBwdArgs a) {
                         dxx[e] = fmaf(g[e], w, dxx[e]);
                         dxx_n[e] = fmaf(has_next ? gn[e] : 0.f, wn, dxx_n[e]);
                     }
-                    if (NQ > 1) ts8<ET>((ET *)a.dm + (size_t)q * a.dm_qs + (size_t)row * a.dm_rs + c, dmq);
+                    if (NQ > 1) store8<ET>((ET *)a.dm + (size_t)q * a.dm_qs + (size_t)row * a.dm_rs + c, dmq);
                 }
                 float o[TV];
 #pragma unroll
                 for (int e = 0; e < TV; ++e) o[e] = sum_dz[e] - dxx[e] + dxx_n[e];
-                ts8<ET>((ET *)a.dx + row * C + c, o);
+                store8<ET>((ET *)a.dx + row * C + c, o);
             }
         }
     }

@@ -45,28 +45,6 @@ __device__ __forceinline__ void keep8(unsigned long long seed, unsigned long lon
     for (int e = 0; e < 8; ++e) keep[e] = ((r[e >> 1] >> (16 * (e & 1))) & 0xffffu) >= thr16;
 }
 
-template <typename T> __device__ __forceinline__ void ld8(const T *p, float *f);
-template <> __device__ __forceinline__ void ld8<float>(const float *p, float *f) {
-    const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-template <> __device__ __forceinline__ void ld8<bf16_t>(const bf16_t *p, float *f) {
-    Elem<bf16_t>::unpack(*reinterpret_cast<const uint4 *>(p), f);
-}
-template <typename T> __device__ __forceinline__ void st8(T *p, const float *f);
-template <> __device__ __forceinline__ void st8<float>(float *p, const float *f) {
-    *reinterpret_cast<float4 *>(p) = make_float4(f[0], f[1], f[2], f[3]);
-    *reinterpret_cast<float4 *>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
-}
-template <> __device__ __forceinline__ void st8<bf16_t>(bf16_t *p, const float *f) {
-    uint4 w;
-    w.x = f32_to_bf16_bits(f[0]) | (f32_to_bf16_bits(f[1]) << 16);
-    w.y = f32_to_bf16_bits(f[2]) | (f32_to_bf16_bits(f[3]) << 16);
-    w.z = f32_to_bf16_bits(f[4]) | (f32_to_bf16_bits(f[5]) << 16);
-    w.w = f32_to_bf16_bits(f[6]) | (f32_to_bf16_bits(f[7]) << 16);
-    *reinterpret_cast<uint4 *>(p) = w;
-}
-
 // MODE 0: out = x + s * keep * y      (x: TX, y: TY, out: TX)
 // MODE 1: dy  = s * keep * dout       (dout: TX -> a, dy: TY -> out)
 template <typename TX, typename TY, int MODE>
@@ -78,16 +56,16 @@ __global__ __launch_bounds__(256) void residual_dropout_kernel(long n8, const TX
         float a[8], o[8];
         if constexpr (MODE == 0) {
             float b[8];
-            ld8<TX>(x + 8 * g, a);
-            ld8<TY>(y + 8 * g, b);
+            load8<TX>(x + 8 * g, a);
+            load8<TY>(y + 8 * g, b);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (!thr16 || keep[e]) ? fmaf(s, b[e], a[e]) : a[e];
-            st8<TX>((TX *)out + 8 * g, o);
+            store8<TX>((TX *)out + 8 * g, o);
         } else {
-            ld8<TX>(x + 8 * g, a);
+            load8<TX>(x + 8 * g, a);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (!thr16 || keep[e]) ? s * a[e] : 0.f;
-            st8<TY>((TY *)out + 8 * g, o);
+            store8<TY>((TY *)out + 8 * g, o);
         }
     }
 }
@@ -100,7 +78,7 @@ __global__ __launch_bounds__(256) void silu_dropout_kernel(long n8, const T *h, 
         bool keep[8];
         if (thr16) keep8(seed, offset, (unsigned long long)g, thr16, keep);
         float a[8], o[8];
-        ld8<T>(h + 8 * g, a);
+        load8<T>(h + 8 * g, a);
         if constexpr (MODE == 0) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -110,7 +88,7 @@ __global__ __launch_bounds__(256) void silu_dropout_kernel(long n8, const T *h, 
             }
         } else {
             float d[8];
-            ld8<T>(dout + 8 * g, d);
+            load8<T>(dout + 8 * g, d);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-a[e]));
@@ -118,7 +96,7 @@ __global__ __launch_bounds__(256) void silu_dropout_kernel(long n8, const T *h, 
                 o[e] = (!thr16 || keep[e]) ? s * d[e] * ds : 0.f;
             }
         }
-        st8<T>(out + 8 * g, o);
+        store8<T>(out + 8 * g, o);
     }
 }
 
