@@ -58,6 +58,9 @@ def lib():
 # checks the table against the headers).
 P, I, G, Z, F, U = c_void_p, c_int, c_long, c_size_t, c_float, c_ulonglong
 SIGNATURES = {
+    # include/pafc_attention.h
+    "pafc_mha_rows": (I, [I, I, I, I, P, G, P, P, G, P, P, P, I, P, G, P]),
+    "pafc_logp_gather_rows": (I, [I, G, I, P, G, P, P, P]),
     # include/pafc_encoder_ops.h
     "pafc_dwconv1d_cl": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P]),
     "pafc_dwconv1d_cl_ex": (I, [I, I, I, I, I, I, I, P, G, P, P, P, I, P, P]),

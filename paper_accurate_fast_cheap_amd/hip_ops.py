@@ -2257,6 +2257,16 @@ def split_weight_cached(weight: torch.Tensor) -> torch.Tensor:
     return ent[1]
 
 
+def split_gemm_takes(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
+    """The one rule for sending an fp32 projection x @ weight.T to the split-operand GEMM (gemm_ph_ex(a_split=True), ~2^-16 per
+    product) instead of exact fp32 products: inference, a long input (DISPATCH["split_gemm_min_rows"] rows) and dims the kernel
+    takes.  The caller adds its own conditions (its split_ok switch, the epilogue: no activation into an fp32 output)."""
+    N, K = weight.shape
+    return (x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_cuda and K % 128 == 0 and N % 8 == 0 and N >= 256
+            and x.numel() // K >= _SPLIT_GEMM_MIN_ROWS and not torch.is_grad_enabled()
+            and (bias is None or bias.dtype == torch.float32))
+
+
 def linear_fused(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: str = "none",
                  split_ok: bool = True) -> torch.Tensor:
     """act(x @ weight.T + bias) with the epilogue fused: bf16 operands on the hand-written GEMM (K % 64 == 0, N % 8 == 0),
@@ -2269,9 +2279,7 @@ def linear_fused(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
         return gemm_skinny(x.reshape(-1, K), weight, bias, act).view(x.shape[:-1] + (N,))
     if x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and K % 64 == 0 and N % 8 == 0:
         return gemm_bf16(x.reshape(-1, K), weight, bias, act).view(x.shape[:-1] + (N,))
-    if (x.dtype == torch.float32 and weight.dtype == torch.float32 and x.is_cuda and K % 128 == 0 and N % 8 == 0 and N >= 256
-            and rows >= _SPLIT_GEMM_MIN_ROWS and split_ok and act == "none" and not torch.is_grad_enabled()
-            and (bias is None or bias.dtype == torch.float32)):
+    if split_ok and act == "none" and split_gemm_takes(x, weight, bias):
         planes = split_planes(x.reshape(rows, K) if x.is_contiguous() else x.reshape(rows, K).contiguous())
         return gemm_ph_ex(planes, split_weight_cached(weight), bias, a_split=True, out_kind="f32").view(x.shape[:-1] + (N,))
     return linear_bias_act(x, weight, bias, act)
@@ -3443,3 +3451,56 @@ def rows_gather(entries, idx: torch.Tensor, m: int, rings=(), offs: Optional[tor
 def rows_scatter(entries, idx: torch.Tensor, m: int) -> None:
     """One-off RowsTable(entries).scatter(idx, m)."""
     RowsTable(entries).scatter(idx, m)
+
+
+def mha_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_off: torch.Tensor, kv_off: torch.Tensor, kv_len: torch.Tensor,
+             heads: int, causal: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Multi-head attention over packed row groups (include/pafc_attention.h: pafc_mha_rows), one launch for every group and
+    head.  q (rows, >= H * 64), k / v (kv rows, >= H * 64): 2-D fp32 or bf16, unit stride in the last dimension (column slices
+    of a stacked projection are fine; k and v share a row pitch); q_off (G + 1), kv_off / kv_len (G) int32 on the device.
+    Group g: query rows [q_off[g], q_off[g + 1]) over the keys / values [kv_off[g], kv_off[g] + kv_len[g]); causal: query i of
+    its group sees the keys [0, i].  Returns out (rows, H * 64)."""
+    d = heads * 64
+    for t in (q, k, v):
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype or t.shape[1] < d:
+            raise _lib.PafcError("mha_rows: q, k, v are 2-D GPU tensors of one dtype, unit stride along the heads")
+    if k.stride(0) != v.stride(0):
+        raise _lib.PafcError("mha_rows: k and v must share their row pitch")
+    for t in (q_off, kv_off, kv_len):
+        if not t.is_cuda or t.dtype != torch.int32 or t.stride(-1) != 1:
+            raise _lib.PafcError("mha_rows: q_off, kv_off, kv_len are int32 GPU tensors")
+    G = kv_len.numel()
+    if q_off.numel() != G + 1 or kv_off.numel() != G:
+        raise _lib.PafcError("mha_rows: q_off (G + 1), kv_off (G), kv_len (G)")
+    if out is None:
+        out = torch.empty(q.shape[0], d, dtype=q.dtype, device=q.device)
+    elif not out.is_cuda or out.dtype != q.dtype or out.dim() != 2 or out.stride(1) != 1 or out.shape != (q.shape[0], d):
+        raise _lib.PafcError("mha_rows: out is (rows, H * 64) in the operands' dtype")
+    if G == 0 or q.shape[0] == 0:
+        return out
+    rc = _lib.lib().pafc_mha_rows(_lib.dtype_code(q.dtype), G, heads, 64, _lib.ptr(q), q.stride(0), _lib.ptr(k), _lib.ptr(v),
+                                  k.stride(0), _lib.ptr(q_off), _lib.ptr(kv_off), _lib.ptr(kv_len), int(bool(causal)),
+                                  _lib.ptr(out), out.stride(0), _lib.stream_of(q))
+    _lib.check(rc, "pafc_mha_rows")
+    return out
+
+
+def logp_gather_rows(logits: torch.Tensor, target: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r] = logits[r, target[r]] - logsumexp(logits[r]) (include/pafc_attention.h: pafc_logp_gather_rows): the logits are
+    read once, the (rows, V) log-softmax is never formed.  logits (rows, V) fp32 / bf16 with unit stride along V, target (rows)
+    int32 on the device; out (rows) float32."""
+    if not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.PafcError("logp_gather_rows: logits are a 2-D GPU tensor with unit stride along the vocabulary")
+    rows, V = logits.shape
+    if not target.is_cuda or target.dtype != torch.int32 or target.numel() != rows or target.stride(-1) != 1:
+        raise _lib.PafcError("logp_gather_rows: target is (rows) int32 on the GPU")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.numel() != rows or out.stride(-1) != 1:
+        raise _lib.PafcError("logp_gather_rows: out is (rows) float32 on the GPU")
+    if rows == 0:
+        return out
+    rc = _lib.lib().pafc_logp_gather_rows(_lib.dtype_code(logits.dtype), rows, V, _lib.ptr(logits), logits.stride(0),
+                                          _lib.ptr(target), _lib.ptr(out), _lib.stream_of(logits))
+    _lib.check(rc, "pafc_logp_gather_rows")
+    return out

@@ -2,14 +2,17 @@
 RNN predictor + joint, `decode(methods=[...,'rnnt_beam_search', 'rnnt_greedy_search'])` (:695-813), `beam_search_decode`
 (:644-693), `greedy_search` (:427-472), the runtime step API (:474-505) and `stream_greedy_search` /
 `stream_beam_search`: the streaming encoder and the greedy / CTC-fused prefix beam search chunk by chunk with carried
-decoder state.  Two-pass decoding (transducer_attention_rescoring, :288-425, without the attention term): `score_hypotheses`
-is the full-sum transducer score log p(y | x) of n-best lists (`_cal_transducer_score`, :185-210), and the decode modes
-"ctc_beam_td_rescoring" / "rnnt_beam_td_rescoring" re-rank a first pass with it (search/rescoring.py).
+decoder state.  Two-pass decoding (transducer_attention_rescoring, :288-425): `score_hypotheses` is the full-sum transducer
+score log p(y | x) of n-best lists (`_cal_transducer_score`, :185-210), and the decode modes "ctc_beam_td_rescoring" /
+"rnnt_beam_td_rescoring" re-rank a first pass with it (search/rescoring.py); with an attention decoder attached
+(`attention_decoder=`, held as `self.decoder`) "attention_rescoring", "ctc_beam_td_attn_rescoring" and
+"rnnt_beam_attn_rescoring" add the attention term of ASRModel.score_attention (transformer/attn_rescore.py).
 
 Training objective (forward, :105-175): transducer_weight * RNN-T loss + ctc_weight * CTC loss over the accelerated
 encoder.  The reference's RNN-T loss is the third-party `optimized_transducer.transducer_loss` (transducer.py:506-523;
 Rev fork, unpinned): restated from the published definition in `loss.py` -- PARITY UNPINNED.  Its attention decoder was
-not released (decoder.py is swallowed by .gitignore:44), so the attention branch does not exist here."""
+not released (decoder.py is swallowed by .gitignore:44): the decoder here is the published WeNet one (transformer/decoder.py),
+used by the second pass only -- the training objective has no attention branch."""
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -19,6 +22,7 @@ from ..transformer.search import DecodeResult
 from .loss import transducer_loss
 from .search.greedy_search import GreedyStreamer, batch_greedy_search
 from .search.prefix_beam_search import BeamStreamer, PrefixBeamSearch
+from ..transformer.attn_rescore import ATTN_RESCORING_MODES, attention_rescore
 from .search.rescoring import RESCORING_MODES, build_arc_tables, check_hypotheses, check_score_backend, rescore
 
 IGNORE_ID = -1
@@ -38,7 +42,7 @@ class Transducer(ASRModel):
                  joint: torch.nn.Module, ctc=None, special_tokens: Optional[dict] = None, attention_decoder=None,
                  ctc_weight: float = 0.0, transducer_weight: float = 1.0, attention_weight: float = 0.0,
                  transducer_type: Optional[str] = None, **_unused_model_conf):
-        super().__init__(vocab_size, encoder, ctc, ctc_weight, special_tokens)
+        super().__init__(vocab_size, encoder, ctc, ctc_weight, special_tokens, decoder=attention_decoder)
         # model_conf.transducer_type (the reference's key, default "optimized_transducer"): every value but "fused_joint" keeps the
         # restated path below; "fused_joint" asks for the fused joint + loss kernels (hip_ops.rnnt_joint_loss) and never falls back
         self.fused_joint = transducer_type == FUSED_JOINT
@@ -288,25 +292,38 @@ class Transducer(ASRModel):
                ) -> Dict[str, List[DecodeResult]]:
         """frame_body: for rnnt_beam_search and rnnt_beam_td_rescoring, the per-frame body of beam_search_decode ("framework" /
         "kernels").
-        Two-pass modes (the reference's rnnt_beam_attn_rescoring / ctc_beam_td_attn_rescoring minus `attn`: the attention
-        decoder was not released, so a non-zero reverse_weight or attn_weight with them is a ValueError):
+        Two-pass modes with the attention term (a model with an attention decoder; NotImplementedError without one):
+          "attention_rescoring": first pass ctc_prefix_beam_search, final_i = attn_i + ctc_weight * first_pass_score_i;
+          "ctc_beam_td_attn_rescoring" / "rnnt_beam_attn_rescoring": the first passes of the two modes below,
+            final_i = attn_weight * attn_i + ctc_weight * first_pass_score_i + transducer_weight * td_i (transducer.py:401-420);
+          attn_i = score_attention's l2r_i, or (1 - reverse_weight) * l2r_i + reverse_weight * r2l_i; results as
+          attn_rescore.attention_rescore builds them (nbest_attn_scores, confidence, tokens_confidence).
+        Two-pass modes without it (a non-zero reverse_weight or attn_weight with them is a ValueError):
           "ctc_beam_td_rescoring": first pass ctc_prefix_beam_search (computed once when that mode is requested too);
           "rnnt_beam_td_rescoring": first pass beam_search_decode with search_ctc_weight / search_transducer_weight -- the
             reference's names, but beam_search_decode's defaults 0.3 / 0.7: the reference's 1.0 / 0.0 switch the transducer off.
         Second pass: final_i = ctc_weight * first_pass_score_i + transducer_weight * td_i, td_i = score_hypotheses (backend:
         score_backend), ties to the earlier first-pass rank; nbest / nbest_scores / nbest_times re-ordered by final,
         nbest_td_scores the raw td_i (search/rescoring.py: rescore)."""
-        two_pass = [m for m in methods if m in RESCORING_MODES]
-        if two_pass and (reverse_weight != 0.0 or attn_weight != 0.0):
-            raise ValueError(f"decode mode {two_pass[0]!r} with reverse_weight = {reverse_weight} / attn_weight = {attn_weight}: "
-                             "the attention decoder was not released, there is no attention term to weigh")
-        rest = [m for m in methods if m not in ("rnnt_beam_search", "rnnt_greedy_search") + RESCORING_MODES]
+        td_only = [m for m in methods if m in RESCORING_MODES]
+        if td_only and (reverse_weight != 0.0 or attn_weight != 0.0):
+            raise ValueError(f"decode mode {td_only[0]!r} with reverse_weight = {reverse_weight} / attn_weight = {attn_weight}: "
+                             "the attention decoder was not released with the reference, so this mode has no attention term to "
+                             "weigh; ctc_beam_td_attn_rescoring / rnnt_beam_attn_rescoring of a model built with an attention "
+                             "decoder have one")
+        with_attn = [m for m in methods if m in ATTN_RESCORING_MODES]
+        if with_attn and self.decoder is None:
+            raise NotImplementedError(f"decode mode {with_attn[0]!r} needs an attention decoder (init_model builds one with "
+                                      "args.attention_decoder)")
+        two_pass = [m for m in methods if m in RESCORING_MODES + ATTN_RESCORING_MODES]
+        rest = [m for m in methods if m not in ("rnnt_beam_search", "rnnt_greedy_search") + RESCORING_MODES + ATTN_RESCORING_MODES]
         encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
                                                           num_decoding_left_chunks, simulate_streaming, cat_embs)
         encoder_lens = encoder_mask.squeeze(1).sum(1)
         ctc_probs = self.ctc_logprobs(encoder_out, blank_penalty, blank_id)
         results = {}
-        if "ctc_beam_td_rescoring" in two_pass and "ctc_prefix_beam_search" not in rest:
+        ctc_first = ("ctc_beam_td_rescoring", "attention_rescoring", "ctc_beam_td_attn_rescoring")
+        if any(m in ctc_first for m in two_pass) and "ctc_prefix_beam_search" not in rest:
             rest = rest + ["ctc_prefix_beam_search"]          # the first pass, not reported under its own name
         for m in rest:
             if m == "ctc_greedy_search":
@@ -325,17 +342,27 @@ class Transducer(ASRModel):
             results["rnnt_greedy_search"] = batch_greedy_search(self, encoder_out, encoder_lens)
         if two_pass:
             lens_host = encoder_lens.tolist()
+            firsts, tds, attns = {}, {}, {}                   # per first pass: computed once, shared by the modes that rest on it
             for m in two_pass:
-                if m == "ctc_beam_td_rescoring":
-                    first = results["ctc_prefix_beam_search"]
-                else:
-                    first = self.beam_search_decode(
+                kind = "ctc" if m in ctc_first else "rnnt"
+                if kind not in firsts:
+                    firsts[kind] = results["ctc_prefix_beam_search"] if kind == "ctc" else self.beam_search_decode(
                         encoder_outs=encoder_out, encoder_lens=encoder_lens, ctc_probs=ctc_probs, beam_size=beam_size,
                         ctc_weight=search_ctc_weight, transducer_weight=search_transducer_weight, cat_embs=cat_embs,
                         frame_body=frame_body)
+                first = firsts[kind]
                 hyps = [r.nbest if r.nbest is not None else [r.tokens] for r in first]
-                td = self.score_hypotheses(encoder_out, lens_host, hyps, backend=score_backend)
-                results[m] = rescore(first, td, ctc_weight, transducer_weight)
+                if m != "attention_rescoring" and kind not in tds:
+                    tds[kind] = self.score_hypotheses(encoder_out, lens_host, hyps, backend=score_backend)
+                if m in ATTN_RESCORING_MODES and kind not in attns:
+                    attns[kind] = self.score_attention(encoder_out, lens_host, hyps, reverse_weight, score_backend)
+                if m in RESCORING_MODES:
+                    results[m] = rescore(first, tds[kind], ctc_weight, transducer_weight)
+                elif m == "attention_rescoring":
+                    results[m] = attention_rescore(first, attns[kind], reverse_weight, ctc_weight)
+                else:
+                    results[m] = attention_rescore(first, attns[kind], reverse_weight, ctc_weight, attn_weight, tds[kind],
+                                                   transducer_weight)
             if "ctc_prefix_beam_search" not in methods:
                 results.pop("ctc_prefix_beam_search", None)
         return results

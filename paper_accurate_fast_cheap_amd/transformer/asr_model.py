@@ -1,7 +1,9 @@
 """Encoder + CTC container exposing what the hot path's callers use on the reference's ASRModel / Transducer:
 `.encoder`, `.ctc`, `_forward_encoder` (asr_model.py:294-321), `ctc_logprobs` (:324-335) and `decode` for the
-CTC modes (:337-440).  The attention decoder, RNN-T predictor/joint and their losses are containers around the
-path, not the path; transducer decoding joins in paper_accurate_fast_cheap_amd/transducer."""
+CTC modes (:337-440).  The RNN-T predictor/joint and the losses are containers around the path, not the path; transducer
+decoding joins in paper_accurate_fast_cheap_amd/transducer.  An attention decoder (`decoder=`,
+transformer/decoder.py) serves the second pass: `score_attention` and the "attention_rescoring" mode
+(transformer/attn_rescore.py)."""
 from typing import Callable, Dict, Iterator, List, Optional, Tuple
 
 import torch
@@ -13,11 +15,12 @@ from .search import DecodeResult, ctc_greedy_search
 
 class ASRModel(torch.nn.Module):
     def __init__(self, vocab_size: int, encoder: torch.nn.Module, ctc: CTC, ctc_weight: float = 1.0,
-                 special_tokens: Optional[dict] = None, **_unused_model_conf):
+                 special_tokens: Optional[dict] = None, decoder: Optional[torch.nn.Module] = None, **_unused_model_conf):
         super().__init__()
         self.vocab_size = vocab_size
         self.encoder = encoder
         self.ctc = ctc
+        self.decoder = decoder          # the attention decoder of the second pass (transformer/decoder.py), or None
         self.ctc_weight = ctc_weight
         self.special_tokens = special_tokens
         self.sos = (vocab_size - 1) if special_tokens is None else special_tokens.get("<sos>", vocab_size - 1)
@@ -50,19 +53,57 @@ class ASRModel(torch.nn.Module):
             return logits.log_softmax(dim=2)
         return self.ctc.log_softmax(encoder_out)
 
+    def is_bidirectional_decoder(self) -> bool:
+        return self.decoder is not None and hasattr(self.decoder, "right_decoder")
+
+    def score_attention(self, encoder_out: torch.Tensor, encoder_lens, hyps: List[List[List[int]]],
+                        reverse_weight: float = 0.0, backend: Optional[str] = None):
+        """The attention decoder's scores of n-best lists: hyps[b] is a list of token lists for utterance b of encoder_out
+        (B, T', D); encoder_lens a (B) tensor or list (lengths on the host spare one read of the device).  Returns an
+        attn_rescore.AttentionScores: per utterance and hypothesis l2r = sum_j log p(y_j | y_<j, x) + log p(eos | y, x) and its
+        L + 1 terms l2r_logp; with reverse_weight > 0 also r2l / r2l_logp of the right decoder over the reversed hypothesis.
+        The empty hypothesis is legal and scores log p(eos | sos).
+        backend "framework": the reference's recipe as framework ops (memory repeated per hypothesis, padding, masks, full
+          log-softmax, gather), on the CPU and the GPU.
+        backend "kernels": packed rows on the library's GEMMs and the kernels of include/pafc_attention.h, GPU only, never a
+          fallback: PafcError naming what is unmet.
+        None: kernels on the GPU, framework on the CPU.
+        NotImplementedError without a decoder; ValueError for reverse_weight > 0 without a right_decoder or a token outside the
+        vocabulary.  The result's `stats` holds what the kernels backend counted (rows, chunks, logits_peak_bytes)."""
+        from .attn_rescore import score_attention
+        return score_attention(self, encoder_out, encoder_lens, hyps, reverse_weight, backend)
+
+    def _attention_rescoring(self, first: List[DecodeResult], encoder_out, encoder_lens, ctc_weight: float, reverse_weight: float,
+                             score_backend: Optional[str]) -> List[DecodeResult]:
+        """search.py:364-448 over a CTC prefix beam search: final_i = attn_i + ctc_weight * ctc_score_i."""
+        from .attn_rescore import attention_rescore
+        hyps = [r.nbest if r.nbest is not None else [r.tokens] for r in first]
+        scores = self.score_attention(encoder_out, encoder_lens.tolist(), hyps, reverse_weight, score_backend)
+        return attention_rescore(first, scores, reverse_weight, ctc_weight)
+
     @torch.no_grad()
     def decode(self, methods: List[str], speech: torch.Tensor, speech_lengths: torch.Tensor, beam_size: int = 10,
                decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0,
                simulate_streaming: bool = False, reverse_weight: float = 0.0, blank_id: int = 0,
-               blank_penalty: float = 0.0, cat_embs: Optional[torch.Tensor] = None, context_graph=None, **_ignored
-               ) -> Dict[str, List[DecodeResult]]:
+               blank_penalty: float = 0.0, cat_embs: Optional[torch.Tensor] = None, context_graph=None,
+               score_backend: Optional[str] = None, **_ignored) -> Dict[str, List[DecodeResult]]:
+        """"attention_rescoring" (a model with an attention decoder): first pass ctc_prefix_beam_search (computed once when that
+        mode is requested too), final_i = attn_i + ctc_weight * ctc_score_i with attn_i of score_attention (backend:
+        score_backend) and reverse_weight; the n-best lists come back re-ordered by final (attn_rescore.attention_rescore)."""
         assert speech.shape[0] == speech_lengths.shape[0]
+        rescoring = "attention_rescoring" in methods
+        if rescoring and self.decoder is None:
+            raise NotImplementedError("decode mode 'attention_rescoring' needs an attention decoder (init_model builds one "
+                                      "with args.attention_decoder)")
         encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
                                                           num_decoding_left_chunks, simulate_streaming, cat_embs)
         encoder_lens = encoder_mask.squeeze(1).sum(1)
         ctc_probs = self.ctc_logprobs(encoder_out, blank_penalty, blank_id)
         results = {}
-        for m in methods:
+        todo = [m for m in methods if m != "attention_rescoring"]
+        if rescoring and "ctc_prefix_beam_search" not in todo:
+            todo.append("ctc_prefix_beam_search")                 # the first pass, not reported under its own name
+        for m in todo:
             if m == "ctc_greedy_search":
                 results[m] = ctc_greedy_search(ctc_probs, encoder_lens, blank_id)
             elif m == "ctc_prefix_beam_search":
@@ -70,6 +111,11 @@ class ASRModel(torch.nn.Module):
                 results[m] = ctc_prefix_beam_search(ctc_probs, encoder_lens, beam_size, context_graph, blank_id)
             else:
                 raise NotImplementedError(f"decode mode {m!r} is outside the accelerated path")
+        if rescoring:
+            results["attention_rescoring"] = self._attention_rescoring(results["ctc_prefix_beam_search"], encoder_out,
+                                                                       encoder_lens, ctc_weight, reverse_weight, score_backend)
+            if "ctc_prefix_beam_search" not in methods:
+                del results["ctc_prefix_beam_search"]
         return results
 
     @torch.no_grad()

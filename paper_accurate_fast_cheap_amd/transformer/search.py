@@ -13,7 +13,7 @@ class DecodeResult:
     def __init__(self, tokens: List[int], score: float = 0.0, confidence: float = 0.0, tokens_confidence=None,
                  times=None, nbest: Optional[List[List[int]]] = None, nbest_scores: Optional[List[float]] = None,
                  nbest_times=None, end_times=None, tokens_info=None, ok: bool = True,
-                 nbest_td_scores: Optional[List[float]] = None):
+                 nbest_td_scores: Optional[List[float]] = None, nbest_attn_scores: Optional[List[float]] = None):
         self.tokens = tokens
         self.score = score
         self.confidence = confidence
@@ -26,6 +26,7 @@ class DecodeResult:
         self.tokens_info = tokens_info      # forced alignment: (start, end) seconds per token
         self.ok = ok                        # forced alignment: False when the labels cannot be aligned to the frames
         self.nbest_td_scores = nbest_td_scores    # transducer rescoring: log p(y | x) of every entry of nbest, in its order
+        self.nbest_attn_scores = nbest_attn_scores    # attention rescoring: the attention decoder's score of every entry of nbest
 
 
 def log_add(args: List[float]) -> float:

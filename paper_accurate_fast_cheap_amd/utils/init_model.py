@@ -4,8 +4,10 @@
 Reads the same config keys (cmvn, cmvn_conf, input_dim, output_dim, encoder, encoder_conf, ctc, ctc_conf,
 model, model_conf, tokenizer_conf, dataset_conf), honours args.checkpoint, and sets configs['init_infos'],
 ['num_seen_frames'], ['step'] and the model attributes lsl_enc / lsl_dec / add_cat_embs / cat_labels exactly like
-the reference (:242-268).  It builds encoder + CTC (+ RNN predictor and joint for `model: transducer`); the `decoder` section of a reference
-YAML is accepted and skipped (a checkpoint's extra keys are ignored the way the reference's def_strict=False does, :243).
+the reference (:242-268).  It builds encoder + CTC (+ RNN predictor and joint for `model: transducer`).  The `decoder` section of a reference
+YAML (`transformer` / `bitransformer` + decoder_conf) becomes the frozen attention decoder of the second pass when
+args.attention_decoder is true; otherwise it is accepted and skipped (a checkpoint's extra keys are ignored the way the
+reference's def_strict=False does, :243).
 """
 import logging
 
@@ -46,6 +48,20 @@ def init_model(args, configs):
     ctc.fp32_split_operands = bool(getattr(encoder, "fp32_split_operands", True))   # a pure-fp32 model keeps exact fp32 products
     model_conf = dict(configs.get("model_conf", {}))
     special = configs.get("tokenizer_conf", {}).get("special_tokens", None)
+    # The attention decoder of the second pass (init_model.py:150-160 of the reference) is built only on request
+    # (args.attention_decoder) and frozen: the training objective has no attention term, and an unused trainable decoder breaks
+    # DDP's unused-parameter check.  Without the switch a YAML's `decoder` section is accepted and skipped, as before.
+    decoder = None
+    if getattr(args, "attention_decoder", False):
+        from ..transformer.decoder import DECODER_CLASSES
+        decoder_type = configs.get("decoder", "bitransformer")
+        if decoder_type not in DECODER_CLASSES:
+            raise NotImplementedError(f"decoder {decoder_type!r}: only {sorted(DECODER_CLASSES)} are implemented")
+        decoder = DECODER_CLASSES[decoder_type](vocab_size, encoder.output_size(), **configs.get("decoder_conf", {}))
+        decoder.fp32_split_operands = bool(getattr(encoder, "fp32_split_operands", True))
+        decoder.requires_grad_(False)
+    model_conf.pop("decoder", None)
+    model_conf.pop("attention_decoder", None)
     if configs.get("model", "asr_model") == "transducer" and "predictor_conf" in configs and "joint_conf" in configs:
         # init_model.py:192-209: RNN predictor + joint around the same encoder / CTC (config c5)
         from ..transducer.joint import TransducerJoint
@@ -56,9 +72,9 @@ def init_model(args, configs):
         predictor = RNNPredictor(vocab_size, **configs["predictor_conf"])
         joint = TransducerJoint(vocab_size, **configs["joint_conf"])
         model = Transducer(vocab_size=vocab_size, blank=0, encoder=encoder, predictor=predictor, joint=joint, ctc=ctc,
-                           special_tokens=special, **model_conf)
+                           special_tokens=special, attention_decoder=decoder, **model_conf)
     else:
-        model = ASRModel(vocab_size=vocab_size, encoder=encoder, ctc=ctc, special_tokens=special, **model_conf)
+        model = ASRModel(vocab_size=vocab_size, encoder=encoder, ctc=ctc, special_tokens=special, decoder=decoder, **model_conf)
 
     if getattr(args, "checkpoint", None) is not None:
         infos = load_checkpoint(model, args.checkpoint, def_strict=False)
