@@ -1,6 +1,7 @@
 /*
- * pafc_attention.h -- C ABI of the attention decoder's second pass (attention rescoring: wenet/transformer/search.py:364-448,
- * asr_model.py:876-986 of the reference).
+ * pafc_attention.h -- C ABI of the attention decoder over packed rows: its second pass (attention rescoring:
+ * wenet/transformer/search.py:364-448, asr_model.py:876-986 of the reference) and, further down, the training half (the
+ * attention loss, asr_model.py:251-292: attention with statistics, its backward, the label-smoothing loss from the logits).
  *
  * The reference repeats the encoder output once per hypothesis, pads every hypothesis to the longest and forms the
  * (beam, L, V) log-softmax to read L + 1 numbers of each.  Here all hypotheses of all utterances are packed as rows without
@@ -41,6 +42,59 @@ int pafc_mha_rows(int dtype, int G, int H, int dk, const void *q, long ldq, cons
  * a row gives NaN for that row, as log_softmax does; -inf logits are ordinary (a row of nothing but -inf gives NaN). */
 int pafc_logp_gather_rows(int dtype, long rows, int V, const void *logits, long ldl, const int32_t *target, float *out,
                           pafc_stream_t stream);
+
+/* ---- the training half: the attention decoder's loss on packed rows (one group per utterance, [sos] + y) ---- */
+
+/* pafc_mha_rows that also writes lse[r, h] = m + log(l), the log of the softmax's denominator of query row r and head h, as
+ * float32 (rows, H) (row pitch H): what the backward needs to form P again.  out holds the bits pafc_mha_rows writes.  Rows of a
+ * group with kv_len[g] = 0 get lse = -inf; rows outside every group are not written. */
+int pafc_mha_rows_lse(int dtype, int G, int H, int dk, const void *q, long ldq, const void *k, const void *v, long ldkv,
+                      const int32_t *q_off, const int32_t *kv_off, const int32_t *kv_len, int causal, void *out, long ldo,
+                      float *lse, pafc_stream_t stream);
+
+/* Bytes of pafc_mha_rows_bwd's workspace (delta, one float32 per query row and head): rows * H * 4; 0 for bad arguments. */
+size_t pafc_mha_rows_bwd_workspace_bytes(long rows, int H);
+
+/* The backward of pafc_mha_rows: from q, k, v, the forward's out and lse and the upstream gradient dout, with
+ *   P = exp(S / sqrt(dk) - lse), delta_i = sum_d dout_id out_id, dS = P o (dout V^T - delta)
+ * per group and head,
+ *   dq = dS K / sqrt(dk),  dk = dS^T Q / sqrt(dk),  dv = P^T dout.
+ * dtype as in the forward: PAFC_F32 takes every product exactly on the fp32 matrix cores, PAFC_BF16 runs on the bf16 matrix
+ *   cores with fp32 accumulation, P and dS rounded to bf16 for the products that consume them.
+ * rows: the query rows q / out / dout / dq / lse hold (q_off[G] <= rows); it sizes the workspace.
+ * out / dout / dq: rows of ldo / lddo / lddq elements; dk_out, dv_out: rows of lddkv elements (two pointers into one stacked
+ *   buffer, or two buffers).  Every pitch >= H*dk and a multiple of 16 bytes, every operand 16-byte aligned; nothing past a
+ *   group's end is read.
+ * PRECONDITION: the key ranges [kv_off[g], kv_off[g] + kv_len[g]) of two groups that both have query rows do not overlap.  A
+ *   row of dk / dv then has one owner and no atomics are needed: two runs on the same input give the same bits.  Overlapping
+ *   ranges give wrong values in the shared rows, never an access outside the buffers.
+ * Written: dq for the query rows of every group (zeros where kv_len[g] = 0), dk / dv for the key rows of every group that has
+ *   query rows.  Rows outside every group's range are NOT written by the kernels: the caller zeroes dq / dk / dv first where
+ *   it needs zeros there (hip_ops.mha_rows_bwd does).
+ * workspace: pafc_mha_rows_bwd_workspace_bytes(rows, H) bytes, 4-byte aligned.
+ * dk != 64: PAFC_ERR_UNSUPPORTED. */
+int pafc_mha_rows_bwd(int dtype, int G, int H, int dk, long rows, const void *q, long ldq, const void *k, const void *v,
+                      long ldkv, const void *out, long ldo, const void *dout, long lddo, const float *lse,
+                      const int32_t *q_off, const int32_t *kv_off, const int32_t *kv_len, int causal, void *dq, long lddq,
+                      void *dk_out, void *dv_out, long lddkv, void *workspace, size_t workspace_bytes, pafc_stream_t stream);
+
+/* Label-smoothing loss per row in one pass over the logits (reference: wenet/transformer/label_smoothing_loss.py, the KL sum
+ * against the smoothed one-hot distribution, without the (rows, V) log-softmax):
+ *   loss[r] = C - conf * logp_y - s * (sum_v x_v - V * lse[r] - logp_y),   logp_y = x_y - lse[r],  y = target[r],
+ *   s = smoothing / (V - 1), conf = 1 - smoothing, C = conf log conf + (V - 1) s log s with 0 log 0 = 0;
+ *   lse[r] = logsumexp(x_r);  correct[r] = (argmax_v x_rv == y), the lowest index winning a tie.
+ * logits: (rows, V) PAFC_F32 or PAFC_BF16 with row pitch ldl >= V; target: (rows) int32; loss, lse: (rows) float32; correct:
+ * (rows) int32 -- all in device memory.  target -1 is the ignore id: loss 0, correct 0.  Any other target outside [0, V) gives
+ * loss NaN and correct 0 for that row; nothing is read out of bounds.  V >= 2, 0 <= smoothing <= 1. */
+int pafc_lsm_loss_rows(int dtype, long rows, int V, const void *logits, long ldl, const int32_t *target, float smoothing,
+                       float *loss, float *lse, int32_t *correct, pafc_stream_t stream);
+
+/* dlogits[r, v] = g * (exp(x_rv - lse[r]) - t_v) in the logits' dtype, t_v = conf at the target and s elsewhere: the gradient
+ * of sum_r loss[r] scaled by g, ONE float32 read from device memory (the upstream gradient times 1 / denominator).  Ignored rows
+ * (target -1) get zeros, a row whose target is otherwise outside [0, V) gets NaN, and the columns [V, ldd) of every row get
+ * zeros (the padding that makes the dX GEMM's K a multiple of 64).  dlogits may be the logits themselves (then ldd = ldl). */
+int pafc_lsm_loss_rows_bwd(int dtype, long rows, int V, const void *logits, long ldl, const int32_t *target, float smoothing,
+                           const float *lse, const float *g, void *dlogits, long ldd, pafc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,11 @@ SIGNATURES = {
     # include/pafc_attention.h
     "pafc_mha_rows": (I, [I, I, I, I, P, G, P, P, G, P, P, P, I, P, G, P]),
     "pafc_logp_gather_rows": (I, [I, G, I, P, G, P, P, P]),
+    "pafc_mha_rows_lse": (I, [I, I, I, I, P, G, P, P, G, P, P, P, I, P, G, P, P]),
+    "pafc_mha_rows_bwd_workspace_bytes": (Z, [G, I]),
+    "pafc_mha_rows_bwd": (I, [I, I, I, I, G, P, G, P, P, G, P, G, P, G, P, P, P, P, I, P, G, P, P, G, P, Z, P]),
+    "pafc_lsm_loss_rows": (I, [I, G, I, P, G, P, F, P, P, P, P]),
+    "pafc_lsm_loss_rows_bwd": (I, [I, G, I, P, G, P, F, P, P, P, G, P]),
     # include/pafc_encoder_ops.h
     "pafc_dwconv1d_cl": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P]),
     "pafc_dwconv1d_cl_ex": (I, [I, I, I, I, I, I, I, P, G, P, P, P, I, P, P]),

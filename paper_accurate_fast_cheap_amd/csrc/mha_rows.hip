@@ -15,6 +15,8 @@
 // sum taken over the rounded values, so the weights PV applies sum to one.
 // Rows past the end of a group or of its keys are never read: the row index is clamped to the last valid one and the
 // duplicate is masked (keys: -inf before the softmax) or not stored (queries).
+// pafc_mha_rows_lse is the same kernel instantiated with one more store per query row and head, lse = m + log(l), for the
+// backward (mha_rows_bwd.hip); the arithmetic of `out` is untouched, so it carries the same bits.
 #include "pafc_attention.h"
 #include "pafc_common.h"
 
@@ -41,6 +43,7 @@ struct MhaArgs {
     const int32_t *q_off, *kv_off, *kv_len;
     int causal;
     void *out; long ldo;
+    float *lse;          // (rows, H) m + log(l) of every query row and head: the LSE instantiations only
 };
 
 // One online-softmax step of a lane's query over NR masked scores s[] (already scaled): updates m, l, rescales o, leaves the
@@ -92,6 +95,7 @@ __device__ __forceinline__ void store_tile<bf16_t>(const MhaArgs &a, int h, long
 }
 
 // fp32: one 16-query tile against keys [0, kend)
+template <bool LSE>
 __device__ __forceinline__ void mha_tile(const MhaArgs &a, float, int h, int q0, int nq, int kv0, int nkv, int t, int lane) {
     const int lr = lane & 15, lq = lane >> 4;
     const int qidx = 16 * t + lr;
@@ -127,9 +131,11 @@ __device__ __forceinline__ void mha_tile(const MhaArgs &a, float, int h, int q0,
             for (int r = 0; r < 4; ++r) o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[r][16 * c], s[r], o[c], 0, 0, 0);
     }
     store_tile<float>(a, h, (long)q0 + qidx, qidx < nq, lq, o, 1.f / l);
+    if (LSE && lq == 0 && qidx < nq) a.lse[((long)q0 + qidx) * a.H + h] = m + logf(l);
 }
 
 // bf16: the same tile, keys in steps of 32
+template <bool LSE>
 __device__ __forceinline__ void mha_tile(const MhaArgs &a, bf16_t, int h, int q0, int nq, int kv0, int nkv, int t, int lane) {
     const int lr = lane & 15, lq = lane >> 4;
     const int qidx = 16 * t + lr;
@@ -171,9 +177,10 @@ __device__ __forceinline__ void mha_tile(const MhaArgs &a, bf16_t, int h, int q0
         }
     }
     store_tile<bf16_t>(a, h, (long)q0 + qidx, qidx < nq, lq, o, 1.f / l);
+    if (LSE && lq == 0 && qidx < nq) a.lse[((long)q0 + qidx) * a.H + h] = m + logf(l);
 }
 
-template <typename ET> __global__ __launch_bounds__(kMhaWaves * kWave) void mha_rows_kernel(MhaArgs a) {
+template <typename ET, bool LSE> __global__ __launch_bounds__(kMhaWaves * kWave) void mha_rows_kernel(MhaArgs a) {
     const int g = blockIdx.x, h = blockIdx.y;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q0 = a.q_off[g], nq = a.q_off[g + 1] - q0;
@@ -185,9 +192,10 @@ template <typename ET> __global__ __launch_bounds__(kMhaWaves * kWave) void mha_
             const f32x4 z[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             const int qidx = 16 * t + (lane & 15);
             store_tile<ET>(a, h, (long)q0 + qidx, qidx < nq, lane >> 4, z, 0.f);
+            if (LSE && lane < 16 && qidx < nq) a.lse[((long)q0 + qidx) * a.H + h] = -INFINITY;       // the sum over no keys
             continue;
         }
-        mha_tile(a, ET(), h, q0, nq, kv0, nkv, t, lane);
+        mha_tile<LSE>(a, ET(), h, q0, nq, kv0, nkv, t, lane);
     }
 }
 
@@ -235,24 +243,40 @@ __global__ __launch_bounds__(256) void logp_gather_kernel(int V, const ET *x, lo
 
 }  // namespace pafc
 
-extern "C" int pafc_mha_rows(int dtype, int G, int H, int dk, const void *q, long ldq, const void *k, const void *v, long ldkv,
-                             const int32_t *q_off, const int32_t *kv_off, const int32_t *kv_len, int causal, void *out, long ldo,
-                             pafc_stream_t stream) {
-    if (!q || !k || !v || !q_off || !kv_off || !kv_len || !out) return PAFC_ERR_NULL_POINTER;
+static int mha_rows_launch(int dtype, int G, int H, int dk, const void *q, long ldq, const void *k, const void *v, long ldkv,
+                           const int32_t *q_off, const int32_t *kv_off, const int32_t *kv_len, int causal, void *out, long ldo,
+                           float *lse, bool want_lse, pafc_stream_t stream) {
+    if (!q || !k || !v || !q_off || !kv_off || !kv_len || !out || (want_lse && !lse)) return PAFC_ERR_NULL_POINTER;
     if (dtype != PAFC_F32 && dtype != PAFC_BF16) return PAFC_ERR_DTYPE;
     if (G <= 0 || H <= 0 || dk <= 0 || H > 65535) return PAFC_ERR_BAD_DIMS;
     if (dk != pafc::kDk) return PAFC_ERR_UNSUPPORTED;
     const long width = (long)H * dk, per16 = dtype == PAFC_F32 ? 4 : 8;
     if (ldq < width || ldkv < width || ldo < width || ldq % per16 || ldkv % per16 || ldo % per16) return PAFC_ERR_BAD_DIMS;
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) return PAFC_ERR_ALIGNMENT;
-    pafc::MhaArgs a{H, q, ldq, k, v, ldkv, q_off, kv_off, kv_len, causal != 0, out, ldo};
+    pafc::MhaArgs a{H, q, ldq, k, v, ldkv, q_off, kv_off, kv_len, causal != 0, out, ldo, lse};
     const dim3 grid((unsigned)G, (unsigned)H), block(pafc::kMhaWaves * pafc::kWave);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PAFC_F32)
-        hipLaunchKernelGGL((pafc::mha_rows_kernel<float>), grid, block, 0, s, a);
+    if (dtype == PAFC_F32 && !want_lse)
+        hipLaunchKernelGGL((pafc::mha_rows_kernel<float, false>), grid, block, 0, s, a);
+    else if (dtype == PAFC_F32)
+        hipLaunchKernelGGL((pafc::mha_rows_kernel<float, true>), grid, block, 0, s, a);
+    else if (!want_lse)
+        hipLaunchKernelGGL((pafc::mha_rows_kernel<pafc::bf16_t, false>), grid, block, 0, s, a);
     else
-        hipLaunchKernelGGL((pafc::mha_rows_kernel<pafc::bf16_t>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((pafc::mha_rows_kernel<pafc::bf16_t, true>), grid, block, 0, s, a);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+extern "C" int pafc_mha_rows(int dtype, int G, int H, int dk, const void *q, long ldq, const void *k, const void *v, long ldkv,
+                             const int32_t *q_off, const int32_t *kv_off, const int32_t *kv_len, int causal, void *out, long ldo,
+                             pafc_stream_t stream) {
+    return mha_rows_launch(dtype, G, H, dk, q, ldq, k, v, ldkv, q_off, kv_off, kv_len, causal, out, ldo, nullptr, false, stream);
+}
+
+extern "C" int pafc_mha_rows_lse(int dtype, int G, int H, int dk, const void *q, long ldq, const void *k, const void *v,
+                                 long ldkv, const int32_t *q_off, const int32_t *kv_off, const int32_t *kv_len, int causal,
+                                 void *out, long ldo, float *lse, pafc_stream_t stream) {
+    return mha_rows_launch(dtype, G, H, dk, q, ldq, k, v, ldkv, q_off, kv_off, kv_len, causal, out, ldo, lse, true, stream);
 }
 
 extern "C" int pafc_logp_gather_rows(int dtype, long rows, int V, const void *logits, long ldl, const int32_t *target,

@@ -3504,3 +3504,272 @@ def logp_gather_rows(logits: torch.Tensor, target: torch.Tensor, out: Optional[t
                                           _lib.ptr(target), _lib.ptr(out), _lib.stream_of(logits))
     _lib.check(rc, "pafc_logp_gather_rows")
     return out
+
+
+# ---- the attention decoder's loss on packed rows (include/pafc_attention.h, csrc/mha_rows_bwd.hip) ---------------------------
+def _mha_rows_operands(who: str, q, k, v, q_off, kv_off, kv_len, heads: int) -> int:
+    d = heads * 64
+    for t in (q, k, v):
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype or t.shape[1] < d:
+            raise _lib.PafcError(f"{who}: q, k, v are 2-D GPU tensors of one dtype, unit stride along the heads")
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.PafcError(f"{who}: fp32 or bf16 operands")
+    if k.stride(0) != v.stride(0) or k.shape[0] != v.shape[0]:
+        raise _lib.PafcError(f"{who}: k and v must share their rows and their row pitch")
+    for t in (q_off, kv_off, kv_len):
+        if not t.is_cuda or t.dtype != torch.int32 or t.stride(-1) != 1:
+            raise _lib.PafcError(f"{who}: q_off, kv_off, kv_len are int32 GPU tensors")
+    G = kv_len.numel()
+    if q_off.numel() != G + 1 or kv_off.numel() != G:
+        raise _lib.PafcError(f"{who}: q_off (G + 1), kv_off (G), kv_len (G)")
+    return G
+
+
+def mha_rows_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_off: torch.Tensor, kv_off: torch.Tensor,
+                 kv_len: torch.Tensor, heads: int, causal: bool):
+    """mha_rows that also returns lse (rows, H) float32, the log of every row's softmax denominator per head
+    (pafc_mha_rows_lse): -> (out (rows, H * 64) with the bits of mha_rows, lse).  Rows outside every group: out undefined,
+    lse -inf."""
+    G = _mha_rows_operands("mha_rows_lse", q, k, v, q_off, kv_off, kv_len, heads)
+    out = torch.empty(q.shape[0], heads * 64, dtype=q.dtype, device=q.device)
+    lse = torch.full((q.shape[0], heads), float("-inf"), dtype=torch.float32, device=q.device)
+    if G == 0 or q.shape[0] == 0:
+        return out, lse
+    rc = _lib.lib().pafc_mha_rows_lse(_lib.dtype_code(q.dtype), G, heads, 64, _lib.ptr(q), q.stride(0), _lib.ptr(k), _lib.ptr(v),
+                                      k.stride(0), _lib.ptr(q_off), _lib.ptr(kv_off), _lib.ptr(kv_len), int(bool(causal)),
+                                      _lib.ptr(out), out.stride(0), _lib.ptr(lse), _lib.stream_of(q))
+    _lib.check(rc, "pafc_mha_rows_lse")
+    return out, lse
+
+
+def mha_rows_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor,
+                 q_off: torch.Tensor, kv_off: torch.Tensor, kv_len: torch.Tensor, heads: int, causal: bool,
+                 dq: Optional[torch.Tensor] = None, dk: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None):
+    """(dq, dk, dv) of mha_rows from its operands, the out / lse of mha_rows_lse and the upstream gradient dout
+    (pafc_mha_rows_bwd; no atomics, two runs give the same bits).  PRECONDITION: the key ranges of two groups that both have
+    query rows do not overlap.  dq (rows, >= H * 64), dk / dv (kv rows, >= H * 64, one row pitch) may be handed in, column
+    slices of stacked buffers included; THIS wrapper zeroes them first (the kernels write owned rows only), so rows outside
+    every group's range come back zero."""
+    G = _mha_rows_operands("mha_rows_bwd", q, k, v, q_off, kv_off, kv_len, heads)
+    d, rows = heads * 64, q.shape[0]
+    for t in (out, dout):
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype or t.shape[0] != rows or t.shape[1] < d:
+            raise _lib.PafcError("mha_rows_bwd: out and dout are (rows, >= H * 64) in the operands' dtype")
+    if not lse.is_cuda or lse.dtype != torch.float32 or lse.shape != (rows, heads) or not lse.is_contiguous():
+        raise _lib.PafcError("mha_rows_bwd: lse is (rows, H) float32, contiguous")
+    if dq is None:
+        dq = torch.zeros(rows, d, dtype=q.dtype, device=q.device)
+    else:
+        dq.zero_()
+    if dk is None or dv is None:
+        dkv = torch.zeros(k.shape[0], 2 * d, dtype=q.dtype, device=q.device)
+        dk, dv = dkv[:, :d], dkv[:, d:]
+    else:
+        dk.zero_()
+        dv.zero_()
+    if (not dq.is_cuda or dq.dtype != q.dtype or dq.dim() != 2 or dq.stride(1) != 1 or dq.shape[0] != rows or dq.shape[1] < d):
+        raise _lib.PafcError("mha_rows_bwd: dq is (rows, >= H * 64) in the operands' dtype")
+    for t in (dk, dv):
+        if (not t.is_cuda or t.dtype != q.dtype or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != k.shape[0] or t.shape[1] < d
+                or t.stride(0) != dk.stride(0)):
+            raise _lib.PafcError("mha_rows_bwd: dk, dv are (kv rows, >= H * 64) in the operands' dtype with one row pitch")
+    if G == 0 or rows == 0:
+        return dq, dk, dv
+    L = _lib.lib()
+    nbytes = L.pafc_mha_rows_bwd_workspace_bytes(rows, heads)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    rc = L.pafc_mha_rows_bwd(_lib.dtype_code(q.dtype), G, heads, 64, rows, _lib.ptr(q), q.stride(0), _lib.ptr(k), _lib.ptr(v),
+                             k.stride(0), _lib.ptr(out), out.stride(0), _lib.ptr(dout), dout.stride(0), _lib.ptr(lse),
+                             _lib.ptr(q_off), _lib.ptr(kv_off), _lib.ptr(kv_len), int(bool(causal)), _lib.ptr(dq), dq.stride(0),
+                             _lib.ptr(dk), _lib.ptr(dv), dk.stride(0), _lib.ptr(ws), nbytes, _lib.stream_of(q))
+    _lib.check(rc, "pafc_mha_rows_bwd")
+    return dq, dk, dv
+
+
+class _MhaRowsTrain(torch.autograd.Function):
+    """mha_rows under autograd: pafc_mha_rows_lse forward, pafc_mha_rows_bwd backward.  When q, k and v are the column thirds
+    of one stacked projection (self-attention) the three gradients are the thirds of one buffer, k | v halves likewise."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_off, kv_off, kv_len, heads, causal):
+        out, lse = mha_rows_lse(q, k, v, q_off, kv_off, kv_len, heads, causal)
+        ctx.save_for_backward(q, k, v, out, lse, q_off, kv_off, kv_len)
+        ctx.heads, ctx.causal = heads, bool(causal)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, q_off, kv_off, kv_len = ctx.saved_tensors
+        d = ctx.heads * 64
+        if dout.dtype != q.dtype:
+            dout = dout.to(q.dtype)
+        if dout.stride(1) != 1 or (dout.stride(0) * dout.element_size()) % 16 or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        dq = dk = dv = None
+        if q.shape[0] == k.shape[0]:                       # one buffer for the three: the stacked projection's gradient
+            buf = torch.zeros(q.shape[0], 3 * d, dtype=q.dtype, device=q.device)
+            dq, dk, dv = buf[:, :d], buf[:, d:2 * d], buf[:, 2 * d:]
+        dq, dk, dv = mha_rows_bwd(q, k, v, out, dout, lse, q_off, kv_off, kv_len, ctx.heads, ctx.causal, dq, dk, dv)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def mha_rows_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_off: torch.Tensor, kv_off: torch.Tensor,
+                   kv_len: torch.Tensor, heads: int, causal: bool) -> torch.Tensor:
+    """mha_rows with gradients for q, k and v (which may be slices of one stacked projection).  The key ranges of two groups
+    with query rows must not overlap (mha_rows_bwd)."""
+    return _MhaRowsTrain.apply(q, k, v, q_off, kv_off, kv_len, heads, causal)
+
+
+def _lsm_operands(who: str, logits: torch.Tensor, target: torch.Tensor):
+    if not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.PafcError(f"{who}: logits are a 2-D fp32 / bf16 GPU tensor with unit stride along the vocabulary")
+    if not target.is_cuda or target.dtype != torch.int32 or target.numel() != logits.shape[0] or target.stride(-1) != 1:
+        raise _lib.PafcError(f"{who}: target is (rows) int32 on the GPU")
+
+
+def lsm_loss_rows(logits: torch.Tensor, target: torch.Tensor, smoothing: float):
+    """Per row of (rows, V) logits: the label-smoothing loss against target (int32; -1 is ignored), lse = logsumexp and
+    correct = (argmax == target) (pafc_lsm_loss_rows) -> (loss, lse float32 (rows), correct int32 (rows))."""
+    _lsm_operands("lsm_loss_rows", logits, target)
+    rows, V = logits.shape
+    loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    correct = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    if rows:
+        rc = _lib.lib().pafc_lsm_loss_rows(_lib.dtype_code(logits.dtype), rows, V, _lib.ptr(logits), logits.stride(0),
+                                           _lib.ptr(target), float(smoothing), _lib.ptr(loss), _lib.ptr(lse), _lib.ptr(correct),
+                                           _lib.stream_of(logits))
+        _lib.check(rc, "pafc_lsm_loss_rows")
+    return loss, lse, correct
+
+
+def lsm_loss_rows_bwd(logits: torch.Tensor, target: torch.Tensor, smoothing: float, lse: torch.Tensor, g: torch.Tensor,
+                      out: Optional[torch.Tensor] = None, pad_to: Optional[int] = None) -> torch.Tensor:
+    """g * d(sum of lsm_loss_rows' losses) / dlogits in the logits' dtype (pafc_lsm_loss_rows_bwd); g one float32 on the device.
+    out: where to write ((rows, V) view of rows with pitch pad_to, default a fresh buffer; may be `logits`); the columns from V
+    to pad_to of every row are zeroed.  Returns the (rows, V) view."""
+    _lsm_operands("lsm_loss_rows_bwd", logits, target)
+    rows, V = logits.shape
+    if out is None:
+        width = pad_to or V
+        out = torch.empty(rows, width, dtype=logits.dtype, device=logits.device)[:, :V]
+    if (not out.is_cuda or out.dtype != logits.dtype or out.shape != logits.shape or out.stride(1) != 1
+            or out.stride(0) < (pad_to or V)):
+        raise _lib.PafcError("lsm_loss_rows_bwd: out is (rows, V) in the logits' dtype with a row pitch of at least pad_to")
+    if (not lse.is_cuda or lse.dtype != torch.float32 or lse.numel() != rows or not g.is_cuda or g.dtype != torch.float32
+            or g.numel() != 1):
+        raise _lib.PafcError("lsm_loss_rows_bwd: lse (rows) and g (1) are float32 on the GPU")
+    if rows:
+        rc = _lib.lib().pafc_lsm_loss_rows_bwd(_lib.dtype_code(logits.dtype), rows, V, _lib.ptr(logits), logits.stride(0),
+                                               _lib.ptr(target), float(smoothing), _lib.ptr(lse), _lib.ptr(g), _lib.ptr(out),
+                                               pad_to or V, _lib.stream_of(logits))
+        _lib.check(rc, "pafc_lsm_loss_rows_bwd")
+    return out
+
+
+class _AttHeadLoss(torch.autograd.Function):
+    """output_layer + label-smoothing loss of the attention decoder on hand-written kernels only, in the manner of
+    _CtcHeadLoss: logits = x W^T + b as bf16 rows padded to a multiple of 64 columns (pafc_gemm_bf16), loss / lse / correct per
+    row from the logits (pafc_lsm_loss_rows), and backwards the gradient written over the logits (pafc_lsm_loss_rows_bwd),
+    dX = dlogits W on pafc_gemm_bf16 against the zero-padded W^T, dW / db through gemm_tn.  The (rows, V) log-softmax never
+    exists.  A vocabulary that is no multiple of 8 runs the three products over the padded width (zero weight rows)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, target, smoothing, denom):
+        M, C = x.shape
+        V = weight.shape[0]
+        Vp = (V + 63) // 64 * 64
+        xb = x.to(torch.bfloat16)
+        if xb.stride(1) != 1 or xb.stride(0) % 8 or xb.data_ptr() % 16:
+            xb = xb.contiguous()
+        wb = _bf16_shadow(weight).detach()
+        bb = None if bias is None else _bf16_shadow(bias).detach()
+        padded = V % 8 != 0
+        if padded:
+            wp = torch.zeros((Vp, C), dtype=torch.bfloat16, device=x.device)
+            wp[:V].copy_(wb)
+            wb = wp
+            if bb is not None:
+                bp = torch.zeros(Vp, dtype=torch.bfloat16, device=x.device)
+                bp[:V].copy_(bb)
+                bb = bp
+        logits = torch.empty((M, Vp), dtype=torch.bfloat16, device=x.device)
+        gemm_bf16(xb, wb, bb, out=logits if padded else logits[:, :V])
+        loss, lse, correct = lsm_loss_rows(logits[:, :V], target, smoothing)
+        ctx.save_for_backward(xb, wb, logits, lse, target, denom)
+        ctx.dims = (M, C, V, Vp, float(smoothing), padded)
+        ctx.w_dtype, ctx.b_dtype, ctx.x_dtype = weight.dtype, None if bias is None else bias.dtype, x.dtype
+        n_correct = correct.sum()
+        ctx.mark_non_differentiable(n_correct)
+        return loss.sum() / denom, n_correct
+
+    @staticmethod
+    def backward(ctx, g, _gcorrect):
+        xb, wb, logits, lse, target, denom = ctx.saved_tensors
+        M, C, V, Vp, smoothing, padded = ctx.dims
+        if getattr(ctx, "spent", False):
+            raise _lib.PafcError("att_head_loss: a second backward pass through one forward (the gradient was written over the logits)")
+        ctx.spent = True
+        gf = (g.detach().to(torch.float32) / denom).reshape(1).contiguous()
+        lsm_loss_rows_bwd(logits[:, :V], target, smoothing, lse, gf, out=logits[:, :V], pad_to=Vp)
+        dl = logits                                                                 # written in place, (M, Vp) with its zero padding
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wt = torch.zeros((C, Vp), dtype=torch.bfloat16, device=xb.device)       # W^T, zero beyond V: K = Vp is a multiple of 64
+            wt[:, :V].copy_(wb[:V].t())
+            dx = gemm_bf16(dl, wt).to(ctx.x_dtype)
+        want_b = ctx.b_dtype is not None and ctx.needs_input_grad[2]
+        dlv = dl if padded else dl[:, :V]
+        if ctx.needs_input_grad[1]:
+            od = ctx.w_dtype if ctx.w_dtype in (torch.float32, torch.bfloat16) else torch.float32
+            if want_b:
+                dw, db = gemm_tn(dlv, xb, od, want_bias=True)
+                db = db[:V].to(ctx.b_dtype)
+            else:
+                dw = gemm_tn(dlv, xb, od)
+            dw = dw[:V].to(ctx.w_dtype)
+        elif want_b:
+            db = dl[:, :V].sum(0, dtype=torch.float32).to(ctx.b_dtype)
+        return dx, dw, db, None, None, None
+
+
+def att_head_loss(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], target: torch.Tensor, smoothing: float,
+                  denom: torch.Tensor):
+    """(sum_r lsm_loss(x_r W^T + b, target_r) / denom, number of rows whose argmax is their target): see _AttHeadLoss.  x (rows,
+    C) with C % 64 == 0, target (rows) int32 on the GPU (-1: ignored), denom a float32 scalar tensor on the GPU (the batch size
+    or the number of scored tokens).  One backward pass per forward: the gradient is written over the saved logits."""
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or x.shape[1] % 64:
+        raise _lib.PafcError("att_head_loss: x (rows, C) against weight (V, C), C a multiple of 64")
+    if not denom.is_cuda or denom.dtype != torch.float32 or denom.numel() != 1:
+        raise _lib.PafcError("att_head_loss: denom is one float32 on the GPU")
+    return _AttHeadLoss.apply(x, weight, bias, target, float(smoothing), denom.reshape(()))
+
+
+def att_loss_unmet(decoders, x: torch.Tensor) -> Optional[str]:
+    """What keeps the attention decoder's loss from running on packed rows over the library's kernels, or None.  decoders: the
+    TransformerDecoder modules that will run (left, and right when reverse_weight > 0); x: the encoder output."""
+    from .transformer.attn_rescore import KERNEL_ACTS
+    if not x.is_cuda:
+        return "the operands are not on the GPU"
+    if not torch.is_grad_enabled():
+        return "gradients are disabled"
+    if not train_kernels_enabled():
+        return "PAFC_TRAIN_KERNELS=0"
+    autocast_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    for dec in decoders:
+        params = list(dec.parameters())
+        if any(not p.is_cuda for p in params):
+            return "the decoder is not on the GPU"
+        bf16_model = x.dtype == torch.bfloat16 and all(p.dtype == torch.bfloat16 for p in params)
+        if not (bf16_model or (autocast_bf16 and all(p.dtype in (torch.float32, torch.bfloat16) for p in params))):
+            return "neither bf16 autocast nor a bf16 module"
+        d = dec.after_norm.normalized_shape[0]
+        if d != dec.attention_heads * 64:
+            return f"attention heads of {d / dec.attention_heads:g} dimensions (the attention kernels take 64)"
+        if any(l.self_attn.dropout.p != 0 or l.src_attn.dropout.p != 0 for l in dec.decoders):
+            return "attention-probability dropout (self_attention_dropout_rate / src_attention_dropout_rate must be 0)"
+        if dec.activation_type not in KERNEL_ACTS:
+            return f"activation_type {dec.activation_type!r} (the kernels path has {sorted(KERNEL_ACTS)})"
+        if not dec.use_output_layer:
+            return "a decoder without output_layer"
+    return None

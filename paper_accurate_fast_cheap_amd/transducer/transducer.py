@@ -12,7 +12,8 @@ Training objective (forward, :105-175): transducer_weight * RNN-T loss + ctc_wei
 encoder.  The reference's RNN-T loss is the third-party `optimized_transducer.transducer_loss` (transducer.py:506-523;
 Rev fork, unpinned): restated from the published definition in `loss.py` -- PARITY UNPINNED.  Its attention decoder was
 not released (decoder.py is swallowed by .gitignore:44): the decoder here is the published WeNet one (transformer/decoder.py),
-used by the second pass only -- the training objective has no attention branch."""
+used by the second pass and, when it is built trainable (init_model: args.train_attention_decoder), by the attention term of
+the objective, attention_decoder_weight * loss_att (transformer/attn_train.py)."""
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -41,8 +42,10 @@ class Transducer(ASRModel):
     def __init__(self, vocab_size: int, blank: int, encoder: torch.nn.Module, predictor: torch.nn.Module,
                  joint: torch.nn.Module, ctc=None, special_tokens: Optional[dict] = None, attention_decoder=None,
                  ctc_weight: float = 0.0, transducer_weight: float = 1.0, attention_weight: float = 0.0,
-                 transducer_type: Optional[str] = None, **_unused_model_conf):
-        super().__init__(vocab_size, encoder, ctc, ctc_weight, special_tokens, decoder=attention_decoder)
+                 transducer_type: Optional[str] = None, reverse_weight: float = 0.0, lsm_weight: float = 0.0,
+                 length_normalized_loss: bool = False, **_unused_model_conf):
+        super().__init__(vocab_size, encoder, ctc, ctc_weight, special_tokens, decoder=attention_decoder,
+                         reverse_weight=reverse_weight, lsm_weight=lsm_weight, length_normalized_loss=length_normalized_loss)
         # model_conf.transducer_type (the reference's key, default "optimized_transducer"): every value but "fused_joint" keeps the
         # restated path below; "fused_joint" asks for the fused joint + loss kernels (hip_ops.rnnt_joint_loss) and never falls back
         self.fused_joint = transducer_type == FUSED_JOINT
@@ -54,7 +57,8 @@ class Transducer(ASRModel):
         self.bs: Optional[PrefixBeamSearch] = None
 
     def forward(self, batch: dict, device: torch.device) -> Dict[str, Optional[torch.Tensor]]:
-        """transducer.py:105-175 without the attention decoder: encoder -> RNN-T loss (+ ctc_weight * CTC)."""
+        """transducer.py:105-175: encoder -> RNN-T loss (+ ctc_weight * CTC) (+ attention_decoder_weight * attention loss when
+        the model has an attention decoder with trainable parameters and that weight is not 0)."""
         speech = batch["feats"].to(device)
         speech_lengths = batch["feats_lengths"].to(device)
         text = batch["target"].to(device)
@@ -68,7 +72,11 @@ class Transducer(ASRModel):
         if self.ctc_weight != 0.0 and self.ctc is not None:
             loss_ctc = self.ctc.loss(encoder_out.float(), encoder_out_lens, text, text_lengths)
             loss = loss + self.ctc_weight * loss_ctc.sum()
-        return {"loss": loss, "loss_att": None, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "th_accuracy": -1.0}
+        loss_att, acc_att = None, -1.0
+        if self.attention_decoder_weight != 0.0 and self._trains_attention():
+            loss_att, acc_att = self._calc_att_loss(encoder_out, encoder_mask, text, batch["target_lengths"])
+            loss = loss + self.attention_decoder_weight * loss_att.sum()
+        return {"loss": loss, "loss_att": loss_att, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "th_accuracy": acc_att}
 
     def _compute_loss(self, encoder_out, encoder_out_lens, text, text_lengths) -> torch.Tensor:
         """transducer.py:525-561 (optimized_transducer branch): predictor over blank-prepended targets, joint on the

@@ -15,19 +15,27 @@ from .search import DecodeResult, ctc_greedy_search
 
 class ASRModel(torch.nn.Module):
     def __init__(self, vocab_size: int, encoder: torch.nn.Module, ctc: CTC, ctc_weight: float = 1.0,
-                 special_tokens: Optional[dict] = None, decoder: Optional[torch.nn.Module] = None, **_unused_model_conf):
+                 special_tokens: Optional[dict] = None, decoder: Optional[torch.nn.Module] = None, reverse_weight: float = 0.0,
+                 lsm_weight: float = 0.0, length_normalized_loss: bool = False, **_unused_model_conf):
         super().__init__()
         self.vocab_size = vocab_size
         self.encoder = encoder
         self.ctc = ctc
         self.decoder = decoder          # the attention decoder of the second pass (transformer/decoder.py), or None
         self.ctc_weight = ctc_weight
+        # the attention term of the training objective (transformer/attn_train.py): the right decoder's share of it, the label
+        # smoothing and the loss' denominator (the reference's keys and defaults, asr_model.py:66-68)
+        self.reverse_weight = reverse_weight
+        self.lsm_weight = lsm_weight
+        self.length_normalized_loss = length_normalized_loss
         self.special_tokens = special_tokens
         self.sos = (vocab_size - 1) if special_tokens is None else special_tokens.get("<sos>", vocab_size - 1)
         self.eos = (vocab_size - 1) if special_tokens is None else special_tokens.get("<eos>", vocab_size - 1)
 
     def forward(self, batch: dict, device: torch.device) -> Dict[str, Optional[torch.Tensor]]:
-        """CTC-only training objective over the accelerated encoder (the hybrid losses live outside the path)."""
+        """The training objective over the accelerated encoder: the CTC loss, and with an attention decoder that has trainable
+        parameters and ctc_weight != 1 the hybrid ctc_weight * ctc + (1 - ctc_weight) * att of asr_model.py:199-205 (adding the
+        keys loss_att and th_accuracy).  Without a decoder, or with the frozen one of the second pass, CTC only."""
         speech = batch["feats"].to(device)
         speech_lengths = batch["feats_lengths"].to(device)
         text = batch["target"].to(device)
@@ -35,7 +43,22 @@ class ASRModel(torch.nn.Module):
         encoder_out, encoder_mask = self.encoder(speech, speech_lengths)
         encoder_out_lens = encoder_mask.squeeze(1).sum(1)
         loss_ctc = self.ctc.loss(encoder_out.float(), encoder_out_lens, text, text_lengths)
+        if self.ctc_weight != 1.0 and self._trains_attention():
+            loss_att, acc_att = self._calc_att_loss(encoder_out, encoder_mask, text, batch["target_lengths"])
+            loss = self.ctc_weight * loss_ctc + (1 - self.ctc_weight) * loss_att
+            return {"loss": loss, "loss_att": loss_att, "loss_ctc": loss_ctc, "th_accuracy": acc_att}
         return {"loss": loss_ctc, "loss_ctc": loss_ctc}
+
+    def _trains_attention(self) -> bool:
+        from .attn_train import trainable_decoder
+        return trainable_decoder(self)
+
+    def _calc_att_loss(self, encoder_out: torch.Tensor, encoder_mask: torch.Tensor, text: torch.Tensor,
+                       text_lengths: torch.Tensor, backend: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(loss_att, acc_att) of asr_model.py:251-292 (transformer/attn_train.att_loss); text_lengths as the batch holds them
+        (on the host: the packed rows are then planned without reading the device)."""
+        from .attn_train import att_loss
+        return att_loss(self, encoder_out, encoder_mask, text, text_lengths, backend)
 
     def _forward_encoder(self, speech: torch.Tensor, speech_lengths: torch.Tensor, decoding_chunk_size: int = -1,
                          num_decoding_left_chunks: int = -1, simulate_streaming: bool = False,

@@ -6,7 +6,8 @@ model, model_conf, tokenizer_conf, dataset_conf), honours args.checkpoint, and s
 ['num_seen_frames'], ['step'] and the model attributes lsl_enc / lsl_dec / add_cat_embs / cat_labels exactly like
 the reference (:242-268).  It builds encoder + CTC (+ RNN predictor and joint for `model: transducer`).  The `decoder` section of a reference
 YAML (`transformer` / `bitransformer` + decoder_conf) becomes the frozen attention decoder of the second pass when
-args.attention_decoder is true; otherwise it is accepted and skipped (a checkpoint's extra keys are ignored the way the
+args.attention_decoder is true, the trainable one of the attention loss when args.train_attention_decoder is; otherwise it is
+accepted and skipped (a checkpoint's extra keys are ignored the way the
 reference's def_strict=False does, :243).
 """
 import logging
@@ -48,18 +49,23 @@ def init_model(args, configs):
     ctc.fp32_split_operands = bool(getattr(encoder, "fp32_split_operands", True))   # a pure-fp32 model keeps exact fp32 products
     model_conf = dict(configs.get("model_conf", {}))
     special = configs.get("tokenizer_conf", {}).get("special_tokens", None)
-    # The attention decoder of the second pass (init_model.py:150-160 of the reference) is built only on request
-    # (args.attention_decoder) and frozen: the training objective has no attention term, and an unused trainable decoder breaks
-    # DDP's unused-parameter check.  Without the switch a YAML's `decoder` section is accepted and skipped, as before.
+    # The attention decoder (init_model.py:150-160 of the reference) is built only on request.  args.attention_decoder: the
+    # frozen decoder of the second pass (an unused trainable decoder breaks DDP's unused-parameter check).
+    # args.train_attention_decoder: trainable, for the attention term of the objective (transformer/attn_train.py); with
+    # model_conf.reverse_weight == 0 the right decoder takes no part in it and stays frozen, for the same check.  Without either
+    # switch a YAML's `decoder` section is accepted and skipped, as before.
     decoder = None
-    if getattr(args, "attention_decoder", False):
+    train_decoder = bool(getattr(args, "train_attention_decoder", False))
+    if getattr(args, "attention_decoder", False) or train_decoder:
         from ..transformer.decoder import DECODER_CLASSES
         decoder_type = configs.get("decoder", "bitransformer")
         if decoder_type not in DECODER_CLASSES:
             raise NotImplementedError(f"decoder {decoder_type!r}: only {sorted(DECODER_CLASSES)} are implemented")
         decoder = DECODER_CLASSES[decoder_type](vocab_size, encoder.output_size(), **configs.get("decoder_conf", {}))
         decoder.fp32_split_operands = bool(getattr(encoder, "fp32_split_operands", True))
-        decoder.requires_grad_(False)
+        decoder.requires_grad_(train_decoder)
+        if train_decoder and float(model_conf.get("reverse_weight", 0.0)) == 0.0 and hasattr(decoder, "right_decoder"):
+            decoder.right_decoder.requires_grad_(False)
     model_conf.pop("decoder", None)
     model_conf.pop("attention_decoder", None)
     if configs.get("model", "asr_model") == "transducer" and "predictor_conf" in configs and "joint_conf" in configs:
