@@ -66,6 +66,10 @@ SIGNATURES = {
     "pafc_mha_rows_bwd": (I, [I, I, I, I, G, P, G, P, P, G, P, G, P, G, P, P, P, P, I, P, G, P, P, G, P, Z, P]),
     "pafc_lsm_loss_rows": (I, [I, G, I, P, G, P, F, P, P, P, P]),
     "pafc_lsm_loss_rows_bwd": (I, [I, G, I, P, G, P, F, P, P, P, G, P]),
+    # include/pafc_attn_search.h
+    "pafc_mha_step": (I, [I, I, I, I, I, I, P, G, P, P, P, P, P, G, P]),
+    "pafc_attn_beam_select_workspace_bytes": (Z, [I, I]),
+    "pafc_attn_beam_select": (I, [I, I, I, I, I, I, I, P, G, P, P, P, P, P, P, P, P, P, P, Z, P]),
     # include/pafc_encoder_ops.h
     "pafc_dwconv1d_cl": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P]),
     "pafc_dwconv1d_cl_ex": (I, [I, I, I, I, I, I, I, P, G, P, P, P, I, P, P]),

@@ -3773,3 +3773,87 @@ def att_loss_unmet(decoders, x: torch.Tensor) -> Optional[str]:
         if not dec.use_output_layer:
             return "a decoder without output_layer"
     return None
+
+
+# ---- the attention decoder's beam search (include/pafc_attn_search.h, csrc/attn_search.hip) ----------------------------------
+def _i32_gpu(who: str, **tensors) -> None:
+    for name, t in tensors.items():
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.PafcError(f"{who}: {name} is a contiguous int32 GPU tensor")
+
+
+def mha_step(qkv: torch.Tensor, cache: torch.Tensor, anc: torch.Tensor, pos: torch.Tensor, done: torch.Tensor, beam: int,
+             heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Single-query self-attention of the R new rows of a beam-search step through the ancestor table (pafc_mha_step).
+    qkv (R, >= 3 * H * 64) the stacked q | k | v projection of the new rows, fp32 or bf16, unit stride along the columns;
+    cache (P, R, 2 * H * 64) contiguous in qkv's dtype: the launch stores the rows' k | v at position pos[0] and attends over
+    the positions [0, pos[0]]; anc (2, R, P), pos (1), done (1) int32 on the device.  With done set or pos outside [0, P)
+    nothing is written.  Returns out (R, H * 64)."""
+    d = heads * 64
+    if not qkv.is_cuda or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < 3 * d:
+        raise _lib.PafcError("mha_step: qkv is a 2-D GPU tensor of at least 3 * H * 64 columns with unit stride along them")
+    R = qkv.shape[0]
+    if not cache.is_cuda or cache.dtype != qkv.dtype or cache.dim() != 3 or not cache.is_contiguous() \
+            or cache.shape[1:] != (R, 2 * d) or cache.shape[0] < 1:
+        raise _lib.PafcError("mha_step: cache is (P, R, 2 * H * 64), contiguous, in qkv's dtype")
+    P = cache.shape[0]
+    _i32_gpu("mha_step", anc=anc, pos=pos, done=done)
+    if anc.shape != (2, R, P) or pos.numel() != 1 or done.numel() != 1:
+        raise _lib.PafcError("mha_step: anc is (2, R, P), pos and done hold one int32 each")
+    if not 1 <= beam <= 16 or R % beam:
+        raise _lib.PafcError(f"mha_step: a beam of {beam} for {R} rows (1..16, dividing the rows)")
+    if out is None:
+        out = torch.empty(R, d, dtype=qkv.dtype, device=qkv.device)
+    elif not out.is_cuda or out.dtype != qkv.dtype or out.dim() != 2 or out.stride(1) != 1 or out.shape != (R, d):
+        raise _lib.PafcError("mha_step: out is (R, H * 64) in qkv's dtype")
+    rc = _lib.lib().pafc_mha_step(_lib.dtype_code(qkv.dtype), R, beam, heads, 64, P, _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cache),
+                                  _lib.ptr(anc), _lib.ptr(pos), _lib.ptr(done), _lib.ptr(out), out.stride(0), _lib.stream_of(qkv))
+    _lib.check(rc, "pafc_mha_step")
+    return out
+
+
+def attn_beam_select_workspace(B: int, beam: int, device) -> torch.Tensor:
+    nbytes = _lib.lib().pafc_attn_beam_select_workspace_bytes(B, beam)
+    if nbytes == 0:
+        raise _lib.PafcError(f"attn_beam_select: {B} utterances with a beam of {beam} (the beam is 1..16)")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def attn_beam_select(logits: torch.Tensor, beam: int, eos: int, cap: int, score: torch.Tensor, ended: torch.Tensor,
+                     token: torch.Tensor, anc: torch.Tensor, trace_parent: torch.Tensor, trace_token: torch.Tensor,
+                     trace_score: torch.Tensor, pos: torch.Tensor, done: torch.Tensor,
+                     workspace: Optional[torch.Tensor] = None) -> None:
+    """One beam-search step's selection straight from the (R, V) logits (pafc_attn_beam_select): per row the logsumexp and
+    the `beam` largest logits (an ended row: the single candidate (eos, 0)), per utterance the `beam` best of its beam * beam
+    candidates by score[parent] + logp; writes score / ended / token (R), the trace row pos[0] of trace_parent / trace_token /
+    trace_score (P, R), the other half of anc (2, R, P), done and pos += 1, all in place.  Frozen (nothing written) when done
+    is set or pos[0] >= cap."""
+    if not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.PafcError("attn_beam_select: logits are a 2-D GPU tensor with unit stride along the vocabulary")
+    R, V = logits.shape
+    if not 1 <= beam <= 16 or R % beam or R == 0:
+        raise _lib.PafcError(f"attn_beam_select: a beam of {beam} for {R} rows (1..16, dividing the rows)")
+    if V < beam:
+        raise _lib.PafcError(f"attn_beam_select: a vocabulary of {V} for a beam of {beam}")
+    _i32_gpu("attn_beam_select", ended=ended, token=token, anc=anc, trace_parent=trace_parent, trace_token=trace_token, pos=pos,
+             done=done)
+    for name, t in (("score", score), ("trace_score", trace_score)):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PafcError(f"attn_beam_select: {name} is a contiguous float32 GPU tensor")
+    P = trace_parent.shape[0] if trace_parent.dim() == 2 else 0
+    if score.numel() != R or ended.numel() != R or token.numel() != R or anc.shape != (2, R, P) or pos.numel() != 1 \
+            or done.numel() != 1 or any(t.shape != (P, R) for t in (trace_parent, trace_token, trace_score)):
+        raise _lib.PafcError("attn_beam_select: score / ended / token (R), anc (2, R, P), the traces (P, R), pos and done (1)")
+    if not 1 <= cap < P:
+        raise _lib.PafcError(f"attn_beam_select: a cap of {cap} steps for tables of {P} positions (1 <= cap < P)")
+    B = R // beam
+    if workspace is None:
+        workspace = attn_beam_select_workspace(B, beam, logits.device)
+    elif not workspace.is_cuda or not workspace.is_contiguous():
+        raise _lib.PafcError("attn_beam_select: the workspace is a contiguous GPU tensor")
+    rc = _lib.lib().pafc_attn_beam_select(_lib.dtype_code(logits.dtype), B, beam, V, P, cap, eos, _lib.ptr(logits),
+                                          logits.stride(0), _lib.ptr(score), _lib.ptr(ended), _lib.ptr(token), _lib.ptr(anc),
+                                          _lib.ptr(trace_parent), _lib.ptr(trace_token), _lib.ptr(trace_score), _lib.ptr(pos),
+                                          _lib.ptr(done), _lib.ptr(workspace), workspace.numel() * workspace.element_size(),
+                                          _lib.stream_of(logits))
+    _lib.check(rc, "pafc_attn_beam_select")

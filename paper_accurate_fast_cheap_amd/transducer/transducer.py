@@ -296,8 +296,8 @@ class Transducer(ASRModel):
                transducer_weight: float = 0.0, simulate_streaming: bool = False, reverse_weight: float = 0.0,
                context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0, cat_embs=None,
                frame_body: Optional[str] = None, attn_weight: float = 0.0, search_ctc_weight: float = 0.3,
-               search_transducer_weight: float = 0.7, score_backend: Optional[str] = None, **_ignored
-               ) -> Dict[str, List[DecodeResult]]:
+               search_transducer_weight: float = 0.7, score_backend: Optional[str] = None, length_penalty: float = 0.0,
+               **_ignored) -> Dict[str, List[DecodeResult]]:
         """frame_body: for rnnt_beam_search and rnnt_beam_td_rescoring, the per-frame body of beam_search_decode ("framework" /
         "kernels").
         Two-pass modes with the attention term (a model with an attention decoder; NotImplementedError without one):
@@ -306,6 +306,9 @@ class Transducer(ASRModel):
             final_i = attn_weight * attn_i + ctc_weight * first_pass_score_i + transducer_weight * td_i (transducer.py:401-420);
           attn_i = score_attention's l2r_i, or (1 - reverse_weight) * l2r_i + reverse_weight * r2l_i; results as
           attn_rescore.attention_rescore builds them (nbest_attn_scores, confidence, tokens_confidence).
+        "attention_beam_search" (likewise a model with an attention decoder): the decoder's own autoregressive beam search with
+          length_penalty (attn_search.attention_beam_search, backend: score_backend); the reference's spelling "attention" is
+          still refused.
         Two-pass modes without it (a non-zero reverse_weight or attn_weight with them is a ValueError):
           "ctc_beam_td_rescoring": first pass ctc_prefix_beam_search (computed once when that mode is requested too);
           "rnnt_beam_td_rescoring": first pass beam_search_decode with search_ctc_weight / search_transducer_weight -- the
@@ -319,7 +322,7 @@ class Transducer(ASRModel):
                              "the attention decoder was not released with the reference, so this mode has no attention term to "
                              "weigh; ctc_beam_td_attn_rescoring / rnnt_beam_attn_rescoring of a model built with an attention "
                              "decoder have one")
-        with_attn = [m for m in methods if m in ATTN_RESCORING_MODES]
+        with_attn = [m for m in methods if m in ATTN_RESCORING_MODES + ("attention_beam_search",)]
         if with_attn and self.decoder is None:
             raise NotImplementedError(f"decode mode {with_attn[0]!r} needs an attention decoder (init_model builds one with "
                                       "args.attention_decoder)")
@@ -340,6 +343,12 @@ class Transducer(ASRModel):
             elif m == "ctc_prefix_beam_search":
                 from ..transformer.search import ctc_prefix_beam_search
                 results[m] = ctc_prefix_beam_search(ctc_probs, encoder_lens, beam_size, context_graph, blank_id)
+            elif m == "attention_beam_search":
+                from ..transformer.attn_search import attention_beam_search
+                results[m] = attention_beam_search(self, encoder_out, encoder_mask, beam_size, length_penalty, score_backend)
+            elif m == "attention":
+                raise NotImplementedError("decode mode 'attention' is not accepted under the reference's name: the attention "
+                                          "decoder's beam search is the mode 'attention_beam_search'")
             else:
                 raise NotImplementedError(f"decode mode {m!r} is outside the accelerated path")
         if "rnnt_beam_search" in methods:

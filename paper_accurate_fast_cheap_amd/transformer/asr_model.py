@@ -109,15 +109,20 @@ class ASRModel(torch.nn.Module):
                decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0,
                simulate_streaming: bool = False, reverse_weight: float = 0.0, blank_id: int = 0,
                blank_penalty: float = 0.0, cat_embs: Optional[torch.Tensor] = None, context_graph=None,
-               score_backend: Optional[str] = None, **_ignored) -> Dict[str, List[DecodeResult]]:
+               score_backend: Optional[str] = None, length_penalty: float = 0.0, **_ignored
+               ) -> Dict[str, List[DecodeResult]]:
         """"attention_rescoring" (a model with an attention decoder): first pass ctc_prefix_beam_search (computed once when that
         mode is requested too), final_i = attn_i + ctc_weight * ctc_score_i with attn_i of score_attention (backend:
-        score_backend) and reverse_weight; the n-best lists come back re-ordered by final (attn_rescore.attention_rescore)."""
+        score_backend) and reverse_weight; the n-best lists come back re-ordered by final (attn_rescore.attention_rescore).
+        "attention_beam_search" (likewise): the decoder's own autoregressive beam search with length_penalty
+        (attn_search.attention_beam_search, backend: score_backend) -- the reference's mode "attention", a spelling that is still
+        refused here."""
         assert speech.shape[0] == speech_lengths.shape[0]
         rescoring = "attention_rescoring" in methods
-        if rescoring and self.decoder is None:
-            raise NotImplementedError("decode mode 'attention_rescoring' needs an attention decoder (init_model builds one "
-                                      "with args.attention_decoder)")
+        for m in ("attention_rescoring", "attention_beam_search"):
+            if m in methods and self.decoder is None:
+                raise NotImplementedError(f"decode mode {m!r} needs an attention decoder (init_model builds one "
+                                          "with args.attention_decoder)")
         encoder_out, encoder_mask = self._forward_encoder(speech, speech_lengths, decoding_chunk_size,
                                                           num_decoding_left_chunks, simulate_streaming, cat_embs)
         encoder_lens = encoder_mask.squeeze(1).sum(1)
@@ -132,6 +137,12 @@ class ASRModel(torch.nn.Module):
             elif m == "ctc_prefix_beam_search":
                 from .search import ctc_prefix_beam_search
                 results[m] = ctc_prefix_beam_search(ctc_probs, encoder_lens, beam_size, context_graph, blank_id)
+            elif m == "attention_beam_search":
+                from .attn_search import attention_beam_search
+                results[m] = attention_beam_search(self, encoder_out, encoder_mask, beam_size, length_penalty, score_backend)
+            elif m == "attention":
+                raise NotImplementedError("decode mode 'attention' is not accepted under the reference's name: the attention "
+                                          "decoder's beam search is the mode 'attention_beam_search'")
             else:
                 raise NotImplementedError(f"decode mode {m!r} is outside the accelerated path")
         if rescoring:

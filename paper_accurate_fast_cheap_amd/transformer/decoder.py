@@ -5,7 +5,7 @@ bitransformer`).  Parameter names and constructor keys are upstream's, so refere
   decoders.N.feed_forward.w_{1,2}.*, decoders.N.norm{1,2,3}.*, after_norm.*, output_layer.*
 These modules are the definition and the "framework" backend of ASRModel.score_attention; on the GPU the second pass runs
 the same weights over packed rows through the library's kernels (transformer/attn_rescore.py)."""
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -65,6 +65,22 @@ class TransformerDecoder(torch.nn.Module):
             x = self.output_layer(x)
         return x, torch.tensor(0.0), tgt_mask.sum(1)
 
+    def forward_one_step(self, memory: torch.Tensor, memory_mask: torch.Tensor, tgt: torch.Tensor, tgt_mask: torch.Tensor,
+                         cache: Optional[List[torch.Tensor]] = None) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """One step of autoregressive decoding (upstream's method, which search.py:304 of the reference calls): tgt (B, L)
+        the prefixes, tgt_mask (B, L, L), cache the per-layer outputs (B, L - 1, D) of the previous step or None ->
+        (log p(next token | prefix) (B, V), the per-layer outputs (B, L, D)).  With a cache a layer computes its last row
+        only."""
+        x, _ = self.embed(tgt)
+        new_cache = []
+        for i, layer in enumerate(self.decoders):
+            x, tgt_mask, memory, memory_mask = layer(x, tgt_mask, memory, memory_mask, cache=None if cache is None else cache[i])
+            new_cache.append(x)
+        y = self.after_norm(x[:, -1]) if self.normalize_before else x[:, -1]
+        if self.use_output_layer:
+            y = torch.log_softmax(self.output_layer(y), dim=-1)
+        return y, new_cache
+
 
 class BiTransformerDecoder(torch.nn.Module):
     def __init__(self, vocab_size: int, encoder_output_size: int, attention_heads: int = 4, linear_units: int = 2048,
@@ -83,6 +99,11 @@ class BiTransformerDecoder(torch.nn.Module):
         if reverse_weight > 0.0:
             r_x, _, olens = self.right_decoder(memory, memory_mask, r_ys_in_pad, ys_in_lens)
         return l_x, r_x, olens
+
+    def forward_one_step(self, memory: torch.Tensor, memory_mask: torch.Tensor, tgt: torch.Tensor, tgt_mask: torch.Tensor,
+                         cache: Optional[List[torch.Tensor]] = None) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """The left decoder's step: hypotheses grow left to right."""
+        return self.left_decoder.forward_one_step(memory, memory_mask, tgt, tgt_mask, cache)
 
 
 DECODER_CLASSES = {"transformer": TransformerDecoder, "bitransformer": BiTransformerDecoder}

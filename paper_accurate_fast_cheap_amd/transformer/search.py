@@ -13,7 +13,8 @@ class DecodeResult:
     def __init__(self, tokens: List[int], score: float = 0.0, confidence: float = 0.0, tokens_confidence=None,
                  times=None, nbest: Optional[List[List[int]]] = None, nbest_scores: Optional[List[float]] = None,
                  nbest_times=None, end_times=None, tokens_info=None, ok: bool = True,
-                 nbest_td_scores: Optional[List[float]] = None, nbest_attn_scores: Optional[List[float]] = None):
+                 nbest_td_scores: Optional[List[float]] = None, nbest_attn_scores: Optional[List[float]] = None,
+                 stats: Optional[dict] = None, trace: Optional[dict] = None):
         self.tokens = tokens
         self.score = score
         self.confidence = confidence
@@ -27,6 +28,8 @@ class DecodeResult:
         self.ok = ok                        # forced alignment: False when the labels cannot be aligned to the frames
         self.nbest_td_scores = nbest_td_scores    # transducer rescoring: log p(y | x) of every entry of nbest, in its order
         self.nbest_attn_scores = nbest_attn_scores    # attention rescoring: the attention decoder's score of every entry of nbest
+        self.stats = stats                  # attention beam search, kernels backend: steps, host reads, launches per step
+        self.trace = trace                  # attention beam search with return_trace: parent / token / score per step and slot
 
 
 def log_add(args: List[float]) -> float:
