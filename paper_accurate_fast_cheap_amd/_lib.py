@@ -70,6 +70,11 @@ SIGNATURES = {
     "pafc_mha_step": (I, [I, I, I, I, I, I, P, G, P, P, P, P, P, G, P]),
     "pafc_attn_beam_select_workspace_bytes": (Z, [I, I]),
     "pafc_attn_beam_select": (I, [I, I, I, I, I, I, I, P, G, P, P, P, P, P, P, P, P, P, P, Z, P]),
+    # include/pafc_joint_search.h
+    "pafc_mha_step_paths": (I, [I, I, I, I, I, I, P, G, P, P, G, P, P, P, P, G, P]),
+    "pafc_joint_candidates": (I, [I, I, I, I, I, I, F, P, P, P, P, P, P, P]),
+    "pafc_joint_frame": (I, [P, I, I, I, P, G, P, P, I, P]),
+    "pafc_joint_collect": (I, [P, P, P, P, P, P, P, P]),
     # include/pafc_encoder_ops.h
     "pafc_dwconv1d_cl": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P]),
     "pafc_dwconv1d_cl_ex": (I, [I, I, I, I, I, I, I, P, G, P, P, P, I, P, P]),

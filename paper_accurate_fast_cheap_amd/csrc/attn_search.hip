@@ -1,6 +1,6 @@
 // attn_search.hip -- the two kernels of the attention decoder's beam search (include/pafc_attn_search.h).
 //
-// mha_step_kernel: one wave per (row, head).  A step's self-attention is a GEMV per (row, head) over at most P keys of 64
+// mha_step_kernel: one wave per (row, head); its body is mha_step_body.h, shared with pafc_mha_step_paths.  A step's self-attention is a GEMV per (row, head) over at most P keys of 64
 // dimensions, bound by the reads of the cache: nothing for the matrix cores.  QK runs with the lanes over the keys of a tile
 // of 64 (a lane reads its key's 64 contiguous elements as 16-byte accesses and holds q in registers), the online softmax
 // merges a tile with two wave reductions, and PV runs with the lanes over the 64 dimensions (one coalesced row segment per
@@ -10,21 +10,13 @@
 // over the elements that come after the previous pass's winner in the order (value descending, index ascending): exact
 // ties go to the lowest index without an exclusion list, and a NaN is never selected.
 #include "pafc_attn_search.h"
-#include "pafc_common.h"
+#include "mha_step_body.h"
 
 #include <math.h>
 
 namespace pafc {
 
-constexpr int kStepDk = 64;
-constexpr int kStepWaves = 4;
 constexpr int kMaxBeam = 16;
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, kWave));
-    return x;
-}
 
 struct StepArgs {
     int R, N, H, P;
@@ -44,52 +36,12 @@ template <typename ET> __global__ __launch_bounds__(kStepWaves * kWave) void mha
     const long d = (long)a.H * kStepDk;
     const ET *qkv = static_cast<const ET *>(a.qkv) + (long)r * a.ldqkv;
     ET *cache = static_cast<ET *>(a.cache);
-    const ET *own_k = qkv + d + h * kStepDk, *own_v = qkv + 2 * d + h * kStepDk;
-    // the row's own slot: k and v of this head, one element per lane
-    ET *slot = cache + ((long)p * a.R + r) * 2 * d + h * kStepDk;
-    slot[lane] = own_k[lane];
-    slot[d + lane] = own_v[lane];
-    float q[kStepDk];
-#pragma unroll
-    for (int i = 0; i < kStepDk; i += 8) load8<ET>(qkv + h * kStepDk + i, q + i);
     const int32_t *anc = a.anc + ((long)(p & 1) * a.R + r) * a.P;
-    const int base = (r / a.N) * a.N;
-    float m = -INFINITY, l = 0.f, acc = 0.f;
-    for (int j0 = 0; j0 <= p; j0 += kWave) {
-        const int j = j0 + lane;
-        const bool valid = j <= p;
-        // the cache row of key j (keys of earlier positions through the ancestor table; key p is read from qkv: the slot
-        // above was written by other lanes of this launch)
-        int row = -1;                                       // (P * R fits an int: checked before the launch)
-        if (valid && j < p) row = j * a.R + base + min(max(anc[j], 0), a.N - 1);
-        float s = -INFINITY;
-        if (valid) {
-            const ET *kr = row >= 0 ? cache + (long)row * 2 * d + h * kStepDk : own_k;
-            float dot = 0.f;
-#pragma unroll
-            for (int i = 0; i < kStepDk; i += 8) {
-                float kk[8];
-                load8<ET>(kr + i, kk);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) dot = fmaf(q[i + e], kk[e], dot);
-            }
-            s = dot * 0.125f;
-        }
-        const float m_new = fmaxf(m, wave_max(s));          // finite: lane 0 of every tile is valid
-        const float pj = valid ? expf(s - m_new) : 0.f;
-        const float scale = expf(m - m_new);                // 0 on the first tile (m = -inf)
-        l = l * scale + wave_sum(pj);
-        acc *= scale;
-        const int n = min(kWave, p + 1 - j0);
-        for (int jj = 0; jj < n; ++jj) {
-            const float pb = __shfl(pj, jj, kWave);
-            const int rb = __shfl(row, jj, kWave);
-            const ET *vr = rb >= 0 ? cache + (long)rb * 2 * d + d + h * kStepDk : own_v;
-            acc = fmaf(pb, Elem<ET>::load(vr + lane), acc);
-        }
-        m = m_new;
-    }
-    Elem<ET>::store(static_cast<ET *>(a.out) + (long)r * a.ldo + h * kStepDk + lane, acc / l);
+    const int base = (r / a.N) * a.N, R = a.R, N = a.N;
+    // the cache row of key j < p through the ancestor table     (P * R fits an int: checked before the launch)
+    mha_step_row<ET>(qkv, cache, d, h, lane, p, cache + ((long)p * a.R + r) * 2 * d,
+                     [=](int j) { return j * R + base + min(max(anc[j], 0), N - 1); },
+                     static_cast<ET *>(a.out) + (long)r * a.ldo);
 }
 
 // ---- selection ----

@@ -3857,3 +3857,140 @@ def attn_beam_select(logits: torch.Tensor, beam: int, eos: int, cap: int, score:
                                           _lib.ptr(done), _lib.ptr(workspace), workspace.numel() * workspace.element_size(),
                                           _lib.stream_of(logits))
     _lib.check(rc, "pafc_attn_beam_select")
+
+
+# ---- joint CTC/attention decoding (include/pafc_joint_search.h, csrc/joint_search.hip) -------------------------------------
+def mha_step_paths(qkv: torch.Tensor, cache: torch.Tensor, path: torch.Tensor, length: torch.Tensor, new_row: torch.Tensor,
+                   need: torch.Tensor, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Single-query self-attention of R rows at different positions through per-row tables of cache rows
+    (pafc_mha_step_paths).  qkv (R, >= 3 * H * 64) the stacked q | k | v projection, fp32 or bf16, unit stride along the columns;
+    cache (rows, 2 * H * 64) contiguous in qkv's dtype; path (R, W) int32: row r of length[r] attends over the cache rows
+    path[r, 0 .. length[r] - 2] and its own k, v, and stores its k | v into cache row new_row[r] iff need[r].  A row with
+    need == 0 writes nothing to the cache; its out row is computed all the same and is meant to be discarded.  Table entries
+    outside the cache are clamped into it.  Returns out (R, H * 64)."""
+    d = heads * 64
+    if not qkv.is_cuda or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[1] < 3 * d:
+        raise _lib.PafcError("mha_step_paths: qkv is a 2-D GPU tensor of at least 3 * H * 64 columns with unit stride along them")
+    R = qkv.shape[0]
+    if not cache.is_cuda or cache.dtype != qkv.dtype or cache.dim() != 2 or not cache.is_contiguous() or cache.shape[1] != 2 * d \
+            or cache.shape[0] < 1:
+        raise _lib.PafcError("mha_step_paths: cache is (rows, 2 * H * 64), contiguous, in qkv's dtype")
+    _i32_gpu("mha_step_paths", path=path, length=length, new_row=new_row, need=need)
+    if path.dim() != 2 or path.shape[0] != R or path.shape[1] < 1 or length.numel() != R or new_row.numel() != R \
+            or need.numel() != R:
+        raise _lib.PafcError("mha_step_paths: path is (R, W), length / new_row / need hold R int32 each")
+    if out is None:
+        out = torch.empty(R, d, dtype=qkv.dtype, device=qkv.device)
+    elif not out.is_cuda or out.dtype != qkv.dtype or out.dim() != 2 or out.stride(1) != 1 or out.shape != (R, d):
+        raise _lib.PafcError("mha_step_paths: out is (R, H * 64) in qkv's dtype")
+    rc = _lib.lib().pafc_mha_step_paths(_lib.dtype_code(qkv.dtype), R, heads, 64, cache.shape[0], path.shape[1], _lib.ptr(qkv),
+                                        qkv.stride(0), _lib.ptr(cache), _lib.ptr(path), path.stride(0), _lib.ptr(length),
+                                        _lib.ptr(new_row), _lib.ptr(need), _lib.ptr(out), out.stride(0), _lib.stream_of(qkv))
+    _lib.check(rc, "pafc_mha_step_paths")
+    return out
+
+
+class _JointStateStruct(ctypes.Structure):
+    """pafc_joint_state of include/pafc_joint_search.h, field for field."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "N", "C", "T", "M", "HS")] + [(n, ctypes.c_void_p) for n in (
+        "parent", "token", "length", "start", "end", "snap_end", "ctc_conf", "snap_ctc_conf", "att_conf", "att_sum", "lse", "row",
+        "p_nb", "p_b", "stamp", "hash_key", "hash_node", "n_nodes", "executed", "nlive", "evals", "node", "need", "in_token",
+        "in_pos", "in_len", "new_row", "row_of_slot", "store_row", "score", "path", "cand_tok", "cand_p", "p_blank", "skip",
+        "trace_node", "trace_score", "trace_exec")]
+
+
+class JointSearchState:
+    """The device state of one joint_decoding call (pafc_joint_state): the tensors by name, in their initial values, and the
+    struct that the kernels take.  B utterances, beam N, C candidates per frame, T frames; decode: whether the decoder runs
+    (dec_w > 0: slot 0 of every utterance then asks for round 0's decode of [sos])."""
+
+    def __init__(self, B: int, N: int, C: int, T: int, sos: int, device, decode: bool = True):
+        if not (1 <= N <= 16 and 1 <= C <= 24 and B >= 1 and T >= 1):
+            raise _lib.PafcError(f"joint search: {B} utterances, a beam of {N} (1..16), {C} candidates per frame (1..24), {T} frames")
+        M = 1 + T * N * C
+        HS = 1 << (2 * M - 1).bit_length()
+        R = B * N
+        if (T + 2) * R > 0x7fffffff:
+            raise _lib.PafcError(f"joint search: {(T + 2) * R} cache rows do not fit an int32")
+        self.B, self.N, self.C, self.T, self.M, self.HS, self.R = B, N, C, T, M, HS, R
+        i32 = lambda *shape, fill=0: torch.full(shape, fill, dtype=torch.int32, device=device)                 # noqa: E731
+        f64 = lambda *shape, fill=0.0: torch.full(shape, fill, dtype=torch.float64, device=device)             # noqa: E731
+        f32 = lambda *shape, fill=0.0: torch.full(shape, fill, dtype=torch.float32, device=device)             # noqa: E731
+        inf = float("inf")
+        t = self.t = dict(
+            parent=i32(B, M, fill=-1), token=i32(B, M), length=i32(B, M), start=i32(B, M), end=i32(B, M), snap_end=i32(B, M),
+            ctc_conf=f32(B, M, fill=-inf), snap_ctc_conf=f32(B, M, fill=-inf), att_conf=f64(B, M, fill=-inf), att_sum=f64(B, M),
+            lse=f64(B, M, fill=float("nan")), row=i32(B, M, fill=-1), p_nb=f64(2, B, M, fill=-inf), p_b=f64(2, B, M, fill=-inf),
+            stamp=i32(2, B, M, fill=-1), hash_key=torch.full((B, HS), -1, dtype=torch.int64, device=device), hash_node=i32(B, HS),
+            n_nodes=i32(B, fill=1), executed=i32(B), nlive=i32(B, fill=1), evals=i32(B, fill=1 if decode else 0),
+            node=i32(R, fill=-1), need=i32(R), in_token=i32(R), in_pos=i32(R), in_len=i32(R, fill=1), new_row=i32(R),
+            row_of_slot=i32(R), store_row=i32(R, fill=(T + 1) * R), score=f64(R), path=i32(R, T + 1),
+            cand_tok=i32(B, T, C, fill=-1), cand_p=f32(B, T, C, fill=-inf), p_blank=f32(B, T, fill=-inf), skip=i32(B, T),
+            trace_node=i32(T, R, fill=-1), trace_score=f64(T, R), trace_exec=i32(T, B, fill=-1))
+        # node 0 of every utterance is [sos], in the table of "frame 0" at (p_nb, p_b) = (-inf, 0); it sits in slot 0
+        t["token"][:, 0].fill_(sos)
+        t["length"][:, 0].fill_(1)
+        t["p_b"][0, :, 0].fill_(0.0)
+        t["stamp"][0, :, 0].fill_(0)
+        first = lambda name: t[name].view(B, N)[:, 0]              # slot 0 of every utterance               # noqa: E731
+        first("node").fill_(0)
+        first("in_token").fill_(sos)
+        if decode:
+            rows = torch.arange(0, R, N, dtype=torch.int32, device=device)
+            first("need").fill_(1)
+            for name in ("new_row", "store_row", "row_of_slot"):
+                first(name).copy_(rows)
+            t["row"][:, 0].copy_(rows)
+        self.struct = _JointStateStruct(B, N, C, T, M, HS, **{k: v.data_ptr() for k, v in t.items()})
+
+    def __getattr__(self, name):
+        try:
+            return self.__dict__["t"][name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def joint_candidates(state: JointSearchState, ctc: torch.Tensor, lens: torch.Tensor, blank: int, log_threshold: float) -> None:
+    """The candidates of every frame into state.cand_tok / cand_p / p_blank / skip (pafc_joint_candidates): ctc (B, T, V) fp32
+    or bf16 contiguous on the GPU, lens (B) int32 on the GPU."""
+    _lib.require_gpu(ctc)
+    _i32_gpu("joint_candidates", lens=lens)
+    if ctc.dim() != 3 or ctc.shape[:2] != (state.B, state.T) or lens.numel() != state.B:
+        raise _lib.PafcError(f"joint_candidates: ctc {tuple(ctc.shape)} / lens for a state of {state.B} x {state.T} frames")
+    rc = _lib.lib().pafc_joint_candidates(_lib.dtype_code(ctc.dtype), state.B, state.T, ctc.shape[2], state.C, blank,
+                                          log_threshold, _lib.ptr(ctc), _lib.ptr(lens), _lib.ptr(state.cand_tok),
+                                          _lib.ptr(state.cand_p), _lib.ptr(state.p_blank), _lib.ptr(state.skip),
+                                          _lib.stream_of(ctc))
+    _lib.check(rc, "pafc_joint_candidates")
+
+
+def joint_frame(state: JointSearchState, t: int, logits: Optional[torch.Tensor], V: int, lens: torch.Tensor, ctc_w: float,
+                dec_w: float, bonus: float, blank: int) -> None:
+    """Frame t of the search for every utterance (pafc_joint_frame): logits (R, >= V) fp32 or bf16 with unit stride along the
+    vocabulary, row r the output_layer row of slot r's prefix (None with dec_w == 0); everything else is in `state`."""
+    _i32_gpu("joint_frame", lens=lens)
+    if logits is not None and (not logits.is_cuda or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != state.R
+                               or logits.shape[1] < V):
+        raise _lib.PafcError("joint_frame: logits are (R, >= V) on the GPU with unit stride along the vocabulary")
+    if logits is None and dec_w > 0:
+        raise _lib.PafcError("joint_frame: dec_w > 0 needs the logits")
+    weights = (ctypes.c_double * 3)(ctc_w, dec_w, bonus)
+    rc = _lib.lib().pafc_joint_frame(ctypes.byref(state.struct), t, _lib.dtype_code(logits.dtype) if logits is not None else 0, V,
+                                     _lib.ptr(logits), logits.stride(0) if logits is not None else 0, _lib.ptr(lens), weights,
+                                     blank, _lib.stream_of(lens))
+    _lib.check(rc, "pafc_joint_frame")
+
+
+def joint_collect(state: JointSearchState) -> dict:
+    """The beams' hypotheses in compact form (pafc_joint_collect): dict(len (R), tok / start / end (R, T + 1) int32, ctc_conf
+    (R, T + 1) float32, att_conf (R, T + 1) float64), on the device."""
+    dev, R, W = state.node.device, state.R, state.T + 1
+    out = dict(len=torch.zeros(R, dtype=torch.int32, device=dev), tok=torch.zeros(R, W, dtype=torch.int32, device=dev),
+               start=torch.zeros(R, W, dtype=torch.int32, device=dev), end=torch.zeros(R, W, dtype=torch.int32, device=dev),
+               ctc_conf=torch.zeros(R, W, dtype=torch.float32, device=dev),
+               att_conf=torch.zeros(R, W, dtype=torch.float64, device=dev))
+    rc = _lib.lib().pafc_joint_collect(ctypes.byref(state.struct), _lib.ptr(out["len"]), _lib.ptr(out["tok"]),
+                                       _lib.ptr(out["start"]), _lib.ptr(out["end"]), _lib.ptr(out["ctc_conf"]),
+                                       _lib.ptr(out["att_conf"]), _lib.stream_of(state.node))
+    _lib.check(rc, "pafc_joint_collect")
+    return out

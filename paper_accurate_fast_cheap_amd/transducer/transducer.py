@@ -309,6 +309,8 @@ class Transducer(ASRModel):
         "attention_beam_search" (likewise a model with an attention decoder): the decoder's own autoregressive beam search with
           length_penalty (attn_search.attention_beam_search, backend: score_backend); the reference's spelling "attention" is
           still refused.
+        "joint_decoding" (likewise): the time-synchronous joint CTC/attention beam search (joint_search.joint_decoding) with
+          ctc_weight, beam_size and length_bonus = length_penalty; backend: score_backend; cat_embs must be None for it.
         Two-pass modes without it (a non-zero reverse_weight or attn_weight with them is a ValueError):
           "ctc_beam_td_rescoring": first pass ctc_prefix_beam_search (computed once when that mode is requested too);
           "rnnt_beam_td_rescoring": first pass beam_search_decode with search_ctc_weight / search_transducer_weight -- the
@@ -322,7 +324,7 @@ class Transducer(ASRModel):
                              "the attention decoder was not released with the reference, so this mode has no attention term to "
                              "weigh; ctc_beam_td_attn_rescoring / rnnt_beam_attn_rescoring of a model built with an attention "
                              "decoder have one")
-        with_attn = [m for m in methods if m in ATTN_RESCORING_MODES + ("attention_beam_search",)]
+        with_attn = [m for m in methods if m in ATTN_RESCORING_MODES + ("attention_beam_search", "joint_decoding")]
         if with_attn and self.decoder is None:
             raise NotImplementedError(f"decode mode {with_attn[0]!r} needs an attention decoder (init_model builds one with "
                                       "args.attention_decoder)")
@@ -346,6 +348,11 @@ class Transducer(ASRModel):
             elif m == "attention_beam_search":
                 from ..transformer.attn_search import attention_beam_search
                 results[m] = attention_beam_search(self, encoder_out, encoder_mask, beam_size, length_penalty, score_backend)
+            elif m == "joint_decoding":
+                from ..transformer.joint_search import joint_decoding
+                results[m] = joint_decoding(self, encoder_out, encoder_lens, ctc_probs, ctc_weight, beam_size,
+                                            length_bonus=length_penalty, blank_id=blank_id, backend=score_backend,
+                                            cat_embs=cat_embs)
             elif m == "attention":
                 raise NotImplementedError("decode mode 'attention' is not accepted under the reference's name: the attention "
                                           "decoder's beam search is the mode 'attention_beam_search'")

@@ -116,10 +116,13 @@ class ASRModel(torch.nn.Module):
         score_backend) and reverse_weight; the n-best lists come back re-ordered by final (attn_rescore.attention_rescore).
         "attention_beam_search" (likewise): the decoder's own autoregressive beam search with length_penalty
         (attn_search.attention_beam_search, backend: score_backend) -- the reference's mode "attention", a spelling that is still
-        refused here."""
+        refused here.
+        "joint_decoding" (likewise): the time-synchronous joint CTC/attention beam search (joint_search.joint_decoding) with
+        ctc_weight, beam_size and length_bonus = length_penalty, as the reference maps them; backend: score_backend; cat_embs
+        must be None for it."""
         assert speech.shape[0] == speech_lengths.shape[0]
         rescoring = "attention_rescoring" in methods
-        for m in ("attention_rescoring", "attention_beam_search"):
+        for m in ("attention_rescoring", "attention_beam_search", "joint_decoding"):
             if m in methods and self.decoder is None:
                 raise NotImplementedError(f"decode mode {m!r} needs an attention decoder (init_model builds one "
                                           "with args.attention_decoder)")
@@ -140,6 +143,11 @@ class ASRModel(torch.nn.Module):
             elif m == "attention_beam_search":
                 from .attn_search import attention_beam_search
                 results[m] = attention_beam_search(self, encoder_out, encoder_mask, beam_size, length_penalty, score_backend)
+            elif m == "joint_decoding":
+                from .joint_search import joint_decoding
+                results[m] = joint_decoding(self, encoder_out, encoder_lens, ctc_probs, ctc_weight, beam_size,
+                                            length_bonus=length_penalty, blank_id=blank_id, backend=score_backend,
+                                            cat_embs=cat_embs)
             elif m == "attention":
                 raise NotImplementedError("decode mode 'attention' is not accepted under the reference's name: the attention "
                                           "decoder's beam search is the mode 'attention_beam_search'")
