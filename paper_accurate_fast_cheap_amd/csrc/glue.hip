@@ -349,11 +349,52 @@ __global__ __launch_bounds__(256) void tmix_lora_mix4_kernel(int T, int C, long 
 }
 
 
+// In-kernel cycle stamps of the three LDS-/register-resident front-end kernels below, for tools/micro/tmix_front_stamps.cpp only
+// (-DPAFC_TMIX_STAMPS): per wave and trip {tile start, cycles between "loads issued" and "first use of loaded data" (summed
+// over the K groups of tmix_lora_down), arithmetic done, stores issued}, written by lane 0 with ordinary stores into a buffer
+// nothing else reads.  The library build defines none of this.
+#ifdef PAFC_TMIX_STAMPS
+constexpr int TMIX_STAMP_TRIPS = 8;
+__device__ unsigned long long *g_tmix_stamps;     // [wave][TMIX_STAMP_TRIPS][4]
+__device__ long g_tmix_stamp_waves;               // waves the buffer has room for
+__device__ __forceinline__ unsigned long long tmix_clk() {
+    asm volatile("" ::: "memory");
+    const unsigned long long c = __builtin_amdgcn_s_memtime();
+    asm volatile("" ::: "memory");
+    return c;
+}
+#define TMIX_ST_DECL unsigned long long st_t0 = 0, st_wait = 0, st_ar = 0, st_c = 0; int st_trip = 0;
+#define TMIX_ST_START do { st_t0 = tmix_clk(); st_wait = 0; } while (0)
+#define TMIX_ST_WAIT0 do { st_c = tmix_clk(); } while (0)
+#define TMIX_ST_WAIT1(v) do { asm volatile("" ::"v"(v)); st_wait += tmix_clk() - st_c; } while (0)
+#define TMIX_ST_ARITH do { st_ar = tmix_clk(); } while (0)
+#define TMIX_ST_END(wg)                                                                                                  \
+    do {                                                                                                                 \
+        const unsigned long long st_e = tmix_clk();                                                                      \
+        if ((threadIdx.x & 63) == 0 && st_trip < TMIX_STAMP_TRIPS && (long)(wg) < g_tmix_stamp_waves) {                  \
+            unsigned long long *st_p = g_tmix_stamps + ((size_t)(wg) * TMIX_STAMP_TRIPS + st_trip) * 4;                  \
+            st_p[0] = st_t0; st_p[1] = st_wait; st_p[2] = st_ar; st_p[3] = st_e;                                          \
+        }                                                                                                                \
+        ++st_trip;                                                                                                       \
+    } while (0)
+#else
+#define TMIX_ST_DECL
+#define TMIX_ST_START do {} while (0)
+#define TMIX_ST_WAIT0 do {} while (0)
+#define TMIX_ST_WAIT1(v) do {} while (0)
+#define TMIX_ST_ARITH do {} while (0)
+#define TMIX_ST_END(wg) do {} while (0)
+#endif
+
 // Weight-stationary form of tmix_lora_mix4_kernel: a block keeps ONE 64-column slice of W2 and maa of ONE direction in
 // registers (16 MFMA A fragments + the lerp coefficients) and walks over row tiles with it, so the weights are read from L2
 // once per block instead of once per 16 rows (720 MB of fragment reads per layer at the 30-minute shape otherwise).
 // grid = (G, C / 64, ndir); a wave takes the 16-row tiles blockIdx.x * 4 + wave, + 4 G, ...
-template <int NW, int WCOLS>   // waves per block; how many of them sit side by side on one row tile (adjacent 64-column slices)
+// PIPE: the eight 16-byte loads of the wave's NEXT tile run under this tile's arithmetic and stores: x and its neighbour row
+// (2 each) are issued before the q loop, once this tile's have been unpacked, and t of map q into the registers of this tile's
+// t of map q right after the products that consumed them -- a second full register set costs <4, 4> and, with stamps, <4, 1>
+// an occupancy step (PAFC_TMIX_PIPE=0: the plain loop).
+template <int NW, int WCOLS, bool PIPE = true>   // waves per block; how many of them sit side by side on one row tile (adjacent 64-column slices)
 __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C, long rows, int ndir, int rev0,
                                                                 const bf16_t *__restrict__ x, const bf16_t *__restrict__ t,
                                                                 const bf16_t *__restrict__ w2t,
@@ -380,28 +421,56 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
             a2[q][cbi] = *reinterpret_cast<const uint4 *>(wq + 4 * 32);
             av[q][cbi] = *reinterpret_cast<const uint4 *>(maa + ((size_t)d * 4 + q) * C + cb * 32 + 8 * qq);
         }
-    const long ntiles = (rows + 15) / 16;
-    for (long tile = (long)blockIdx.x * WROWS + wrow; tile < ntiles; tile += (long)gridDim.x * WROWS) {
-        const long row = tile * 16 + r16;
+    const long ntiles = (rows + 15) / 16, tstride = (long)gridDim.x * WROWS;
+    // the loads of one row tile, as they arrive: its x and neighbour-row pieces, and the lane's row of t (the four maps' pieces
+    // are read from there); only ever formed for a tile < ntiles, rows clamped to rows - 1
+    auto issue_x = [&](long tl, uint4(&xo)[2], uint4(&xn)[2], bool &has_nb, const bf16_t *&trow) {
+        const long row = tl * 16 + r16;
         const long rowc = row < rows ? row : rows - 1;     // clamp (every lane takes part in the MFMAs), skip the store
         const int tt = (int)(rowc % T);
         const bool in_seq = rev ? (tt < T - 1) : (tt > 0);
-        const bool has_nb = in_seq || (prev != nullptr && !rev);       // prev: (B, C) the frame before each sequence, or null
+        has_nb = in_seq || (prev != nullptr && !rev);       // prev: (B, C) the frame before each sequence, or null
         const bf16_t *nbrow = in_seq ? x + (rev ? rowc + 1 : rowc - 1) * C : (has_nb ? prev + (rowc / T) * C : x + rowc * C);
-        uint4 tb[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            tb[q] = *reinterpret_cast<const uint4 *>(t + ((size_t)d * rows + rowc) * 128 + 32 * q + 8 * qq);
-        float xc[2][VEC], xx[2][VEC];
+        trow = t + ((size_t)d * rows + rowc) * 128 + 8 * qq;
 #pragma unroll
         for (int cbi = 0; cbi < 2; ++cbi) {
             const int col = (cy * 2 + cbi) * 32 + 8 * qq;
+            xo[cbi] = *reinterpret_cast<const uint4 *>(x + rowc * C + col);
+            xn[cbi] = *reinterpret_cast<const uint4 *>(nbrow + col);
+        }
+    };
+    uint4 tb[4], lxo[2], lxn[2];        // the loads in flight: of this tile (plain loop), of the next one (PIPE)
+    bool lhas = false;
+    const bf16_t *trow = t;
+    TMIX_ST_DECL
+    long tile = (long)blockIdx.x * WROWS + wrow;
+    if (PIPE && tile < ntiles) {
+        issue_x(tile, lxo, lxn, lhas, trow);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) tb[q] = *reinterpret_cast<const uint4 *>(trow + 32 * q);
+    }
+    for (; tile < ntiles; tile += tstride) {
+        TMIX_ST_START;
+        if (!PIPE) {
+            issue_x(tile, lxo, lxn, lhas, trow);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tb[q] = *reinterpret_cast<const uint4 *>(trow + 32 * q);
+        }
+        TMIX_ST_WAIT0;
+        TMIX_ST_WAIT1(lxo[0].x);
+        const bool has_nb = lhas;
+        float xc[2][VEC], xx[2][VEC];
+#pragma unroll
+        for (int cbi = 0; cbi < 2; ++cbi) {
             float xn[VEC];
-            load8<bf16_t>(x + rowc * C + col, xc[cbi]);
-            load8<bf16_t>(nbrow + col, xn);
+            Elem<bf16_t>::unpack(lxo[cbi], xc[cbi]);
+            Elem<bf16_t>::unpack(lxn[cbi], xn);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) xx[cbi][e] = round_bf16((has_nb ? xn[e] : 0.f) - xc[cbi][e]);
         }
+        const bool more = PIPE && tile + tstride < ntiles;      // wave-uniform: a whole wave has a next tile or none
+        if (more) issue_x(tile + tstride, lxo, lxn, lhas, trow);
+        TMIX_ST_ARITH;      // (operands formed; the q loop interleaves products, re-layout and stores)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -418,6 +487,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
                 }
                 store8<bf16_t>(&s_z[wave][r16][cbi * 32 + 8 * qq], o);
             }
+            if (more) tb[q] = *reinterpret_cast<const uint4 *>(trow + 32 * q);      // this tile's tb[q] is dead: the next tile's
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -431,6 +501,7 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
+        TMIX_ST_END(((long)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * NW + wave);
     }
 }
 
@@ -445,6 +516,12 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_mix4_ws_kernel(int T, int C
 // for 206 MB at the 30-minute shape).
 constexpr int DL_C = 512, DL_H = 64;      // model width and LoRA width this kernel is built for (checked on the host)
 constexpr int DL_WAVES = 8;
+// PIPE: the sixteen z_w fragments are dead once the first product has consumed them, so the next tile's sixteen loads go into
+// those same registers right after it and run under the tanh, the second product and the store loop (PAFC_TMIX_PIPE=0: the
+// plain loop, which loads at the top of each tile).  time_decay of the block's direction (1 KiB) then sits in LDS behind the
+// per-wave tiles: a global load of it inside the store loop would make the wave wait for every prefetched load issued before it
+// (the vector-memory counter is in order).
+template <bool PIPE = true>
 __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, int ndir, const bf16_t *__restrict__ zw,
                                                                    const bf16_t *__restrict__ d1n,
                                                                    const bf16_t *__restrict__ d2n,
@@ -458,6 +535,7 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
     uint4 *s_d1 = reinterpret_cast<uint4 *>(dl_lds);                       // [ks 16][tau 4][lane 64]   64 KiB
     uint4 *s_d2 = s_d1 + 16 * 4 * 64;                                      // [cb 16][a 2][p 2][lane 64] 64 KiB
     bf16_t(*s_z)[16][LDZ] = reinterpret_cast<bf16_t(*)[16][LDZ]>(s_d2 + 16 * 2 * 2 * 64);   // [wave][row][col]
+    bf16_t *s_bias = &s_z[DL_WAVES][0][0];                                 // PIPE: time_decay of my direction, 1 KiB
     const int colslot = 8 * (r16 >> 2) + (r16 & 3);   // column (in a 32-block) whose weight row this lane feeds as MFMA row r16
     const long ntiles = (rows + 15) / 16;
     {
@@ -472,20 +550,34 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
             const uint2 lo = *reinterpret_cast<const uint2 *>(dq), hi = *reinterpret_cast<const uint2 *>(dq + 16);
             s_d2[f * 64 + lane] = uint4{lo.x, lo.y, hi.x, hi.y};
         }
-        __syncthreads();
-        for (long tile = (long)blockIdx.x * DL_WAVES + wave; tile < ntiles; tile += (long)gridDim.x * DL_WAVES) {
-            const long row = tile * 16 + r16;
+        const long tstride = (long)gridDim.x * DL_WAVES;
+        uint4 zf[16];
+        // the sixteen 16-byte loads of one row tile; only ever formed for a tile < ntiles, rows clamped to rows - 1
+        auto issue = [&](long tl) {
+            const long row = tl * 16 + r16;
             const long rowc = row < rows ? row : rows - 1;     // clamp (every lane takes part in the MFMAs), skip the store
             const bf16_t *zr = zw + ((size_t)d * rows + rowc) * C + 8 * qq;
-            uint4 zf[16];
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) zf[ks] = *reinterpret_cast<const uint4 *>(zr + 32 * ks);
+        };
+        TMIX_ST_DECL
+        long tile = (long)blockIdx.x * DL_WAVES + wave;
+        if (PIPE && bias && threadIdx.x < C / 8)
+            reinterpret_cast<uint4 *>(s_bias)[threadIdx.x] = reinterpret_cast<const uint4 *>(bias + (size_t)d * C)[threadIdx.x];
+        if (PIPE && tile < ntiles) issue(tile);         // the first tile's loads run under the end of the weight staging
+        __syncthreads();
+        for (; tile < ntiles; tile += tstride) {
+            TMIX_ST_START;
+            if (!PIPE) issue(tile);
+            TMIX_ST_WAIT0;
+            TMIX_ST_WAIT1(zf[0].x);
             f32x4 acc1[4] = {zero, zero, zero, zero};
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks)
 #pragma unroll
                 for (int tau = 0; tau < 4; ++tau)
                     acc1[tau] = mfma_bf16_packed(s_d1[(ks * 4 + tau) * 64 + lane], zf[ks], acc1[tau]);
+            if (PIPE && tile + tstride < ntiles) issue(tile + tstride);   // wave-uniform: a whole wave has a next tile or none
             // tanh + rounding; k-step p of the second product takes n1 = 32 p + 4 qq + e (e < 4) | 32 p + 16 + 4 qq + e - 4
             u32x4 b2[2];
 #pragma unroll
@@ -496,6 +588,7 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
                 b2[p] = u32x4{pack_bf16_exact(v[0], v[1]), pack_bf16_exact(v[2], v[3]),
                               pack_bf16_exact(v[4], v[5]), pack_bf16_exact(v[6], v[7])};
             }
+            TMIX_ST_ARITH;      // (first product and tanh done; the cy loop interleaves the second product and the stores)
             for (int cy = 0; cy < C / 64; ++cy) {
 #pragma unroll
                 for (int cbi = 0; cbi < 2; ++cbi) {
@@ -511,7 +604,8 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
                     for (int e = 0; e < VEC; ++e) ov[e] = e < 4 ? o[0][e] : o[1][e - 4];
                     if (bias) {   // w = time_decay + ww, each rounded where the reference's op chain rounds it
                         float bv[VEC];
-                        load8<bf16_t>(bias + (size_t)d * C + cb * 32 + 8 * qq, bv);
+                        if (PIPE) load8<bf16_t>(s_bias + cb * 32 + 8 * qq, bv);
+                        else load8<bf16_t>(bias + (size_t)d * C + cb * 32 + 8 * qq, bv);
 #pragma unroll
                         for (int e = 0; e < VEC; ++e) ov[e] = bv[e] + round_bf16(ov[e]);
                     }
@@ -530,6 +624,7 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
+            TMIX_ST_END(((long)blockIdx.y * gridDim.x + blockIdx.x) * DL_WAVES + wave);
         }
     }
 }
@@ -542,7 +637,12 @@ __global__ __launch_bounds__(DL_WAVES * 64) void decay_lora_kernel(long rows, in
 // written and read back at the 30-minute shape) never exists in memory.  Transposed product t^T[n][row]; the weight rows of
 // a pair of MFMAs are interleaved so that a lane ends up with 8 consecutive n of its row = one 16-byte store.
 constexpr int LD_C = 512, LD_N = 128;
-template <int NW>
+// PIPE: the K-group loop is rotated -- the eight 16-byte loads (x and its neighbour row, four K-steps) of group g + 1 are issued
+// before the arithmetic of group g, across the tile boundary too (the first group of the wave's next tile under the last group
+// of this one; the very first group before the barrier that ends the W1 staging), and maa_x of the block's direction (1 KiB)
+// sits in LDS behind W1 instead of being loaded from global memory per K-step and tile.  Products, roundings and their order
+// are those of the plain loop (PAFC_TMIX_PIPE=0).
+template <int NW, bool PIPE = true>
 __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long rows, int rev0, const bf16_t *__restrict__ x,
                                                                        const bf16_t *__restrict__ maa_x,
                                                                        const bf16_t *__restrict__ w1n, bf16_t *__restrict__ tout,
@@ -553,52 +653,45 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     extern __shared__ __attribute__((aligned(16))) unsigned char dl_lds[];
     uint4 *s_w1 = reinterpret_cast<uint4 *>(dl_lds);                       // [ks 16][np 4][a 2][lane 64]   128 KiB
+    const bf16_t *s_maa = reinterpret_cast<const bf16_t *>(dl_lds + 2 * 65536);   // PIPE: maa_x of my direction, 1 KiB
     const int colslot = 8 * (r16 >> 2) + (r16 & 3);
     const int d = blockIdx.y;                           // a block serves one direction: its weights are staged once
     const bool rev = (d == 0) ? (rev0 != 0) : true;
-    for (int f = wave; f < 128; f += NW) {        // fragment (ks, np, a): lane (r16, qq) <- W1^T[32 np + colslot + 4 a][32 ks + 8 qq ..]
-        const int ks = f >> 3, np = (f >> 1) & 3, a = f & 1;
-        s_w1[f * 64 + lane] = *reinterpret_cast<const uint4 *>(w1n + ((size_t)d * LD_N + 32 * np + colslot + 4 * a) * C + 32 * ks + 8 * qq);
-    }
-    __syncthreads();
-    const long ntiles = (rows + 15) / 16;
-    for (long tile = (long)blockIdx.x * NW + wave; tile < ntiles; tile += (long)gridDim.x * NW) {
-        const long row = tile * 16 + r16;
+    const long ntiles = (rows + 15) / 16, tstride = (long)gridDim.x * NW;
+    // a tile's two row pointers (own row, neighbour row) at this lane's 8 columns of a 32-column K-step, and whether the
+    // neighbour counts; only ever formed for a tile < ntiles, rows clamped to rows - 1
+    auto tile_rows = [&](long tl, const bf16_t *&xr, const bf16_t *&xnr, bool &has_nb) {
+        const long row = tl * 16 + r16;
         const long rowc = row < rows ? row : rows - 1;     // clamp (every lane takes part in the MFMAs), skip the store
         const int tt = (int)(rowc % T);
         const bool in_seq = rev ? (tt < T - 1) : (tt > 0);
-        const bool has_nb = in_seq || (prev != nullptr && !rev);       // prev: (B, C) the frame before each sequence, or null
+        has_nb = in_seq || (prev != nullptr && !rev);       // prev: (B, C) the frame before each sequence, or null
         const bf16_t *nbrow = in_seq ? x + (rev ? rowc + 1 : rowc - 1) * C : (has_nb ? prev + (rowc / T) * C : x + rowc * C);
-        const bf16_t *xr = x + rowc * C + 8 * qq, *xnr = nbrow + 8 * qq, *mr = maa_x + (size_t)d * C + 8 * qq;
-        f32x4 acc[4][2];
+        xr = x + rowc * C + 8 * qq;
+        xnr = nbrow + 8 * qq;
+    };
+    // one K-step from the 16 bytes of x, of its neighbour row and of maa_x: the operand in registers, then its eight products
+    auto kstep = [&](int ks, const float *xc, const float *xn, const float *mm, bool has_nb, f32x4(&acc)[4][2]) {
+        float o[VEC];
 #pragma unroll
-        for (int np = 0; np < 4; ++np) { acc[np][0] = zero; acc[np][1] = zero; }
-#pragma unroll 1
-        for (int kc = 0; kc < 16; kc += 4)   // four K-steps at a time: their 12 loads are in flight together, no more
-#pragma unroll
-        for (int ks = kc; ks < kc + 4; ++ks) {
-            float xc[VEC], xn[VEC], mm[VEC];
-            load8<bf16_t>(xr + 32 * ks, xc);
-            load8<bf16_t>(xnr + 32 * ks, xn);                // branch-free: select after the load
-            load8<bf16_t>(mr + 32 * ks, mm);
-            float o[VEC];
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float xx = round_bf16((has_nb ? xn[e] : 0.f) - xc[e]);
-                o[e] = xc[e] + round_bf16(xx * mm[e]);              // (rounded by the packing conversion below: one v_cvt_pk per pair)
-            }
-            const u32x4 bq = {pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]),
-                              pack_bf16_rne(o[6], o[7])};
-            // the K-step's products at raised wave priority: a wave that has formed its operand (115 VALU instructions per K-step)
-            // gets the matrix pipe ahead of the waves still forming theirs (8 waves per block: 49.0 -> 43.5 us; 16: 47.6 -> 45.3)
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int np = 0; np < 4; ++np)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    acc[np][a] = mfma_bf16_packed(s_w1[((ks * 4 + np) * 2 + a) * 64 + lane], bq, acc[np][a]);
-            __builtin_amdgcn_s_setprio(0);
+        for (int e = 0; e < VEC; ++e) {
+            const float xx = round_bf16((has_nb ? xn[e] : 0.f) - xc[e]);
+            o[e] = xc[e] + round_bf16(xx * mm[e]);              // (rounded by the packing conversion below: one v_cvt_pk per pair)
         }
+        const u32x4 bq = {pack_bf16_rne(o[0], o[1]), pack_bf16_rne(o[2], o[3]), pack_bf16_rne(o[4], o[5]),
+                          pack_bf16_rne(o[6], o[7])};
+        // the K-step's products at raised wave priority: a wave that has formed its operand (115 VALU instructions per K-step)
+        // gets the matrix pipe ahead of the waves still forming theirs (8 waves per block: 49.0 -> 43.5 us; 16: 47.6 -> 45.3)
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int np = 0; np < 4; ++np)
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+                acc[np][a] = mfma_bf16_packed(s_w1[((ks * 4 + np) * 2 + a) * 64 + lane], bq, acc[np][a]);
+        __builtin_amdgcn_s_setprio(0);
+    };
+    auto finish = [&](long tl, const f32x4(&acc)[4][2]) {
+        const long row = tl * 16 + r16;
         if (row < rows) {
 #pragma unroll
             for (int np = 0; np < 4; ++np) {
@@ -607,6 +700,113 @@ __global__ __launch_bounds__(NW * 64) void tmix_lora_down_kernel(int T, long row
                 for (int e = 0; e < VEC; ++e) o[e] = epilogue_act<2>(e < 4 ? acc[np][0][e] : acc[np][1][e - 4]);
                 store8<bf16_t>(tout + ((size_t)d * rows + row) * LD_N + 32 * np + 8 * qq, o);
             }
+        }
+    };
+    TMIX_ST_DECL
+    long tile = (long)blockIdx.x * NW + wave;
+    // PIPE: two K-groups of raw loads, the one being multiplied and the one in flight.  A group is four K-steps, as in the plain
+    // loop, with 8 waves per block; with 16 (half the register budget: the full group spills) it is two, half a group ahead
+    constexpr int GK = NW > 8 ? 2 : 4, NG = 16 / GK;
+    static_assert(NG % 2 == 0, "the set a tile's first group lies in must not depend on the trip");
+    uint4 gx[2][GK], gn[2][GK];
+    const bf16_t *xr = x, *xnr = x;
+    bool has_nb = false;
+    if (PIPE && tile < ntiles) {       // the first tile's first group runs under the W1 staging
+        tile_rows(tile, xr, xnr, has_nb);
+#pragma unroll
+        for (int j = 0; j < GK; ++j) {
+            gx[0][j] = *reinterpret_cast<const uint4 *>(xr + 32 * j);
+            gn[0][j] = *reinterpret_cast<const uint4 *>(xnr + 32 * j);
+        }
+    }
+    for (int f = wave; f < 128; f += NW) {        // fragment (ks, np, a): lane (r16, qq) <- W1^T[32 np + colslot + 4 a][32 ks + 8 qq ..]
+        const int ks = f >> 3, np = (f >> 1) & 3, a = f & 1;
+        s_w1[f * 64 + lane] = *reinterpret_cast<const uint4 *>(w1n + ((size_t)d * LD_N + 32 * np + colslot + 4 * a) * C + 32 * ks + 8 * qq);
+    }
+    if (PIPE && threadIdx.x < C / 8)
+        reinterpret_cast<uint4 *>(dl_lds + 2 * 65536)[threadIdx.x] = reinterpret_cast<const uint4 *>(maa_x + (size_t)d * C)[threadIdx.x];
+    __syncthreads();
+    if constexpr (PIPE) {
+        for (; tile < ntiles; tile += tstride) {
+            TMIX_ST_START;
+            const bool more = tile + tstride < ntiles;      // wave-uniform: a whole wave has a next tile or none
+            const bf16_t *nxr = xr, *nxnr = xnr;
+            bool nhas = false;
+            if (more) tile_rows(tile + tstride, nxr, nxnr, nhas);
+            f32x4 acc[4][2];
+#pragma unroll
+            for (int np = 0; np < 4; ++np) { acc[np][0] = zero; acc[np][1] = zero; }
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {      // group g in set g & 1, the next group's loads into the other set
+                if (g < NG - 1) {
+#pragma unroll
+                    for (int j = 0; j < GK; ++j) {
+                        gx[(g + 1) & 1][j] = *reinterpret_cast<const uint4 *>(xr + 32 * (GK * (g + 1) + j));
+                        gn[(g + 1) & 1][j] = *reinterpret_cast<const uint4 *>(xnr + 32 * (GK * (g + 1) + j));
+                    }
+                } else if (more) {
+#pragma unroll
+                    for (int j = 0; j < GK; ++j) {
+                        gx[0][j] = *reinterpret_cast<const uint4 *>(nxr + 32 * j);
+                        gn[0][j] = *reinterpret_cast<const uint4 *>(nxnr + 32 * j);
+                    }
+                }
+                TMIX_ST_WAIT0;
+                TMIX_ST_WAIT1(gx[g & 1][0].x);
+#pragma unroll
+                for (int j = 0; j < GK; ++j) {
+                    const int ks = GK * g + j;
+                    float xc[VEC], xn[VEC], mm[VEC];
+                    Elem<bf16_t>::unpack(gx[g & 1][j], xc);
+                    Elem<bf16_t>::unpack(gn[g & 1][j], xn);                // branch-free: select after the load
+                    load8<bf16_t>(s_maa + 32 * ks + 8 * qq, mm);
+                    kstep(ks, xc, xn, mm, has_nb, acc);
+                }
+            }
+            TMIX_ST_ARITH;
+            finish(tile, acc);
+            TMIX_ST_END(((long)blockIdx.y * gridDim.x + blockIdx.x) * NW + wave);
+            xr = nxr; xnr = nxnr; has_nb = nhas;
+        }
+    } else {
+        for (; tile < ntiles; tile += tstride) {
+            TMIX_ST_START;
+            tile_rows(tile, xr, xnr, has_nb);
+            const bf16_t *mr = maa_x + (size_t)d * C + 8 * qq;
+            f32x4 acc[4][2];
+#pragma unroll
+            for (int np = 0; np < 4; ++np) { acc[np][0] = zero; acc[np][1] = zero; }
+#pragma unroll 1
+            for (int kc = 0; kc < 16; kc += 4) {   // four K-steps at a time: their 12 loads are in flight together, no more
+#ifdef PAFC_TMIX_STAMPS
+                uint4 rx[4], rn[4], rm[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    rx[j] = *reinterpret_cast<const uint4 *>(xr + 32 * (kc + j));
+                    rn[j] = *reinterpret_cast<const uint4 *>(xnr + 32 * (kc + j));
+                    rm[j] = *reinterpret_cast<const uint4 *>(mr + 32 * (kc + j));
+                }
+                TMIX_ST_WAIT0;
+                TMIX_ST_WAIT1(rx[0].x);
+#endif
+#pragma unroll
+                for (int ks = kc; ks < kc + 4; ++ks) {
+                    float xc[VEC], xn[VEC], mm[VEC];
+#ifdef PAFC_TMIX_STAMPS
+                    Elem<bf16_t>::unpack(rx[ks - kc], xc);
+                    Elem<bf16_t>::unpack(rn[ks - kc], xn);
+                    Elem<bf16_t>::unpack(rm[ks - kc], mm);
+#else
+                    load8<bf16_t>(xr + 32 * ks, xc);
+                    load8<bf16_t>(xnr + 32 * ks, xn);                // branch-free: select after the load
+                    load8<bf16_t>(mr + 32 * ks, mm);
+#endif
+                    kstep(ks, xc, xn, mm, has_nb, acc);
+                }
+            }
+            TMIX_ST_ARITH;
+            finish(tile, acc);
+            TMIX_ST_END(((long)blockIdx.y * gridDim.x + blockIdx.x) * NW + wave);
         }
     }
 }
@@ -640,6 +840,21 @@ int launch_ln(int dtype_out, const LnArgs &a, hipStream_t s) {
     else
         hipLaunchKernelGGL((add_layernorm_kernel<EX, float>), grid, block, 0, s, a);
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+// PAFC_TMIX_PIPE=0 (read per call): tmix_lora_down, tmix_lora_mix4 (weight-stationary) and decay_lora take their plain loops,
+// which load a tile, wait, compute and store before the next loads, instead of keeping the next tile's loads in flight (A/B
+// runs and tests: both forms in one process; the outputs are bit-identical).
+bool tmix_pipe() {
+    const char *e = getenv("PAFC_TMIX_PIPE");
+    return !(e && e[0] == '0');
+}
+// PAFC_LORA_DOWN_BLOCKS / PAFC_DECAY_LORA_BLOCKS: blocks per direction in place of the one-per-CU rule (tests and A/B runs only)
+long blocks_override(const char *name, long grid) {
+    const char *e = getenv(name);
+    if (!e) return grid;
+    const long g = atol(e);
+    return g < 1 ? 1 : (g > 65535 ? 65535 : g);
 }
 
 }  // namespace
@@ -755,14 +970,21 @@ int pafc_tmix_lora_mix4_bf16_prev(int B, int T, int C, int ndir, int reverse0, c
         const int wcols = wc ? atoi(wc) : 1;
         long G = g ? atol(g) : 2048 / ((C / 64) * ndir);   // measured at the 30-minute shape: 512 blocks 145 us, 1024: 128, 2048: 123
         if (G < 1) G = 1;
-#define PAFC_WS(NW, WCOLS)                                                                                               \
-    hipLaunchKernelGGL((pafc::tmix_lora_mix4_ws_kernel<NW, WCOLS>), dim3((unsigned)G, (C / 64) / WCOLS, ndir), dim3(NW * 64), 0, \
+        const bool pipe = pafc::tmix_pipe();
+#define PAFC_WS_(NW, WCOLS, PIPE)                                                                                        \
+    hipLaunchKernelGGL((pafc::tmix_lora_mix4_ws_kernel<NW, WCOLS, PIPE>), dim3((unsigned)G, (C / 64) / WCOLS, ndir), dim3(NW * 64), 0, \
                        (hipStream_t)stream, T, C, rows, ndir, reverse0, (const pafc::bf16_t *)x, (const pafc::bf16_t *)t,  \
                        (const pafc::bf16_t *)w2t, (const pafc::bf16_t *)maa, (pafc::bf16_t *)z, (const pafc::bf16_t *)prev)
+#define PAFC_WS(NW, WCOLS)                                                                                               \
+    do {                                                                                                                 \
+        if (pipe) PAFC_WS_(NW, WCOLS, true);                                                                             \
+        else PAFC_WS_(NW, WCOLS, false);                                                                                 \
+    } while (0)
         if (wcols == 8 && (C / 64) % 8 == 0) PAFC_WS(8, 8);
         else if (wcols == 4 && (C / 64) % 4 == 0) PAFC_WS(4, 4);
         else PAFC_WS(4, 1);
 #undef PAFC_WS
+#undef PAFC_WS_
         return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
     }
     if (e && e[0] == '1')
@@ -781,10 +1003,11 @@ int pafc_decay_lora_bf16(long rows, int C, int H, int ndir, const void *zw, cons
     if (!zw || !d1n || !d2n || !w) return PAFC_ERR_NULL_POINTER;
     if (rows <= 0 || ndir < 1 || ndir > 2) return PAFC_ERR_BAD_DIMS;
     if (C != pafc::DL_C || H != pafc::DL_H) return PAFC_ERR_UNSUPPORTED;
-    const size_t lds = 2 * 65536 + pafc::DL_WAVES * 16 * (64 + 8) * sizeof(pafc::bf16_t);
-    if (hipFuncSetAttribute((const void *)pafc::decay_lora_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-        return PAFC_ERR_LAUNCH;
+    const bool pipe = pafc::tmix_pipe();
+    const size_t lds = 2 * 65536 + pafc::DL_WAVES * 16 * (64 + 8) * sizeof(pafc::bf16_t) +     // D1, D2, the waves' tiles,
+                       (pipe ? pafc::DL_C * sizeof(pafc::bf16_t) : 0);                         // and time_decay behind them
+    const void *kernel = pipe ? (const void *)pafc::decay_lora_kernel<true> : (const void *)pafc::decay_lora_kernel<false>;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PAFC_ERR_LAUNCH;
     const long ntiles = (rows + 15) / 16;
     int cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -792,9 +1015,14 @@ int pafc_decay_lora_bf16(long rows, int C, int H, int ndir, const void *zw, cons
         return PAFC_ERR_LAUNCH;
     long grid = cus / ndir;                       // one block per CU in all (128 KiB of LDS each)
     if (grid > (ntiles + pafc::DL_WAVES - 1) / pafc::DL_WAVES) grid = (ntiles + pafc::DL_WAVES - 1) / pafc::DL_WAVES;
-    hipLaunchKernelGGL(pafc::decay_lora_kernel, dim3((unsigned)grid, ndir), dim3(pafc::DL_WAVES * 64), lds, (hipStream_t)stream, rows, ndir,
-                       (const pafc::bf16_t *)zw, (const pafc::bf16_t *)d1n, (const pafc::bf16_t *)d2n,
-                       (const pafc::bf16_t *)bias, (pafc::bf16_t *)w);
+    grid = pafc::blocks_override("PAFC_DECAY_LORA_BLOCKS", grid);
+#define PAFC_DECAY(PIPE)                                                                                                 \
+    hipLaunchKernelGGL(pafc::decay_lora_kernel<PIPE>, dim3((unsigned)grid, ndir), dim3(pafc::DL_WAVES * 64), lds, (hipStream_t)stream, \
+                       rows, ndir, (const pafc::bf16_t *)zw, (const pafc::bf16_t *)d1n, (const pafc::bf16_t *)d2n,         \
+                       (const pafc::bf16_t *)bias, (pafc::bf16_t *)w)
+    if (pipe) PAFC_DECAY(true);
+    else PAFC_DECAY(false);
+#undef PAFC_DECAY
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 
@@ -808,7 +1036,8 @@ int pafc_tmix_lora_down_bf16_prev(int B, int T, int C, int N, int ndir, int reve
     if (!x || !maa_x || !w1n || !t) return PAFC_ERR_NULL_POINTER;
     if (B <= 0 || T <= 0 || ndir < 1 || ndir > 2) return PAFC_ERR_BAD_DIMS;
     if (C != pafc::LD_C || N != pafc::LD_N) return PAFC_ERR_UNSUPPORTED;
-    const size_t lds = 2 * 65536;
+    const bool pipe = pafc::tmix_pipe();
+    const size_t lds = 2 * 65536 + (pipe ? pafc::LD_C * sizeof(pafc::bf16_t) : 0);      // W1, and maa_x behind it
     const long rows = (long)B * T, ntiles = (rows + 15) / 16;
     int cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -818,18 +1047,25 @@ int pafc_tmix_lora_down_bf16_prev(int B, int T, int C, int N, int ndir, int reve
     const int nw = e ? atoi(e) : 8;
     long grid = cus / ndir;                       // one block per CU in all (128 KiB of LDS each)
     if (grid > (ntiles + nw - 1) / nw) grid = (ntiles + nw - 1) / nw;
+    grid = pafc::blocks_override("PAFC_LORA_DOWN_BLOCKS", grid);
+#define PAFC_DOWN_(NW, PIPE)                                                                                               \
+    do {                                                                                                                   \
+        if (hipFuncSetAttribute((const void *)pafc::tmix_lora_down_kernel<NW, PIPE>,                                       \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)                       \
+            return PAFC_ERR_LAUNCH;                                                                                        \
+        hipLaunchKernelGGL((pafc::tmix_lora_down_kernel<NW, PIPE>), dim3((unsigned)grid, ndir), dim3(NW * 64), lds,        \
+                           (hipStream_t)stream, T, rows, reverse0, (const pafc::bf16_t *)x, (const pafc::bf16_t *)maa_x,   \
+                           (const pafc::bf16_t *)w1n, (pafc::bf16_t *)t, (const pafc::bf16_t *)prev);                      \
+    } while (0)
 #define PAFC_DOWN(NW)                                                                                                      \
     do {                                                                                                                   \
-        if (hipFuncSetAttribute((const void *)pafc::tmix_lora_down_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                (int)lds) != hipSuccess)                                                                   \
-            return PAFC_ERR_LAUNCH;                                                                                        \
-        hipLaunchKernelGGL(pafc::tmix_lora_down_kernel<NW>, dim3((unsigned)grid, ndir), dim3(NW * 64), lds, (hipStream_t)stream, T, \
-                           rows, reverse0, (const pafc::bf16_t *)x, (const pafc::bf16_t *)maa_x, (const pafc::bf16_t *)w1n, \
-                           (pafc::bf16_t *)t, (const pafc::bf16_t *)prev);                                                 \
+        if (pipe) PAFC_DOWN_(NW, true);                                                                                    \
+        else PAFC_DOWN_(NW, false);                                                                                        \
     } while (0)
     if (nw == 8) PAFC_DOWN(8);
     else PAFC_DOWN(16);
 #undef PAFC_DOWN
+#undef PAFC_DOWN_
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
 }
 
