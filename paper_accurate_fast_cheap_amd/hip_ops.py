@@ -3745,36 +3745,6 @@ def att_head_loss(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
     return _AttHeadLoss.apply(x, weight, bias, target, float(smoothing), denom.reshape(()))
 
 
-def att_loss_unmet(decoders, x: torch.Tensor) -> Optional[str]:
-    """What keeps the attention decoder's loss from running on packed rows over the library's kernels, or None.  decoders: the
-    TransformerDecoder modules that will run (left, and right when reverse_weight > 0); x: the encoder output."""
-    from .transformer.attn_rescore import KERNEL_ACTS
-    if not x.is_cuda:
-        return "the operands are not on the GPU"
-    if not torch.is_grad_enabled():
-        return "gradients are disabled"
-    if not train_kernels_enabled():
-        return "PAFC_TRAIN_KERNELS=0"
-    autocast_bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
-    for dec in decoders:
-        params = list(dec.parameters())
-        if any(not p.is_cuda for p in params):
-            return "the decoder is not on the GPU"
-        bf16_model = x.dtype == torch.bfloat16 and all(p.dtype == torch.bfloat16 for p in params)
-        if not (bf16_model or (autocast_bf16 and all(p.dtype in (torch.float32, torch.bfloat16) for p in params))):
-            return "neither bf16 autocast nor a bf16 module"
-        d = dec.after_norm.normalized_shape[0]
-        if d != dec.attention_heads * 64:
-            return f"attention heads of {d / dec.attention_heads:g} dimensions (the attention kernels take 64)"
-        if any(l.self_attn.dropout.p != 0 or l.src_attn.dropout.p != 0 for l in dec.decoders):
-            return "attention-probability dropout (self_attention_dropout_rate / src_attention_dropout_rate must be 0)"
-        if dec.activation_type not in KERNEL_ACTS:
-            return f"activation_type {dec.activation_type!r} (the kernels path has {sorted(KERNEL_ACTS)})"
-        if not dec.use_output_layer:
-            return "a decoder without output_layer"
-    return None
-
-
 # ---- the attention decoder's beam search (include/pafc_attn_search.h, csrc/attn_search.hip) ----------------------------------
 def _i32_gpu(who: str, **tensors) -> None:
     for name, t in tensors.items():

@@ -10,27 +10,27 @@ hypotheses padded to the longest, masks, the full (beam, L + 1, V) log-softmax, 
 
 backend "kernels" packs instead.  All hypotheses of all utterances are rows without padding -- hypothesis i owns L_i + 1 rows
 ([sos] + y) -- and the encoder output is never repeated: per layer the cross-attention K | V of an utterance is ONE projection
-of its T'_b rows by the stacked [linear_k; linear_v] weight, shared by all its hypotheses.  Every nn.Linear runs on this
-library's GEMMs (hip_ops.linear_fused / linear_bias_act / gemm_f32 / gemm_bf16, and gemm_ph_ex for long fp32 inputs with a
-residual: the framework's fp32 GEMM is the two-stream stall of DESIGN.md section 4), every LayerNorm on
-hip_ops.add_layernorm, both attentions on hip_ops.mha_rows (one launch per attention for all hypotheses and heads; on packed
+of its T'_b rows by the stacked [linear_k; linear_v] weight, shared by all its hypotheses.  The layer body is
+decoder_rows.decoder_layers (which the two searches run too); this module supplies the tables and the causal self-attention.
+Every nn.Linear runs on this library's GEMMs (decoder_rows.proj: hip_ops.linear_fused / linear_bias_act / gemm_f32 / gemm_bf16,
+and gemm_ph_ex for long fp32 inputs with a residual: the framework's fp32 GEMM is the two-stream stall of DESIGN.md section 4),
+every LayerNorm on hip_ops.add_layernorm, both attentions on hip_ops.mha_rows (one launch per attention for all hypotheses and heads; on packed
 rows `causal` equals the reference's pad-and-subsequent mask for every row that is scored), and hip_ops.logp_gather_rows reads
 log p(target) of a row straight from the logits: the (rows, V) log-softmax is never formed, and the output_layer GEMM runs
 over chunks of utterances so the logits never exceed LOGITS_CAP_BYTES.  One upload (the int32 tables) and one read of the
 device (the rows' log-probabilities) per call."""
-import functools
 import math
 from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from .decoder import BiTransformerDecoder
+from .decoder_rows import (KERNEL_ACTS, CrossAttention, decoder_layers, decoder_proj, embed_rows,    # noqa: F401 (re-exports)
+                           kernels_unmet, left_right, position_table, upload_tables)
 from .search import DecodeResult
 
 ATTN_RESCORING_MODES = ("attention_rescoring", "ctc_beam_td_attn_rescoring", "rnnt_beam_attn_rescoring")
 LOGITS_CAP_BYTES = 64 << 20        # the logits of one output_layer chunk: 3355 fp32 rows at V = 5000
-KERNEL_ACTS = {"relu": "relu", "swish": "silu", "tanh": "tanh"}        # the epilogues the GEMMs fuse
 
 
 class AttentionScores:
@@ -48,12 +48,6 @@ class AttentionScores:
         if reverse_weight > 0 and self.r2l is not None:
             return [[a * (1 - reverse_weight) + r * reverse_weight for a, r in zip(la, lr)] for la, lr in zip(self.l2r, self.r2l)]
         return [list(la) for la in self.l2r]
-
-
-def left_right(decoder):
-    if isinstance(decoder, BiTransformerDecoder):
-        return decoder.left_decoder, decoder.right_decoder
-    return decoder, None
 
 
 def check_tokens(hyps: Sequence[Sequence[Sequence[int]]], vocab_size: int) -> None:
@@ -149,110 +143,6 @@ def _score_framework(model, encoder_out, lens, hyps, reverse_weight):
 # the kernels backend
 # ---------------------------------------------------------------------------------------------------------------------------
 
-def kernels_unmet(model, encoder_out: torch.Tensor, use_right: bool) -> Optional[str]:
-    """What keeps the packed second pass from running on the library's kernels, or None."""
-    if not encoder_out.is_cuda:
-        return "the operands are not on the GPU"
-    left, right = left_right(model.decoder)
-    for dec in [left] + ([right] if use_right else []):
-        dts = {p.dtype for p in dec.parameters()}
-        if len(dts) != 1 or next(iter(dts)) not in (torch.float32, torch.bfloat16):
-            return "the decoder's parameters are not all float32 or all bfloat16"
-        if any(not p.is_cuda for p in dec.parameters()):
-            return "the decoder is not on the GPU"
-        d = dec.after_norm.normalized_shape[0]
-        if d != dec.attention_heads * 64:
-            return f"attention heads of {d // dec.attention_heads if d % dec.attention_heads == 0 else d / dec.attention_heads} " \
-                   "dimensions (the attention kernel takes 64)"
-        if dec.activation_type not in KERNEL_ACTS:
-            return f"activation_type {dec.activation_type!r} (the GEMM epilogues have {sorted(KERNEL_ACTS)})"
-        if not dec.use_output_layer:
-            return "a decoder without output_layer"
-    return None
-
-
-def _proj(x, weight, bias, act: str = "none", residual=None, *, split_ok: bool):
-    """act(x weight^T + bias) [+ residual] on the library's GEMMs; PafcError for operands none of them takes.  split_ok (no
-    default: every call site passes the decoder's switch): long fp32 inputs may take the split-operand GEMM."""
-    from .. import hip_ops
-    from .._lib import PafcError
-    N, K = weight.shape
-    if x.dtype == torch.float32:
-        if act == "none" and residual is None:
-            return hip_ops.linear_fused(x, weight, bias, "none", split_ok=split_ok)
-        if act == "none" and split_ok and hip_ops.split_gemm_takes(x, weight, bias):
-            # linear_fused's own rule for long fp32 inputs, with the residual add in the epilogue (the split-operand GEMM
-            # fuses an fp32 residual, not an activation: the feed-forward's first projection stays on exact products)
-            planes = hip_ops.split_planes(x if x.is_contiguous() else x.contiguous())
-            return hip_ops.gemm_ph_ex(planes, hip_ops.split_weight_cached(weight), bias, residual=residual, a_split=True,
-                                      out_kind="f32")
-        if hip_ops.gemm_f32_ok(x, weight):
-            return hip_ops.gemm_f32(x, weight, bias, act, residual=residual)
-    elif K % 64 == 0 and N % 8 == 0:
-        return hip_ops.gemm_bf16(x, weight, bias, act, residual=residual)
-    elif act == "none" and residual is None and K % 4 == 0:
-        return hip_ops.linear_bias_act(x, weight, bias, "none")
-    raise PafcError(f"score_attention(backend='kernels'): no GEMM of the library takes a ({N}, {K}) {x.dtype} projection "
-                    f"with act {act!r}")
-
-
-def _stacked(layer):
-    """[linear_q; linear_k; linear_v] of the self-attention and [linear_k; linear_v] of the source attention as one weight and
-    one bias each, cached on the layer for as long as the five weights are the tensors they were made from."""
-    from .. import hip_ops
-    sa, ca = layer.self_attn, layer.src_attn
-    lins = (sa.linear_q, sa.linear_k, sa.linear_v, ca.linear_k, ca.linear_v)
-    stamp = tuple((l.weight.data_ptr(), l.weight._version, None if l.bias is None else l.bias._version) for l in lins) \
-        + (hip_ops.param_epoch(),)
-    ent = layer.__dict__.get("_pafc_stacked")
-    if ent is None or ent[0] != stamp:
-        bias = lambda l: l.bias if l.bias is not None else torch.zeros_like(l.weight[:, 0])     # noqa: E731 (key_bias: false)
-        ent = (stamp, torch.cat([l.weight for l in lins[:3]]).detach(), torch.cat([bias(l) for l in lins[:3]]).detach(),
-               torch.cat([l.weight for l in lins[3:]]).detach(), torch.cat([bias(l) for l in lins[3:]]).detach(),
-               hip_ops.DerivedFill(sa.linear_q.weight.device))
-        layer.__dict__["_pafc_stacked"] = ent
-    else:
-        ent[5].use(sa.linear_q.weight.device)
-    return ent[1:5]
-
-
-def _decoder_rows(dec, tok, pos, max_rows, memory, q_off, self_len, mem_off, mem_len, split_ok):
-    """The decoder stack over packed rows: tok / pos (rows) int32 the input token and position of every row (positions below
-    max_rows) -> (rows, d), the input of output_layer."""
-    from .. import hip_ops
-    d, H = memory.size(1), dec.attention_heads
-    act = KERNEL_ACTS[dec.activation_type]
-    posenc = dec.embed[1]
-    pe = posenc.position_encoding(0, max_rows, False, device=memory.device)[0]
-    x = dec.embed[0].weight.index_select(0, tok) * posenc.xscale + pe.to(memory.dtype).index_select(0, pos)
-    ln = lambda t, n: hip_ops.add_layernorm(t, None, 0.0, n.weight, n.bias, eps=n.eps)[1]                     # noqa: E731
-    add_ln = lambda t, y, n: hip_ops.add_layernorm(t, y, 1.0, n.weight, n.bias, eps=n.eps, want_x=False)[1]   # noqa: E731
-    proj = functools.partial(_proj, split_ok=split_ok)       # every projection of the stack under the decoder's one switch
-    for layer in dec.decoders:
-        w_qkv, b_qkv, w_kv, b_kv = _stacked(layer)
-        sa, ca, ff = layer.self_attn, layer.src_attn, layer.feed_forward
-        pre = layer.normalize_before
-        qkv = proj(ln(x, layer.norm1) if pre else x, w_qkv, b_qkv)
-        att = hip_ops.mha_rows(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], q_off, q_off[:-1], self_len, H, True)
-        if pre:
-            x = proj(att, sa.linear_out.weight, sa.linear_out.bias, residual=x)
-        else:
-            x = add_ln(x, proj(att, sa.linear_out.weight, sa.linear_out.bias), layer.norm1)
-        q = proj(ln(x, layer.norm2) if pre else x, ca.linear_q.weight, ca.linear_q.bias)
-        kv = proj(memory, w_kv, b_kv)                 # once per utterance row, for all its hypotheses
-        att = hip_ops.mha_rows(q, kv[:, :d], kv[:, d:], q_off, mem_off, mem_len, H, False)
-        if pre:
-            x = proj(att, ca.linear_out.weight, ca.linear_out.bias, residual=x)
-        else:
-            x = add_ln(x, proj(att, ca.linear_out.weight, ca.linear_out.bias), layer.norm2)
-        h = proj(ln(x, layer.norm3) if pre else x, ff.w_1.weight, ff.w_1.bias, act=act)
-        if pre:
-            x = proj(h, ff.w_2.weight, ff.w_2.bias, residual=x)
-        else:
-            x = add_ln(x, proj(h, ff.w_2.weight, ff.w_2.bias), layer.norm3)
-    return ln(x, dec.after_norm) if dec.normalize_before else x
-
-
 def _logits_chunks(utt_row_end: List[int], cap_rows: int) -> List[tuple]:
     """Row ranges for the output_layer GEMM: whole utterances while they fit under cap_rows, an utterance that alone exceeds
     the cap in pieces of cap_rows."""
@@ -312,12 +202,7 @@ def _score_kernels(model, encoder_out, lens, hyps, use_right: bool):
         tgt_l[e - 1] = tgt_r[e - 1] = eos
         pos[a:e] = np.arange(e - a)
     fields = [tok_l, tok_r, tgt_l, tgt_r, pos, q_off, Ls + 1, [mem_row[b] for b, _ in flat], [lens[b] for b, _ in flat]]
-    packed = torch.from_numpy(np.concatenate([np.asarray(f, dtype=np.int32) for f in fields])).to(dev, non_blocking=True)
-    views, at = [], 0
-    for f in fields:
-        views.append(packed[at:at + len(f)])
-        at += len(f)
-    tok_l, tok_r, tgt_l, tgt_r, pos, q_off_d, self_len, mem_off, mem_len = views
+    tok_l, tok_r, tgt_l, tgt_r, pos, q_off_d, self_len, mem_off, mem_len = upload_tables(fields, dev)
     utt_row_end, n = [], 0
     for b in used:
         n += len(hyps[b])
@@ -325,13 +210,18 @@ def _score_kernels(model, encoder_out, lens, hyps, use_right: bool):
     V = left.output_layer.weight.size(0)
     cap_rows = max(1, LOGITS_CAP_BYTES // (V * memory.element_size()))
     chunks = _logits_chunks(utt_row_end, cap_rows)
-    split_ok = bool(getattr(model.decoder, "fp32_split_operands", True))
+    proj = decoder_proj(model, "score_attention")
+    d, H = memory.size(1), left.attention_heads
+    cross = CrossAttention(q_off_d, mem_off, mem_len, memory=memory)     # K | V once per utterance row, for all its hypotheses
+    self_attention = lambda i, layer, qkv: hip_ops.mha_rows(        # causal over a hypothesis' own rows          # noqa: E731
+        qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], q_off_d, q_off_d[:-1], self_len, H, True)
     logp = torch.empty((2 if use_right else 1) * R, dtype=torch.float32, device=dev)
     peak = 0
     for i, (dec, tok, tgt) in enumerate([(left, tok_l, tgt_l)] + ([(right, tok_r, tgt_r)] if use_right else [])):
-        x = _decoder_rows(dec, tok, pos, int(Ls.max()) + 1, memory, q_off_d, self_len, mem_off, mem_len, split_ok)
+        pe = position_table(dec, int(Ls.max()) + 1, dev, dtype)
+        x = decoder_layers(dec, embed_rows(dec, pe, tok, pos), self_attention, cross, proj)
         for a, e in chunks:
-            logits = _proj(x[a:e], dec.output_layer.weight, dec.output_layer.bias, split_ok=split_ok)
+            logits = proj(x[a:e], dec.output_layer.weight, dec.output_layer.bias)
             peak = max(peak, logits.numel() * logits.element_size())
             hip_ops.logp_gather_rows(logits, tgt[a:e], out=logp[i * R + a:i * R + e])
     host = logp.tolist()                                                   # the one read of the device

@@ -9,20 +9,20 @@ backend "kernels" keeps the R = B*N running rows on the device.  Per layer the s
 projection of its memory rows, made before the loop and shared by its beams; the self-attention keeps a key/value cache whose
 rows are written once and never moved -- a beam finds its ancestors through a small index table -- and the two prunings read the
 logits directly (include/pafc_attn_search.h: pafc_mha_step, pafc_attn_beam_select).  Every nn.Linear runs on the library's GEMMs
-through attn_rescore._proj, every LayerNorm on hip_ops.add_layernorm, the source attention on hip_ops.mha_rows with one group per
-utterance.  A step's shapes do not depend on the step and nothing in it reads the device: the position and the `done` flag live
-in device memory, a step that finds `done` set (or the cap reached) changes nothing, and the host looks at (done, pos) once per
-STEPS_PER_READ steps.  After the loop one read brings the trace (parent, token, score of every slot and step) and the scores;
-the backtrace and the length penalty run on the host in float64.  step_graph=True replays a block of steps as one captured
-graph instead of issuing its launches one by one."""
-import functools
+through decoder_rows.proj, every LayerNorm on hip_ops.add_layernorm, the source attention on hip_ops.mha_rows with one group per
+utterance: the layer body is decoder_rows.decoder_layers on the set-up of decoder_rows.SearchEngine; this module supplies the
+self-attention and the selection.  A step's shapes do not depend on the step and nothing in it reads the device: the position
+and the `done` flag live in device memory, a step that finds `done` set (or the cap reached) changes nothing, and the host looks
+at (done, pos) once per STEPS_PER_READ steps.  After the loop one read brings the trace (parent, token, score of every slot and
+step) and the scores; the backtrace and the length penalty run on the host in float64.  step_graph=True replays a block of steps
+as one captured graph instead of issuing its launches one by one."""
 from typing import List, Optional
 
 import numpy as np
 import torch
 
-from .attn_rescore import KERNEL_ACTS, _proj, _stacked, kernels_unmet, left_right
 from .decoder import subsequent_mask
+from .decoder_rows import SearchEngine, kernels_unmet, pass_launches
 from .search import DecodeResult
 from ..utils import graph_step
 
@@ -166,37 +166,24 @@ def _search_framework(model, encoder_out, encoder_mask, beam_size, length_penalt
 # the kernels backend
 # ---------------------------------------------------------------------------------------------------------------------------
 
-class _Engine:
+class _Engine(SearchEngine):
     """The device state of one call and its step.  Nothing here reads the device."""
 
     def __init__(self, model, encoder_out, encoder_mask, N: int, cap: int):
-        from .. import hip_ops
         from .._lib import PafcError
-        self.ops = hip_ops
-        dec, _ = left_right(model.decoder)
-        self.dec, self.N, self.cap, self.eos = dec, N, cap, int(model.eos)
+        self.bind_decoder(model, "attention_beam_search")
+        dec, dtype = self.dec, self.dtype
+        self.N, self.cap, self.eos = N, cap, int(model.eos)
         dev = encoder_out.device
         B, T, d = encoder_out.shape
-        self.B, self.R, self.P, self.d, self.H = B, B * N, cap + 1, d, dec.attention_heads
+        self.B, self.R, self.P = B, B * N, cap + 1
         R, P = self.R, self.P
-        dtype = dec.after_norm.weight.dtype
-        self.split_ok = bool(getattr(model.decoder, "fp32_split_operands", True))
-        self.cache_bytes = len(dec.decoders) * P * R * 2 * d * torch.empty(0, dtype=dtype).element_size()
+        self.cache_bytes = self.cache_bytes_of(P * R, d)
         if self.cache_bytes > CACHE_CAP_BYTES:
             raise PafcError(f"attention_beam_search(backend='kernels'): the key/value caches of {len(dec.decoders)} layers x "
                             f"{P} positions x {R} rows need {self.cache_bytes} bytes, above CACHE_CAP_BYTES = {CACHE_CAP_BYTES}: "
                             "set max_len (or decode fewer utterances per call)")
-        self.proj = functools.partial(_proj, split_ok=self.split_ok)
-        # the source attention's K | V: every layer projects the memory once, for all beams and steps.  The padded rows are
-        # projected too and never read (kv_len): the utterances' lengths stay on the device.
-        memory = encoder_out.to(dtype).reshape(B * T, d)
-        self.mem_kv = [self.proj(memory, *_stacked(layer)[2:]) for layer in dec.decoders]
-        self.q_off = torch.arange(0, R + 1, N, dtype=torch.int32, device=dev)
-        self.kv_off = torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
-        self.kv_len = encoder_mask.reshape(B, T).sum(1).to(torch.int32)
-        posenc = dec.embed[1]
-        self.pe = posenc.position_encoding(0, P, False, device=dev)[0].to(dtype)
-        self.xscale = posenc.xscale
+        self.project_memory(encoder_out, encoder_mask.reshape(B, T).sum(1).to(torch.int32), N, P)
         # the state
         self.caches = [torch.empty(P, R, 2 * d, dtype=dtype, device=dev) for _ in dec.decoders]
         self.anc = torch.zeros(2, R, P, dtype=torch.int32, device=dev)
@@ -210,46 +197,17 @@ class _Engine:
         self.trace_parent = torch.zeros(P, R, dtype=torch.int32, device=dev)
         self.trace_token = torch.zeros(P, R, dtype=torch.int32, device=dev)
         self.trace_score = torch.zeros(P, R, dtype=torch.float32, device=dev)
-        self.workspace = hip_ops.attn_beam_select_workspace(B, N, dev)
-        self.launches = 0
+        self.workspace = self.ops.attn_beam_select_workspace(B, N, dev)
+        self.launches = pass_launches(dec) + 3                  # the decoder pass, output_layer, the selection's two
+
+    def self_attention(self, i, layer, qkv):
+        return self.ops.mha_step(qkv, self.caches[i], self.anc, self.pos, self.done, self.N, self.H)
 
     def step(self):
-        ops, dec, d, H = self.ops, self.dec, self.d, self.H
-        act = KERNEL_ACTS[dec.activation_type]
-        proj = self.proj
-        ln = lambda t, n: ops.add_layernorm(t, None, 0.0, n.weight, n.bias, eps=n.eps)[1]                     # noqa: E731
-        add_ln = lambda t, y, n: ops.add_layernorm(t, y, 1.0, n.weight, n.bias, eps=n.eps, want_x=False)[1]   # noqa: E731
-        x = dec.embed[0].weight.index_select(0, self.token) * self.xscale + self.pe.index_select(0, self.pos)
-        n = 4
-        for layer, cache, mem_kv in zip(dec.decoders, self.caches, self.mem_kv):
-            w_qkv, b_qkv, _, _ = _stacked(layer)
-            sa, ca, ff = layer.self_attn, layer.src_attn, layer.feed_forward
-            pre = layer.normalize_before
-            qkv = proj(ln(x, layer.norm1) if pre else x, w_qkv, b_qkv)
-            att = ops.mha_step(qkv, cache, self.anc, self.pos, self.done, self.N, H)
-            if pre:
-                x = proj(att, sa.linear_out.weight, sa.linear_out.bias, residual=x)
-            else:
-                x = add_ln(x, proj(att, sa.linear_out.weight, sa.linear_out.bias), layer.norm1)
-            q = proj(ln(x, layer.norm2) if pre else x, ca.linear_q.weight, ca.linear_q.bias)
-            att = ops.mha_rows(q, mem_kv[:, :d], mem_kv[:, d:], self.q_off, self.kv_off, self.kv_len, H, False)
-            if pre:
-                x = proj(att, ca.linear_out.weight, ca.linear_out.bias, residual=x)
-            else:
-                x = add_ln(x, proj(att, ca.linear_out.weight, ca.linear_out.bias), layer.norm2)
-            h = proj(ln(x, layer.norm3) if pre else x, ff.w_1.weight, ff.w_1.bias, act=act)
-            if pre:
-                x = proj(h, ff.w_2.weight, ff.w_2.bias, residual=x)
-            else:
-                x = add_ln(x, proj(h, ff.w_2.weight, ff.w_2.bias), layer.norm3)
-            n += 11
-        if dec.normalize_before:
-            x = ln(x, dec.after_norm)
-            n += 1
-        logits = proj(x, dec.output_layer.weight, dec.output_layer.bias)
-        ops.attn_beam_select(logits, self.N, self.eos, self.cap, self.score, self.ended, self.token, self.anc,
-                             self.trace_parent, self.trace_token, self.trace_score, self.pos, self.done, self.workspace)
-        self.launches = n + 3
+        dec = self.dec
+        logits = self.proj(self.decoder_pass(self.token, self.pos), dec.output_layer.weight, dec.output_layer.bias)
+        self.ops.attn_beam_select(logits, self.N, self.eos, self.cap, self.score, self.ended, self.token, self.anc,
+                                  self.trace_parent, self.trace_token, self.trace_score, self.pos, self.done, self.workspace)
 
 
 def backtrace(parent: np.ndarray, token: np.ndarray, N: int) -> List[List[int]]:

@@ -9,8 +9,9 @@ LabelSmoothingLoss, th_accuracy -- on the CPU and the GPU.
 
 backend "kernels" runs packed rows under autograd, the layout of the second pass (transformer/attn_rescore.py): utterance b
 owns L_b + 1 rows ([sos] + y), no padding and no masks.  The memory stays where the encoder left it (kv_off = b * T', kv_len
-the device-side encoder lengths): nothing is copied or repeated.  Projections run through hip_ops.linear (stacked q | k | v
-and k | v weights as a torch.cat of the parameters, so autograd reaches each of them), LayerNorm through hip_ops.layer_norm,
+the device-side encoder lengths): nothing is copied or repeated.  The stack is decoder_rows.decoder_rows_train, next to the
+inference body it mirrors, and decoder_rows.att_loss_unmet says what it takes.  Projections run through hip_ops.linear (stacked
+q | k | v and k | v weights as a torch.cat of the parameters, so autograd reaches each of them), LayerNorm through layer_norm,
 both attentions through hip_ops.mha_rows_train (pafc_mha_rows_lse / pafc_mha_rows_bwd), the residual dropouts through
 hip_ops.residual_dropout, and output_layer + loss + accuracy through hip_ops.att_head_loss: the (rows, V) log-softmax is never
 formed.  The row tables come from the transcript lengths on the host -- the batch holds them there -- in one upload; with
@@ -21,7 +22,8 @@ import numpy as np
 import torch
 
 from ..utils.common import IGNORE_ID, add_sos_eos, reverse_pad_list, th_accuracy
-from .attn_rescore import left_right
+from . import decoder_rows
+from .decoder_rows import decoder_rows_train, left_right, upload_tables
 from .label_smoothing_loss import LabelSmoothingLoss
 
 BACKENDS = ("framework", "kernels")
@@ -41,9 +43,8 @@ def _decoders(model, reverse_weight: float):
 
 
 def att_loss_unmet(model, encoder_out: torch.Tensor) -> Optional[str]:
-    """What keeps att_loss(backend='kernels') from running for this model and input, or None (hip_ops.att_loss_unmet)."""
-    from .. import hip_ops
-    return hip_ops.att_loss_unmet(_decoders(model, float(getattr(model, "reverse_weight", 0.0))), encoder_out)
+    """What keeps att_loss(backend='kernels') from running for this model and input, or None (decoder_rows.att_loss_unmet)."""
+    return decoder_rows.att_loss_unmet(_decoders(model, float(getattr(model, "reverse_weight", 0.0))), encoder_out)
 
 
 def att_loss(model, encoder_out: torch.Tensor, encoder_mask: torch.Tensor, text: torch.Tensor, text_lengths: torch.Tensor,
@@ -117,12 +118,7 @@ def _att_loss_kernels(model, encoder_out, encoder_mask, text, text_lengths):
         raise PafcError(f"att_loss: {B} utterances, text {tuple(text.shape)}, lengths {lens.tolist()}")
     Lmax = max(1, text.size(1))
     R, fields = _tables(lens, Lmax, T, bool(getattr(model, "length_normalized_loss", False)))
-    packed = torch.from_numpy(np.concatenate([np.asarray(f, dtype=np.int32) for f in fields])).to(dev, non_blocking=True)
-    views, at = [], 0
-    for f in fields:
-        views.append(packed[at:at + len(f)])
-        at += len(f)
-    pos, l_in, l_out, r_in, r_out, q_off, self_len, mem_off, denom_i = views
+    pos, l_in, l_out, r_in, r_out, q_off, self_len, mem_off, denom_i = upload_tables(fields, dev)
     denom = denom_i.to(torch.float32)
     flat = text.to(dev).reshape(-1).to(torch.int32)
     if flat.numel() == 0:
@@ -135,7 +131,7 @@ def _att_loss_kernels(model, encoder_out, encoder_mask, text, text_lengths):
     for i, dec in enumerate(decs):
         tok = pick(l_in if i == 0 else r_in, model.sos)
         tgt = pick(l_out if i == 0 else r_out, model.eos)
-        x = _decoder_rows_train(dec, tok, pos, int(lens.max()) + 1, memory, q_off, self_len, mem_off, mem_len)
+        x = decoder_rows_train(dec, tok, pos, int(lens.max()) + 1, memory, q_off, self_len, mem_off, mem_len)
         term, n_correct = hip_ops.att_head_loss(x, dec.output_layer.weight, dec.output_layer.bias, tgt, smoothing, denom)
         if i == 0:
             loss = term * (1 - rw) if rw > 0 else term
@@ -143,39 +139,3 @@ def _att_loss_kernels(model, encoder_out, encoder_mask, text, text_lengths):
         else:
             loss = loss + term * rw
     return loss, acc
-
-
-def _decoder_rows_train(dec, tok, pos, max_rows, memory, q_off, self_len, mem_off, mem_len):
-    """The decoder stack over packed rows under autograd: tok / pos (rows) int32 -> (rows, d), the input of output_layer."""
-    from .. import hip_ops
-    d, H = memory.size(1), dec.attention_heads
-    training = dec.training
-    posenc = dec.embed[1]
-    pe = posenc.position_encoding(0, max_rows, False, device=memory.device)[0]
-    x = torch.nn.functional.embedding(tok, dec.embed[0].weight) * posenc.xscale + pe.to(dec.embed[0].weight.dtype)[pos.long()]
-    x = posenc.dropout(x)
-    ln = lambda t, n: hip_ops.layer_norm(t, n.weight, n.bias, n.eps, bf16_out=True)                         # noqa: E731
-    ln_sum = lambda t, n: hip_ops.layer_norm(t, n.weight, n.bias, n.eps)        # post-norm: the residual stream keeps its dtype  # noqa: E731
-    cat_b = lambda lins: torch.cat([l.bias if l.bias is not None else torch.zeros_like(l.weight[:, 0]) for l in lins])  # noqa: E731
-    for layer in dec.decoders:
-        sa, ca = layer.self_attn, layer.src_attn
-        pre, p = layer.normalize_before, layer.dropout.p
-        lins = (sa.linear_q, sa.linear_k, sa.linear_v)
-        qkv = hip_ops.linear(ln(x, layer.norm1) if pre else x, torch.cat([l.weight for l in lins]), cat_b(lins))
-        att = hip_ops.mha_rows_train(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], q_off, q_off[:-1], self_len, H, True)
-        x = hip_ops.residual_dropout(x, hip_ops.linear(att, sa.linear_out.weight, sa.linear_out.bias), 1.0, p, training)
-        if not pre:
-            x = ln_sum(x, layer.norm1)
-        q = hip_ops.linear(ln(x, layer.norm2) if pre else x, ca.linear_q.weight, ca.linear_q.bias)
-        lins = (ca.linear_k, ca.linear_v)
-        kv = hip_ops.linear(memory, torch.cat([l.weight for l in lins]), cat_b(lins))
-        if q.dtype != kv.dtype:
-            kv = kv.to(q.dtype)
-        att = hip_ops.mha_rows_train(q, kv[:, :d], kv[:, d:], q_off, mem_off, mem_len, H, False)
-        x = hip_ops.residual_dropout(x, hip_ops.linear(att, ca.linear_out.weight, ca.linear_out.bias), 1.0, p, training)
-        if not pre:
-            x = ln_sum(x, layer.norm2)
-        x = hip_ops.residual_dropout(x, layer.feed_forward(ln(x, layer.norm3) if pre else x), 1.0, p, training)
-        if not pre:
-            x = ln_sum(x, layer.norm3)
-    return ln(x, dec.after_norm) if dec.normalize_before else x

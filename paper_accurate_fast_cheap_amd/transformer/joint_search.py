@@ -44,19 +44,19 @@ hidden rows whose rows are written once and never moved (a prefix is decoded at 
 it leaves the beam), and per beam slot the table of its ancestors' cache rows.  Before the loop one launch takes the
 candidates of all frames; a frame is then: gather the beam's hidden rows, output_layer on the library's GEMM, pafc_joint_frame
 (one block per utterance: expansion, recursion, times, confidences, joint scores, the new beam), and the decoder step of the
-R = B * N rows at their different positions (pafc_mha_step_paths; rows that enter the beam decoded ride along and write
-nothing).  Nothing in the loop reads the device; one read after the last frame brings the beams' hypotheses in compact form
-(pafc_joint_collect), the scores and the counters."""
-import functools
+R = B * N rows at their different positions (decoder_rows.decoder_layers on the set-up of decoder_rows.SearchEngine, with
+pafc_mha_step_paths as its self-attention; rows that enter the beam decoded ride along and write nothing).  Nothing in the loop
+reads the device; one read after the last frame brings the beams' hypotheses in compact form (pafc_joint_collect), the scores
+and the counters."""
 import math
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
-from .attn_rescore import KERNEL_ACTS, _proj, _stacked, kernels_unmet, left_right
 from .attn_search import CACHE_CAP_BYTES, MAX_BEAM
 from .decoder import subsequent_mask
+from .decoder_rows import SearchEngine, kernels_unmet, left_right, pass_launches
 from .search import DecodeResult
 
 MAX_PRE_BEAM = 24                  # candidates per frame the kernels backend is laid out for (beam 16 at pre_beam_ratio 1.5)
@@ -257,34 +257,30 @@ class _Utterance:
 # the kernels backend
 # ---------------------------------------------------------------------------------------------------------------------------
 
-class _Engine:
+class _Engine(SearchEngine):
     """The device state of one call, its decoder step and its frame.  Nothing here reads the device."""
 
     def __init__(self, model, encoder_out, lens, ctc_probs, N, C, ctc_w, dec_w, bonus, blank, blank_threshold):
-        from .. import hip_ops
         from .._lib import PafcError
-        self.ops = hip_ops
-        dec, _ = left_right(model.decoder)
-        self.dec, self.N, self.blank = dec, N, blank
+        self.bind_decoder(model, "joint_decoding")
+        dec, dtype = self.dec, self.dtype
+        self.N, self.blank = N, blank
         self.weights = (ctc_w, dec_w, bonus)
         self.use_dec = dec_w > 0
         dev = encoder_out.device
         B, T, d = encoder_out.shape
-        self.B, self.T, self.R, self.d, self.H, self.V = B, T, B * N, d, dec.attention_heads, ctc_probs.size(2)
+        self.B, self.T, self.R, self.V = B, T, B * N, ctc_probs.size(2)
         R = self.R
         self.rows = (T + 1) * R                                   # cache rows; the hidden pool has one more, the dump row
-        dtype = dec.after_norm.weight.dtype
-        self.split_ok = bool(getattr(model.decoder, "fp32_split_operands", True))
-        self.cache_bytes = len(dec.decoders) * self.rows * 2 * d * torch.empty(0, dtype=dtype).element_size() if self.use_dec else 0
+        self.cache_bytes = self.cache_bytes_of(self.rows, d) if self.use_dec else 0
         if self.cache_bytes > CACHE_CAP_BYTES:
             raise PafcError(f"joint_decoding(backend='kernels'): the key/value caches of {len(dec.decoders)} layers x {T + 1} "
                             f"rounds x {R} rows need {self.cache_bytes} bytes, above CACHE_CAP_BYTES = {CACHE_CAP_BYTES}: decode "
                             "fewer utterances per call")
-        self.proj = functools.partial(_proj, split_ok=self.split_ok)
         self.lens = torch.tensor(lens, dtype=torch.int32, device=dev)
-        self.state = hip_ops.JointSearchState(B, N, C, T, int(model.sos), dev, decode=self.use_dec)
+        self.state = self.ops.JointSearchState(B, N, C, T, int(model.sos), dev, decode=self.use_dec)
         ctc = ctc_probs if ctc_probs.dtype in (torch.float32, torch.bfloat16) else ctc_probs.float()
-        hip_ops.joint_candidates(self.state, ctc.contiguous(), self.lens, blank, math.log(blank_threshold))
+        self.ops.joint_candidates(self.state, ctc.contiguous(), self.lens, blank, math.log(blank_threshold))
         self.launches = self.reads = 0
         if not self.use_dec:
             return
@@ -296,54 +292,21 @@ class _Engine:
         st.evals.mul_(has)
         slot0(st.store_row).copy_(torch.where(has, slot0(st.store_row), torch.full_like(self.lens, (T + 1) * R)))
         st.row[:, 0].copy_(torch.where(has, st.row[:, 0], torch.full_like(self.lens, -1)))
-        memory = encoder_out.to(dtype).reshape(B * T, d)
-        self.mem_kv = [self.proj(memory, *_stacked(layer)[2:]) for layer in dec.decoders]
-        self.q_off = torch.arange(0, R + 1, N, dtype=torch.int32, device=dev)
-        self.kv_off = torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
-        self.kv_len = self.lens
-        posenc = dec.embed[1]
-        self.pe = posenc.position_encoding(0, T + 1, False, device=dev)[0].to(dtype)
-        self.xscale = posenc.xscale
+        self.project_memory(encoder_out, self.lens, N, T + 1)
         self.caches = [torch.empty(self.rows, 2 * d, dtype=dtype, device=dev) for _ in dec.decoders]
         self.hidden = torch.zeros(self.rows + 1, d, dtype=dtype, device=dev)
 
+    def self_attention(self, i, layer, qkv):
+        st = self.state
+        return self.ops.mha_step_paths(qkv, self.caches[i], st.path, st.in_len, st.new_row, st.need, self.H)
+
     def decode(self):
         """The decoder step of the R rows at their own positions; rows without `need` ride along and store nothing (their
-        hidden row goes to the dump row)."""
-        ops, dec, d, H, st = self.ops, self.dec, self.d, self.H, self.state
-        act = KERNEL_ACTS[dec.activation_type]
-        proj = self.proj
-        ln = lambda t, n: ops.add_layernorm(t, None, 0.0, n.weight, n.bias, eps=n.eps)[1]                     # noqa: E731
-        add_ln = lambda t, y, n: ops.add_layernorm(t, y, 1.0, n.weight, n.bias, eps=n.eps, want_x=False)[1]   # noqa: E731
-        x = dec.embed[0].weight.index_select(0, st.in_token) * self.xscale + self.pe.index_select(0, st.in_pos)
-        n = 4
-        for layer, cache, mem_kv in zip(dec.decoders, self.caches, self.mem_kv):
-            w_qkv, b_qkv, _, _ = _stacked(layer)
-            sa, ca, ff = layer.self_attn, layer.src_attn, layer.feed_forward
-            pre = layer.normalize_before
-            qkv = proj(ln(x, layer.norm1) if pre else x, w_qkv, b_qkv)
-            att = ops.mha_step_paths(qkv, cache, st.path, st.in_len, st.new_row, st.need, H)
-            if pre:
-                x = proj(att, sa.linear_out.weight, sa.linear_out.bias, residual=x)
-            else:
-                x = add_ln(x, proj(att, sa.linear_out.weight, sa.linear_out.bias), layer.norm1)
-            q = proj(ln(x, layer.norm2) if pre else x, ca.linear_q.weight, ca.linear_q.bias)
-            att = ops.mha_rows(q, mem_kv[:, :d], mem_kv[:, d:], self.q_off, self.kv_off, self.kv_len, H, False)
-            if pre:
-                x = proj(att, ca.linear_out.weight, ca.linear_out.bias, residual=x)
-            else:
-                x = add_ln(x, proj(att, ca.linear_out.weight, ca.linear_out.bias), layer.norm2)
-            h = proj(ln(x, layer.norm3) if pre else x, ff.w_1.weight, ff.w_1.bias, act=act)
-            if pre:
-                x = proj(h, ff.w_2.weight, ff.w_2.bias, residual=x)
-            else:
-                x = add_ln(x, proj(h, ff.w_2.weight, ff.w_2.bias), layer.norm3)
-            n += 11
-        if dec.normalize_before:
-            x = ln(x, dec.after_norm)
-            n += 1
+        hidden row goes to the dump row).  Returns its launches."""
+        st = self.state
+        x = self.decoder_pass(st.in_token, st.in_pos)
         self.hidden.index_copy_(0, st.store_row.long(), x)         # the masked store: rows without need land in the dump row
-        return n + 2
+        return pass_launches(self.dec) + 2
 
     def frame(self, t: int, last: bool):
         ops, dec, st = self.ops, self.dec, self.state
