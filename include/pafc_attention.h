@@ -7,6 +7,7 @@
  * (beam, L, V) log-softmax to read L + 1 numbers of each.  Here all hypotheses of all utterances are packed as rows without
  * padding (hypothesis i owns L_i + 1 rows), an utterance's memory is projected once, and two kernels do what the GEMMs do
  * not: multi-head attention over row groups, and log p(target) per row straight from the logits.
+ * pafc_mha_band is the encoder-side attention of the Conformer baseline (limited context, positional term).
  * Conventions as in pafc_wkv6.h.
  */
 #ifndef PAFC_ATTENTION_H
@@ -42,6 +43,29 @@ int pafc_mha_rows(int dtype, int G, int H, int dk, const void *q, long ldq, cons
  * a row gives NaN for that row, as log_softmax does; -inf logits are ordinary (a row of nothing but -inf gives NaN). */
 int pafc_logp_gather_rows(int dtype, long rows, int V, const void *logits, long ldl, const int32_t *target, float *out,
                           pafc_stream_t stream);
+
+/* Limited-context self-attention with the positional term of the Conformer baseline (limited_rel_selfattn with
+ * global_tokens = 0: wenet/transformer/attention.py:406-645 of the reference), one launch for every batch row, head and query:
+ *   out[b*T + i, h*dk : (h+1)*dk] = sum_j softmax_j(s_ij) v[b*T + j, h]   over the keys j with |j - i| <= w, 0 <= j < t_pad,
+ *   s_ij = ((q[b*T + i, h] + u[h]) . k[b*T + j, h] + (q[b*T + i, h] + v_bias[h]) . p[j, h]) / sqrt(dk)    for j < T;
+ * p[j] is the KEY's position row (no relative shift) and is shared by the batch.  The keys T <= j < t_pad are the zero padding
+ * of the reference's blocked layout and are NOT masked: score 0, value 0, so each adds exp(0 - max) to its queries'
+ * denominators and nothing to their numerators.  They are arithmetic here: no operand has a row T or later.  Any
+ * t_pad >= T is taken (the reference's is T rounded up to a multiple of 2w); with w >= t_pad every query sees every key: full
+ * attention with the positional term.  There is no length mask (the reference applies none): a batch row's padded frames
+ * take part as keys with whatever they hold and get output rows.
+ * dtype: PAFC_F32 (both products on the fp32 matrix cores: exact products, fp32 accumulation) or PAFC_BF16 (bf16 matrix
+ *   cores, fp32 accumulation, q + u and q + v rounded to bf16 once, the probabilities rounded to bf16 for PV); the softmax is
+ *   online over key tiles in fp32.
+ * q: rows of ldq elements; k, v: rows of ldkv elements (three pointers into one stacked [Q | K | V] projection with
+ *   ldq = ldkv, or separate buffers); p: (T) rows of ldp elements; out: rows of ldo elements; all B*T rows except p.
+ *   Every pitch >= H*dk and a multiple of 16 bytes.  pos_bias_u, pos_bias_v: (H, dk) contiguous, in `dtype`.
+ *   q, k, v, p, pos_bias_u, pos_bias_v, out 16-byte aligned.  Row offsets are 64-bit.
+ * B, H in [1, 65535], 1 <= T <= t_pad <= 2^30, w >= 0 (w = 0: a query sees itself, and the padding keys none).
+ * dk != 64: PAFC_ERR_UNSUPPORTED.  No workspace; two runs on the same input give the same bits. */
+int pafc_mha_band(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq, const void *k,
+                  const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u, const void *pos_bias_v,
+                  void *out, long ldo, pafc_stream_t stream);
 
 /* ---- the training half: the attention decoder's loss on packed rows (one group per utterance, [sos] + y) ---- */
 

@@ -61,6 +61,7 @@ SIGNATURES = {
     # include/pafc_attention.h
     "pafc_mha_rows": (I, [I, I, I, I, P, G, P, P, G, P, P, P, I, P, G, P]),
     "pafc_logp_gather_rows": (I, [I, G, I, P, G, P, P, P]),
+    "pafc_mha_band": (I, [I, I, I, I, I, I, I, P, G, P, P, G, P, G, P, P, P, G, P]),
     "pafc_mha_rows_lse": (I, [I, I, I, I, P, G, P, P, G, P, P, P, I, P, G, P, P]),
     "pafc_mha_rows_bwd_workspace_bytes": (Z, [G, I]),
     "pafc_mha_rows_bwd": (I, [I, I, I, I, G, P, G, P, P, G, P, G, P, G, P, P, P, P, I, P, G, P, P, G, P, Z, P]),

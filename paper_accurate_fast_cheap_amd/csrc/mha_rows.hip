@@ -2,7 +2,8 @@
 // groups, and log p(target) per row straight from the logits.
 //
 // pafc_mha_rows.  One block per (group, head), four waves; a wave owns the 16-query tiles t = wave, wave + 4, ... of the group
-// and walks the keys in tiles with an online softmax.  Both products are computed TRANSPOSED, so that no value changes lanes
+// and walks the keys in tiles with an online softmax (the softmax step, the PV product and the output store are
+// mha_tile_body.h, shared with mha_band.hip).  Both products are computed TRANSPOSED, so that no value changes lanes
 // between them:
 //   S^T (keys x queries) = K Q^T     lane l holds S^T[key 4(l>>4) + r][query l&15] in register r = 0..3 (the C/D map)
 //   O^T (dk x queries)  = V^T P^T    and exactly that register is the B operand P^T[k-slot l>>4][query l&15] of the second
@@ -18,23 +19,11 @@
 // pafc_mha_rows_lse is the same kernel instantiated with one more store per query row and head, lse = m + log(l), for the
 // backward (mha_rows_bwd.hip); the arithmetic of `out` is untouched, so it carries the same bits.
 #include "pafc_attention.h"
-#include "pafc_common.h"
-
-#include <math.h>
+#include "mha_tile_body.h"
 
 namespace pafc {
 
-constexpr int kDk = 64;
 constexpr int kMhaWaves = 4;
-
-__device__ __forceinline__ float max_over_lane_groups(float x) {
-    x = fmaxf(x, __shfl_xor(x, 16, kWave));
-    return fmaxf(x, __shfl_xor(x, 32, kWave));
-}
-__device__ __forceinline__ float sum_over_lane_groups(float x) {
-    x += __shfl_xor(x, 16, kWave);
-    return x + __shfl_xor(x, 32, kWave);
-}
 
 struct MhaArgs {
     int H;
@@ -45,54 +34,6 @@ struct MhaArgs {
     void *out; long ldo;
     float *lse;          // (rows, H) m + log(l) of every query row and head: the LSE instantiations only
 };
-
-// One online-softmax step of a lane's query over NR masked scores s[] (already scaled): updates m, l, rescales o, leaves the
-// probabilities in s.  ROUND: the probabilities as bf16 values.
-template <int NR, bool ROUND>
-__device__ __forceinline__ void softmax_step(float *s, float &m, float &l, f32x4 *o) {
-    float tmax = s[0];
-#pragma unroll
-    for (int r = 1; r < NR; ++r) tmax = fmaxf(tmax, s[r]);
-    const float m_new = fmaxf(m, max_over_lane_groups(tmax));   // finite from the first tile on: key 0 is visible to every query
-    const float alpha = expf(m - m_new);                         // (m = -inf before the first tile: 0)
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        float p = expf(s[r] - m_new);
-        if (ROUND) p = round_bf16(p);
-        s[r] = p;
-        psum += p;
-    }
-    l = l * alpha + sum_over_lane_groups(psum);
-    m = m_new;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] *= alpha;
-}
-
-template <typename ET>
-__device__ __forceinline__ void store_tile(const MhaArgs &a, int h, long row, bool valid, int lq, const f32x4 *o, float inv);
-template <>
-__device__ __forceinline__ void store_tile<float>(const MhaArgs &a, int h, long row, bool valid, int lq, const f32x4 *o,
-                                                 float inv) {
-    if (!valid) return;
-    float *op = (float *)a.out + row * a.ldo + h * kDk + lq * 4;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        *reinterpret_cast<float4 *>(op + 16 * c) = make_float4(o[c][0] * inv, o[c][1] * inv, o[c][2] * inv, o[c][3] * inv);
-}
-template <>
-__device__ __forceinline__ void store_tile<bf16_t>(const MhaArgs &a, int h, long row, bool valid, int lq, const f32x4 *o,
-                                                 float inv) {
-    if (!valid) return;
-    bf16_t *op = (bf16_t *)a.out + row * a.ldo + h * kDk + lq * 4;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        uint2 w;
-        w.x = pack_bf16_rne(o[c][0] * inv, o[c][1] * inv);
-        w.y = pack_bf16_rne(o[c][2] * inv, o[c][3] * inv);
-        *reinterpret_cast<uint2 *>(op + 16 * c) = w;
-    }
-}
 
 // fp32: one 16-query tile against keys [0, kend)
 template <bool LSE>
@@ -125,12 +66,9 @@ __device__ __forceinline__ void mha_tile(const MhaArgs &a, float, int h, int q0,
             vp[r] = vbase + (long)(kv0 + min(key, nkv - 1)) * a.ldkv + lr;
         }
         softmax_step<4, false>(s, m, l, o);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[r][16 * c], s[r], o[c], 0, 0, 0);
+        pv_tile_f32(s, vp, o);
     }
-    store_tile<float>(a, h, (long)q0 + qidx, qidx < nq, lq, o, 1.f / l);
+    store_tile<float>(a.out, a.ldo, h, (long)q0 + qidx, qidx < nq, lq, o, 1.f / l);
     if (LSE && lq == 0 && qidx < nq) a.lse[((long)q0 + qidx) * a.H + h] = m + logf(l);
 }
 
@@ -165,18 +103,9 @@ __device__ __forceinline__ void mha_tile(const MhaArgs &a, bf16_t, int h, int q0
         }
         softmax_step<8, true>(s, m, l, o);
         // element j of the PV operands is key k0 + 4 lq + j (j < 4) or k0 + 16 + 4 lq + j - 4: the order s[] is in
-        u32x4 pb;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pb[j] = pack_bf16_exact(s[2 * j], s[2 * j + 1]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            u32x4 va;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) va[j] = (uint32_t)vp[2 * j][16 * c] | ((uint32_t)vp[2 * j + 1][16 * c] << 16);
-            o[c] = mfma_bf16_packed(va, pb, o[c]);
-        }
+        pv_tile_bf16(s, vp, o);
     }
-    store_tile<bf16_t>(a, h, (long)q0 + qidx, qidx < nq, lq, o, 1.f / l);
+    store_tile<bf16_t>(a.out, a.ldo, h, (long)q0 + qidx, qidx < nq, lq, o, 1.f / l);
     if (LSE && lq == 0 && qidx < nq) a.lse[((long)q0 + qidx) * a.H + h] = m + logf(l);
 }
 
@@ -191,7 +120,7 @@ template <typename ET, bool LSE> __global__ __launch_bounds__(kMhaWaves * kWave)
         if (nkv <= 0) {                                   // no keys: zeros
             const f32x4 z[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             const int qidx = 16 * t + (lane & 15);
-            store_tile<ET>(a, h, (long)q0 + qidx, qidx < nq, lane >> 4, z, 0.f);
+            store_tile<ET>(a.out, a.ldo, h, (long)q0 + qidx, qidx < nq, lane >> 4, z, 0.f);
             if (LSE && lane < 16 && qidx < nq) a.lse[((long)q0 + qidx) * a.H + h] = -INFINITY;       // the sum over no keys
             continue;
         }

@@ -3485,6 +3485,59 @@ def mha_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_off: torch.Ten
     return out
 
 
+def mha_band(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, pos_bias_u: torch.Tensor,
+             pos_bias_v: torch.Tensor, batch: int, heads: int, w: int, t_pad: Optional[int] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Limited-context self-attention with the positional term (include/pafc_attention.h: pafc_mha_band), one launch for every
+    batch row, head and query tile.  q, k, v (batch * T, >= H * 64): 2-D fp32 or bf16 with unit stride along the heads, row
+    b * T + i = frame i of batch row b (column slices of one stacked Q | K | V projection are fine; k and v share a row pitch);
+    p (T, >= H * 64): the projected position rows, shared by the batch; pos_bias_u / pos_bias_v (H, 64) contiguous.  Query i
+    sees the keys j with |j - i| <= w, 0 <= j < t_pad; the keys of [T, t_pad) are the reference's unmasked zero padding (score
+    0, value 0) and are never read.  t_pad None: T rounded up to a multiple of 2 w, the reference's value.  Returns out
+    (batch * T, H * 64)."""
+    d = heads * 64
+    for name, t in (("q", q), ("k", k), ("v", v), ("p", p)):
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype or t.shape[1] < d:
+            raise _lib.PafcError(f"mha_band: {name} is a 2-D GPU tensor of q's dtype with at least H * 64 columns and unit stride "
+                                 f"along them")
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.PafcError(f"mha_band: fp32 or bf16 operands, got {q.dtype}")
+    if batch < 1 or heads < 1 or q.shape[0] % batch:
+        raise _lib.PafcError(f"mha_band: q has {q.shape[0]} rows, not a multiple of batch = {batch}")
+    T = q.shape[0] // batch
+    if T < 1 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0] or p.shape[0] != T:
+        raise _lib.PafcError(f"mha_band: q, k, v hold batch * T rows and p holds T = {T} rows "
+                             f"(k {k.shape[0]}, v {v.shape[0]}, p {p.shape[0]})")
+    if k.stride(0) != v.stride(0):
+        raise _lib.PafcError("mha_band: k and v must share their row pitch")
+    if w < 0:
+        raise _lib.PafcError(f"mha_band: w = {w} is negative")
+    if t_pad is None:
+        t_pad = -(-T // (2 * w)) * 2 * w if w > 0 else T
+    if t_pad < T:
+        raise _lib.PafcError(f"mha_band: t_pad = {t_pad} is below T = {T}")
+    per16 = 16 // q.element_size()
+    for name, t in (("q", q), ("k", k), ("v", v), ("p", p)):
+        if t.stride(0) % per16 or t.data_ptr() % 16:
+            raise _lib.PafcError(f"mha_band: {name} needs a 16-byte aligned base and a row pitch that is a multiple of 16 bytes")
+    for name, t in (("pos_bias_u", pos_bias_u), ("pos_bias_v", pos_bias_v)):
+        if not t.is_cuda or t.dtype != q.dtype or tuple(t.shape) != (heads, 64) or not t.is_contiguous() or t.data_ptr() % 16:
+            raise _lib.PafcError(f"mha_band: {name} is a contiguous, 16-byte aligned (H, 64) GPU tensor of q's dtype")
+    if out is None:
+        out = torch.empty(q.shape[0], d, dtype=q.dtype, device=q.device)
+    elif (not out.is_cuda or out.dtype != q.dtype or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (q.shape[0], d)
+          or out.stride(0) % per16 or out.data_ptr() % 16):
+        raise _lib.PafcError("mha_band: out is (batch * T, H * 64) in the operands' dtype, 16-byte aligned rows")
+    from .profiling import op_timer
+    # 384 flop per (query, key) pair: a 128-deep score and a 64-wide PV; the band's corners counted as full (an upper figure)
+    with op_timer("mha_band_w%d" % w, sample=12, flops=384.0 * batch * heads * T * min(T, 2 * w + 1)):
+        rc = _lib.lib().pafc_mha_band(_lib.dtype_code(q.dtype), batch, T, heads, 64, int(w), int(t_pad), _lib.ptr(q), q.stride(0),
+                                      _lib.ptr(k), _lib.ptr(v), k.stride(0), _lib.ptr(p), p.stride(0), _lib.ptr(pos_bias_u),
+                                      _lib.ptr(pos_bias_v), _lib.ptr(out), out.stride(0), _lib.stream_of(q))
+    _lib.check(rc, "pafc_mha_band")
+    return out
+
+
 def logp_gather_rows(logits: torch.Tensor, target: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[r] = logits[r, target[r]] - logsumexp(logits[r]) (include/pafc_attention.h: pafc_logp_gather_rows): the logits are
     read once, the (rows, V) log-softmax is never formed.  logits (rows, V) fp32 / bf16 with unit stride along V, target (rows)

@@ -15,6 +15,10 @@ from .layer_norm import LayerNorm
 
 
 class ConvolutionModule(nn.Module):
+    # inference on the GPU: the two pointwise convolutions on this package's GEMMs instead of the library's (see
+    # PositionwiseFeedForward.own_gemm)
+    own_gemm: bool = False
+
     def __init__(self, channels: int, kernel_size: int = 15, activation: nn.Module = nn.ReLU(),
                  norm: str = "batch_norm", causal: bool = False, bias: bool = True):
         super().__init__()
@@ -43,6 +47,9 @@ class ConvolutionModule(nn.Module):
                 cache: torch.Tensor = torch.zeros((0, 0, 0))) -> Tuple[torch.Tensor, torch.Tensor]:
         """x (B, T, C), mask_pad (B, 1, T) or (0,0,0), cache (B, C, lorder) for causal -> (B, T, C), new_cache."""
         from ..hip_ops import depthwise_conv1d_cl, depthwise_conv1d_cl_autograd, linear
+        if self.own_gemm and x.is_cuda and not torch.is_grad_enabled():
+            from ..hip_ops import linear_fused
+            linear = lambda t, w, b: linear_fused(t, w, b, "none", split_ok=False)     # noqa: E731
         keep = mask_pad.transpose(1, 2) if mask_pad.size(2) > 0 else None  # (B, T, 1)
         if keep is not None:
             # masked_fill(~keep, 0) as ONE kernel each way: masked_fill = clone + fill, its mask a bitwise_not, and its autograd the

@@ -3,8 +3,9 @@
 Reference: wenet/transformer/encoder.py:38-402 (BaseEncoder: forward, forward_chunk, forward_chunk_by_chunk)
 and :453-602 (ConformerEncoder: slot constructor arguments :545-569, layer list :589-602).  Same constructor
 keys as conf/rwkv/*.yaml `encoder_conf`, same sub-module names (embed, encoders.N, after_norm, global_cmvn),
-same return shapes.  Scope: num_langs == 0 and the recurrent slot keys; the MHA baseline, the LSL variant and
-the plain TransformerEncoder are not part of the accelerated path.
+same return shapes.  Scope: num_langs == 0, the recurrent slot keys and the Conformer baseline's limited-context attention
+(`limited_rel_selfattn`, inference, on the module path); full-context MHA, the LSL variant and the plain TransformerEncoder
+are not part of the accelerated path.
 """
 import os
 from .layer_norm import LayerNorm
@@ -61,6 +62,9 @@ class BaseEncoder(torch.nn.Module):
         self._graphs = {}
         self._graphs_token = None              # the parameter state the cached graphs were captured on (_weights_token)
         self._wt_epoch, self._wt_tensors = None, []
+        # a slot that reads pos_emb (limited_rel_selfattn): the embedding hands out an empty placeholder, the encoder
+        # fetches the position rows itself (_slot_pos_emb)
+        self.slot_reads_pos_emb = False
         # a checkpoint load rewrites parameters in place (Tensor._version moves) and may be followed by anything: new epoch
         self.register_load_state_dict_post_hook(_post_load_bump)
 
@@ -89,6 +93,14 @@ class BaseEncoder(torch.nn.Module):
 
     def output_size(self) -> int:
         return self._output_size
+
+    def _slot_pos_emb(self, xs: torch.Tensor, pos_emb: torch.Tensor, offset: int) -> torch.Tensor:
+        """The pos_emb the layers get: for a slot that reads positions, rows [offset, offset + T') of the sinusoid table in the
+        model's dtype (the embedding's own pos_emb is an empty placeholder: nothing on the recurrent path reads it).  No host
+        read, nothing that depends on the lengths: a hipGraph capture passes through."""
+        if not self.slot_reads_pos_emb:
+            return pos_emb
+        return self.embed.pos_enc.position_encoding(offset, xs.size(1), apply_dropout=False, device=xs.device).to(xs.dtype)
 
     def multi_stream_safe(self) -> bool:
         """May several forward passes of this encoder be in flight on different HIP streams?  Only when every GEMM of the pass is
@@ -220,6 +232,7 @@ class BaseEncoder(torch.nn.Module):
         if self.global_cmvn is not None:
             xs = self.global_cmvn(xs)
         xs, pos_emb, masks = self.embed(xs, masks)
+        pos_emb = self._slot_pos_emb(xs, pos_emb, 0)
         mask_pad = masks
         chunk_masks = add_optional_chunk_mask(xs, masks, self.use_dynamic_chunk, self.use_dynamic_left_chunk,
                                               decoding_chunk_size, self.static_chunk_size, num_decoding_left_chunks)
@@ -254,7 +267,13 @@ class BaseEncoder(torch.nn.Module):
         if self.global_cmvn is not None:
             xs = self.global_cmvn(xs)
         xs, pos_emb, _ = self.embed(xs, tmp_masks, offset)
+        pos_emb = self._slot_pos_emb(xs, pos_emb, int(offset))       # the chunk's positions start at `offset`
         elayers = att_cache.size(0)
+        # what the next call is handed of the attention cache (encoder.py:304-309,327 of the reference): a no-op on the
+        # zero-sized caches of the recurrent slots
+        key_size = att_cache.size(2) + xs.size(1)
+        next_cache_start = 0 if required_cache_size < 0 else key_size if required_cache_size == 0 \
+            else max(key_size - required_cache_size, 0)
         plan = self._fused(xs)
         # a causal conv module threads its left context from call to call (encoder.py:311-337, convolution.py:113-126): the
         # layer-by-layer path below hands the caches on; the fused executor serves the cache-free (non-causal) chunk
@@ -273,7 +292,7 @@ class BaseEncoder(torch.nn.Module):
                 xs, att_mask, pos_emb, cat_embs=cat_embs,
                 att_cache=att_cache[i:i + 1] if elayers > 0 else att_cache,
                 cnn_cache=cnn_cache[i] if cnn_cache.size(0) > 0 else cnn_cache)
-            r_att_cache.append(new_att_cache)
+            r_att_cache.append(new_att_cache[:, :, next_cache_start:, :])
             r_cnn_cache.append(new_cnn_cache.unsqueeze(0))
         if self.normalize_before:
             xs = self.after_norm(xs)
@@ -590,8 +609,9 @@ class ConformerEncoder(BaseEncoder):
             raise NotImplementedError("language-specific layers (num_langs > 0) are outside the accelerated path")
         if selfattention_layer_type not in WENET_ATTENTION_CLASSES:
             raise NotImplementedError(
-                f"selfattention_layer_type={selfattention_layer_type!r}: only the recurrent slot keys "
-                f"{sorted(WENET_ATTENTION_CLASSES)} are implemented here (the MHA baseline is out of scope)")
+                f"selfattention_layer_type={selfattention_layer_type!r}: the slot keys implemented here are "
+                f"{sorted(WENET_ATTENTION_CLASSES)} (of the multi-head-attention keys only the Conformer baseline's "
+                f"limited-context 'limited_rel_selfattn'; full-context attention is not)")
         activation = WENET_ACTIVATION_CLASSES[activation_type]()
         self.num_langs = num_langs
         # encoder.py:545-561: (head_size, dim_att, num_blocks, version, direction, ctx_len, do_bfloat16) + layer_id
@@ -599,6 +619,10 @@ class ConformerEncoder(BaseEncoder):
                      rwkv_ctx_len, rwkv_do_bfloat16)
         if selfattention_layer_type == "mamba_att":   # encoder.py:563-569
             slot_args = (output_size // attention_heads, output_size, num_blocks, rnn_att_version, rnn_att_direction)
+        baseline = selfattention_layer_type == "limited_rel_selfattn"
+        if baseline:                                  # encoder.py:533-543: the "limited" keys' argument tuple
+            slot_args = (attention_heads, output_size, attention_dropout_rate, key_bias, att_context_size, global_tokens,
+                         global_tokens_spacing, global_attn_separate)
         ff_args = (output_size, linear_units, dropout_rate, activation)
         conv_args = (output_size, cnn_module_kernel, activation, cnn_module_norm, causal)
         self.encoders = torch.nn.ModuleList([
@@ -614,5 +638,14 @@ class ConformerEncoder(BaseEncoder):
         # fp32 products outside the layers (the subsampling Linear; the CTC head via init_model): split operands on the bf16 matrix
         # cores (~2^-16 relative) only in a model whose slot rounds to bf16 anyway -- a pure-fp32 model (rwkv_do_bfloat16: False,
         # the 1e-3 parity configuration) keeps exact fp32 products everywhere (hip_ops.DISPATCH: split_gemm_min_rows)
-        self.fp32_split_operands = bool(selfattention_layer_type != "mamba_att" and rwkv_do_bfloat16)
+        self.fp32_split_operands = bool(selfattention_layer_type != "mamba_att" and rwkv_do_bfloat16 and not baseline)
         self.embed.fp32_split_operands = self.fp32_split_operands
+        if baseline:
+            # The baseline has no bf16 slot: an fp32 model is pure fp32.  Its layers run on the module path (no fused schedule
+            # for this slot), where the feed-forward and convolution modules' projections would be the framework's library
+            # GEMM: they are sent to this package's GEMMs instead, as the slot's own projections are.
+            self.slot_reads_pos_emb = True
+            for layer in self.encoders:
+                for m in (layer.feed_forward, layer.feed_forward_macaron, layer.conv_module):
+                    if m is not None:
+                        m.own_gemm = True

@@ -4,6 +4,11 @@ import torch
 
 
 class PositionwiseFeedForward(torch.nn.Module):
+    # inference on the GPU: both projections on this package's GEMMs (hip_ops.linear_fused, exact fp32 products in an fp32
+    # model) instead of nn.Linear's library GEMM.  Set by an encoder whose layers run on the module path (the Conformer
+    # baseline); the recurrent models' layers take the fused executor and leave it off.
+    own_gemm: bool = False
+
     def __init__(self, idim: int, hidden_units: int, dropout_rate: float,
                  activation: torch.nn.Module = torch.nn.ReLU(), bias: bool = True):
         super().__init__()
@@ -21,4 +26,9 @@ class PositionwiseFeedForward(torch.nn.Module):
             else:
                 h = self.dropout(self.activation(h))
             return linear(h, self.w_2.weight, self.w_2.bias)
+        if self.own_gemm and xs.is_cuda:
+            from ..hip_ops import linear_fused
+            silu = isinstance(self.activation, torch.nn.SiLU)
+            h = linear_fused(xs, self.w_1.weight, self.w_1.bias, "silu" if silu else "none", split_ok=False)
+            return linear_fused(self.dropout(h if silu else self.activation(h)), self.w_2.weight, self.w_2.bias, "none", split_ok=False)
         return self.w_2(self.dropout(self.activation(self.w_1(xs))))
