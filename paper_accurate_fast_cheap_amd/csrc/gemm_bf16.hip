@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const GemmParams p) {
         for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int fr = lane & 15, kq = lane >> 4;
-    issue(0, 0);
+    if (iters > 0) issue(0, 0);   // (a K share may be empty: it fetches nothing and leaves a zero partial)
     if constexpr (NST >= 3) {
 #pragma unroll
         for (int s_ = 1; s_ < NST - 1; ++s_)
@@ -560,7 +560,13 @@ F32outPlan f32out_plan(long M, int N, int Kw, bool may_split = true) {
     }
     if (const char *e = getenv("PAFC_F32OUT_KSPLIT")) {      // A/B runs: force the factor (1-8)
         const int v = atoi(e);
-        if (v >= 1 && v <= 8 && iters >= v && may_split) pl.S = v;
+        if (v >= 1 && v <= 8 && iters >= v && may_split) {
+            // shares are ceil(iters / S) K-steps each: fewer shares until the last one is not empty (9 K-steps in 4 shares
+            // would be 3, 3, 3, 0 -- a block with nothing to walk)
+            int s = v;
+            while (s > 1 && (long)(s - 1) * ((iters + s - 1) / s) >= iters) --s;
+            pl.S = s;
+        }
     }
     return pl;
 }

@@ -70,6 +70,26 @@ PLAIN_FORMS = {
 }
 FORMS = {**SHARED_FRAGMENT_FORMS, **HI_LO_HI_FORMS, **PLAIN_FORMS}
 
+# what the small tiles of csrc/gemm_bf16.hip take beyond that (pafc_gemm_bf16_f32out_pb: every activation with an fp32 or a
+# planes output, an fp32 residual behind an activation; pafc_gemm_bf16: a bf16 residual behind an activation, GLU over
+# blocks of 64 -- operands["glu_half"] = GLU64_HALF)
+GLU64_HALF = 64
+SMALL_TILE_FORMS = {
+    "f32-res-inplace": Form(False, "f32", "none", "f32"),
+    "f32-silu": Form(False, "f32", "silu", None),
+    "f32-tanh": Form(False, "f32", "tanh", None),
+    "f32-relu": Form(False, "f32", "relu", None),
+    "f32-silu-res": Form(False, "f32", "silu", "f32"),
+    "split-f32-silu": Form(True, "f32", "silu", None),
+    "split-f32-tanh": Form(True, "f32", "tanh", None),
+    "split-f32-relu": Form(True, "f32", "relu", None),
+    "split-f32-silu-res": Form(True, "f32", "silu", "f32"),
+    "bf16-silu-res": Form(False, "bf16", "silu", "bf16"),
+    "bf16-tanh-res": Form(False, "bf16", "tanh", "bf16"),
+    "bf16-relu-res": Form(False, "bf16", "relu", "bf16"),
+    "bf16-glu64": Form(False, "bf16", "glu", None),
+}
+
 
 def split_hi_lo(x: torch.Tensor):
     """fp32 x -> bf16 (hi, lo) with hi = bf16(x), lo = bf16(x - hi): x = hi + lo to 2^-16 relative."""
@@ -237,3 +257,51 @@ def make_operands(form: Form, M: int, N: int, K: int, seed: int, batch: int = 0,
     ops["residual"] = None if form.res is None else (r.bfloat16() if form.res == "bf16" else r)
     ops["a32"], ops["w32"] = a, w                # the fp32 operands the planes were split from
     return {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in ops.items()}
+
+
+def make_grid_operands(form: Form, M: int, N: int, K: int, seed: int, plane_block: int = 0, alpha: float = 1.0,
+                       glu_half: int = 32, device="cpu") -> dict:
+    """Operands on a grid, for which fp32 accumulation is EXACT in any order and in any number of K shares: the hi plane of
+    A (or a plain A) and the weights are integers in [-3, 3]; the lo plane of A, lo_w, the bias and the residual are integers
+    times 2^-6 (in [-3, 3] 2^-6 and [-31, 31] 2^-6).  A kernel multiplies the planes it is given: they need not be the
+    hi / lo split of anything.  With alpha 1 or 0.5 every product, every partial sum and every step of the epilogue before
+    the activation is then a multiple of 2^-7 below 2^17 -- an fp32 number -- as the precondition asserted here says:
+
+        max(|A| |W|^T + |bias| + |residual|) 2^7 < 2^24
+
+    so `round_to(form, ideal(form, ops))` is what a correct kernel gives BIT FOR BIT for act "none", and a K-step that is
+    dropped, walked twice or taken from the wrong plane changes nearly every element (tests/test_gemm_ref.py)."""
+    assert alpha in (1.0, 0.5), alpha
+    g = torch.Generator().manual_seed(seed)
+    ints = lambda lim, *s: torch.randint(-lim, lim + 1, s, generator=g).float()
+    No = N // 2 if form.act == "glu" else N
+    ops = {"alpha": alpha, "plane_block": plane_block, "glu_half": glu_half}
+    if form.a_split:
+        hi, lo = ints(3, M, K), ints(3, M, K) * 2.0 ** -6
+        if plane_block:
+            sh = (M, K // plane_block, plane_block)
+            A = torch.cat([hi.reshape(sh), lo.reshape(sh)], dim=-1).reshape(M, 2 * K)
+        else:
+            A = torch.cat([hi, lo], dim=-1)
+        hi_w = ints(3, N, K)
+        W = torch.cat([hi_w, hi_w, ints(3, N, K) * 2.0 ** -6], dim=-1)
+    else:
+        A, W = ints(3, M, K), ints(3, N, K)
+    b, r = ints(31, N) * 2.0 ** -6, ints(31, M, No) * 2.0 ** -6
+    ops["A"], ops["W"] = A.bfloat16(), W.bfloat16()
+    assert torch.equal(ops["A"].float(), A) and torch.equal(ops["W"].float(), W)
+    ops["bias"] = b.bfloat16() if form.out == "bf16" else b
+    ops["residual"] = None if form.res is None else (r.bfloat16() if form.res == "bf16" else r)
+    ops = {k: (v.to(device) if isinstance(v, torch.Tensor) else v) for k, v in ops.items()}
+    assert grid_bits(form, ops) < 24.0, (form, M, N, K, grid_bits(form, ops))
+    return ops
+
+
+def grid_bits(form: Form, ops: dict) -> float:
+    """log2 of max(|A| |W|^T + |bias| + |residual|) 2^7: the significand bits the grid operands' sums need (< 24: exact)."""
+    import math
+    _, Sp, _ = products(form, ops)
+    S = Sp + _row_vec(ops.get("bias")).abs()
+    if ops.get("residual") is not None and form.act != "glu":
+        S = S + ops["residual"].double().abs()
+    return math.log2(float(S.max()) * 2.0 ** 7)

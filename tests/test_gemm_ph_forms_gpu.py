@@ -34,72 +34,17 @@ import functools
 import pytest
 import torch
 
-from tests import gemm_ref, parity_log
+from tests import gemm_launch, gemm_ref, parity_log
 from tests.gemm_ref import FORMS, HI_LO_HI_FORMS, PLAIN_FORMS, SHARED_FRAGMENT_FORMS
 
 pytestmark = pytest.mark.gpu
 
 TILES = [64, 128, 192, 256]
 MMAX = 2 * 256 + 7
-SENTINEL = 7.0
-_ACT = {"none": 0, "silu": 1, "tanh": 2, "relu": 3, "glu": 4}
-_OUT = {"bf16": 0, "f32": 1, "planes": 2}
-_RES = {None: 0, "bf16": 1, "f32": 2}
-ERR_BAD_DIMS, ERR_UNSUPPORTED = -2, -7
-
-
-def _padded(t, pad, fill=float("nan")):
-    """t (..., rows, cols) inside rows `pad` elements wider; the padding holds NaN: a read of it shows in the result."""
-    if not pad:
-        return t.contiguous()
-    buf = torch.full(t.shape[:-1] + (t.shape[-1] + pad,), fill, dtype=t.dtype, device=t.device)
-    buf[..., :t.shape[-1]] = t
-    return buf
-
-
-def _launch(L, form, ops, tile_m, pad=0, lo_gap=0, inplace=False, overrides=None, min_ldo=0):
-    """Lay the operands out (rows `pad` elements wider than the row, lo plane `lo_gap` columns behind the hi plane, the
-    output inside a sentinel-filled buffer with 64 guard rows per batch entry), call pafc_gemm_ph_ex2.
-    -> (rc, result as float64 (..., M, No), True if every element outside the output kept the sentinel)."""
-    from paper_accurate_fast_cheap_amd import _lib
-    A, W, bias, res = ops["A"], ops["W"], ops.get("bias"), ops.get("residual")
-    batched = A.dim() == 3
-    Z = A.shape[0] if batched else 1
-    M, N = A.shape[-2], W.shape[-2]
-    K = W.shape[-1] // 3 if form.a_split else W.shape[-1]
-    No = N // 2 if form.act == "glu" else N
-    planes = form.out == "planes"
-    lo_off = No + lo_gap if planes else 0
-    ldo = max((lo_off + No if planes else No) + pad, min_ldo)
-    Ab, Wb = _padded(A, pad), _padded(W, pad)
-    out = torch.full((Z, M + 64, ldo), SENTINEL, dtype=torch.float32 if form.out == "f32" else torch.bfloat16, device=A.device)
-    if res is not None and inplace:
-        out[:, :M, :No] = res
-        Rb, ldr, sR = out, ldo, out.stride(0)
-    elif res is not None:
-        Rb = _padded(res, pad)
-        ldr, sR = Rb.stride(-2), (Rb.stride(0) if batched else 0)
-    else:
-        Rb, ldr, sR = None, 0, 0
-    if bias is not None:
-        bias = bias.contiguous()
-    args = dict(M=M, N=N, K=K, batch=Z, A=_lib.ptr(Ab), lda=Ab.stride(-2), strideA=Ab.stride(0) if batched else 0,
-                a_split=int(form.a_split), a_plane_block=int(ops.get("plane_block", 0)), W=_lib.ptr(Wb), ldw=Wb.stride(-2),
-                strideW=Wb.stride(0) if batched else 0, bias=_lib.ptr(bias),
-                strideBias=bias.stride(0) if (bias is not None and bias.dim() == 2) else 0, residual=_lib.ptr(Rb),
-                res_kind=_RES[form.res] if res is not None else 0, ldr=ldr, strideR=sR, out=_lib.ptr(out), out_kind=_OUT[form.out],
-                ldo=ldo, lo_off=lo_off, strideO=out.stride(0), alpha=float(ops.get("alpha", 1.0)), act=_ACT[form.act],
-                tile_m=tile_m, stream=_lib.stream_of(A))
-    args.update(overrides or {})
-    rc = L.pafc_gemm_ph_ex2(*args.values())
-    body = out[:, :M]
-    got = gemm_ref.planes_value(body, No, lo_off) if planes else body[..., :No].double()
-    keep = torch.ones_like(out, dtype=torch.bool)
-    keep[:, :M, :No] = False
-    if planes:
-        keep[:, :M, lo_off:lo_off + No] = False
-    clean = bool((out[keep] == SENTINEL).all())
-    return rc, (got if batched else got[0]), clean, out
+ERR_BAD_DIMS, ERR_UNSUPPORTED = gemm_launch.ERR_BAD_DIMS, gemm_launch.ERR_UNSUPPORTED
+# the buffer layout (NaN-padded rows, sentinel-guarded output, lo_off gap), the launch and the verdict: tests/gemm_launch.py,
+# shared with the battery of the small tiles (tests/test_gemm_small_tiles_gpu.py)
+SENTINEL, _padded, _launch, _judge = gemm_launch.SENTINEL, gemm_launch.padded, gemm_launch.launch_ph, gemm_launch.judge
 
 
 @functools.lru_cache(maxsize=None)
@@ -133,20 +78,6 @@ def _shapes(form, tile_m):
     shapes = [(m, n0, k0) for m in (1, tile_m - 1, tile_m, tile_m + 1, mr)]
     shapes += [(mr, n, k) for n in ((256, 768) if glu else (8, 264, 512, 1000)) for k in (128, 384, 1024) if (n, k) != (n0, k0)]
     return shapes
-
-
-def _judge(form, ops, rc, got, clean):
-    """-> (problem or None, worst err / bound, activation term)"""
-    if rc != 0:
-        return "rc %d" % rc, float("inf"), 0.0
-    want = gemm_ref.ideal(form, ops)
-    act_t = gemm_ref.activation_term(form, ops)
-    ratio = float(((got - want).abs() / gemm_ref.bound(form, ops, act_t)).max())
-    if not bool(torch.isfinite(got).all()):
-        return "not finite", float("inf"), act_t
-    if not clean:
-        return "wrote outside the output", ratio, act_t
-    return (None if ratio <= 1.0 else "err / bound = %.3g" % ratio), ratio, act_t
 
 
 def _run_form(hip, family, name, tile_m):
