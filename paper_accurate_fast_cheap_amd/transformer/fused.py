@@ -35,6 +35,18 @@ _DIR_DROP_SLOTS = (RWKV_TmixWrapper_bidirectional_direction_dropout, RWKV_TmixWr
 _RWKV_SLOTS = (RWKV_TmixWrapper, RWKV_TmixWrapper_bidirectional) + _DIR_DROP_SLOTS
 
 
+def _fold_norm(w: torch.Tensor, b: Optional[torch.Tensor], norm: nn.LayerNorm, interleave: int = 0):
+    """A LayerNorm folded into the projection (w, b) that consumes it: (W' = bf16(gamma * W), b' = b + W beta, csum = fp32 row
+    sums of the ROUNDED W': what the MFMA multiplies); interleave = the GLU block half the rows of W' / b' are re-ordered for."""
+    wf = w.float()
+    bf = (b.float() if b is not None else 0) + wf @ norm.bias.float()
+    wp = (wf * norm.weight.float()).to(torch.bfloat16)
+    if interleave:
+        wp, bf = hip_ops.glu_interleave(wp, interleave), hip_ops.glu_interleave(bf, interleave)
+    wp = wp.contiguous()
+    return wp, bf.to(torch.bfloat16).contiguous(), wp.float().sum(-1).contiguous()
+
+
 class LayerPlan:
     """Stacked / pre-transposed views of one layer's parameters for the batched GEMMs (rebuilt when stale)."""
 
@@ -134,19 +146,10 @@ class LayerPlan:
                 and cm is not None and cm.pointwise_conv1.weight.shape[0] % 256 == 0 and cm.lorder == 0
                 and os.environ.get("PAFC_LN_FOLD", "1") != "0"):
             return
-
-        def fold(w, b, norm, interleave=False):
-            wf, g, be = w.float(), norm.weight.float(), norm.bias.float()
-            bf = (b.float() if b is not None else 0) + wf @ be
-            wp = (wf * g).to(torch.bfloat16)
-            if interleave:
-                wp, bf = hip_ops.glu_interleave(wp, 32), hip_ops.glu_interleave(bf, 32)
-            return wp.contiguous(), bf.to(torch.bfloat16).contiguous(), wp.float().sum(-1).contiguous()
-
         pw1 = cm.pointwise_conv1
-        self.lnf = dict(ffm=fold(L.feed_forward_macaron.w_1.weight, L.feed_forward_macaron.w_1.bias, L.norm_ff_macaron),
-                        ff=fold(L.feed_forward.w_1.weight, L.feed_forward.w_1.bias, L.norm_ff),
-                        pw1=fold(pw1.weight.squeeze(-1), pw1.bias, L.norm_conv, interleave=True))
+        self.lnf = dict(ffm=_fold_norm(L.feed_forward_macaron.w_1.weight, L.feed_forward_macaron.w_1.bias, L.norm_ff_macaron),
+                        ff=_fold_norm(L.feed_forward.w_1.weight, L.feed_forward.w_1.bias, L.norm_ff),
+                        pw1=_fold_norm(pw1.weight.squeeze(-1), pw1.bias, L.norm_conv, interleave=32))
 
     def carry_folds(self):
         """The chunk step's two LayerNorms whose consumer is a few-rows projection -- ln_x -> output, norm_ff -> w_1 -- folded
@@ -156,16 +159,9 @@ class LayerPlan:
             self._carry_folds[2].use()
             return self._carry_folds[1]
         L = self.layer
-
-        def fold(w, b, norm):
-            wf, g, be = w.float(), norm.weight.float(), norm.bias.float()
-            bf = (b.float() if b is not None else 0) + wf @ be
-            wp = (wf * g).to(torch.bfloat16).contiguous()
-            return wp, bf.to(torch.bfloat16).contiguous(), wp.float().sum(-1).contiguous(), norm.eps
-
-        folds = dict(ff=fold(L.feed_forward.w_1.weight, L.feed_forward.w_1.bias, L.norm_ff))
+        folds = dict(ff=_fold_norm(L.feed_forward.w_1.weight, L.feed_forward.w_1.bias, L.norm_ff) + (L.norm_ff.eps,))
         if self.rwkv:
-            folds["out"] = fold(self.Wo, None, self.blocks[0].ln_x)
+            folds["out"] = _fold_norm(self.Wo, None, self.blocks[0].ln_x) + (self.blocks[0].ln_x.eps,)
         self._carry_folds = (self._stamp, folds, hip_ops.DerivedFill())
         return folds
 
@@ -214,16 +210,21 @@ class LayerPlan:
         self.Wo = (wo * 0.5 if self.ndir == 2 else wo).contiguous()                    # /2 is exact in bf16
 
 
+def _layer_shape_common(layer: nn.Module) -> bool:
+    """What every fused schedule asks of a layer: pre-norm, macaron FFN, a conv module with LayerNorm, SiLU throughout."""
+    cm = layer.conv_module
+    return (layer.normalize_before and layer.feed_forward_macaron is not None and cm is not None
+            and cm.use_layer_norm and isinstance(cm.activation, nn.SiLU)
+            and isinstance(layer.feed_forward.activation, nn.SiLU)
+            and isinstance(layer.feed_forward_macaron.activation, nn.SiLU))
+
+
 def eligible(layer: nn.Module) -> bool:
     from .mamba2 import MambaAttWrapper
     slot = layer.self_attn
     if type(slot) not in _RWKV_SLOTS + (MambaAttWrapper,):
         return False
-    cm = layer.conv_module
-    return (layer.normalize_before and layer.feed_forward_macaron is not None and cm is not None
-            and cm.use_layer_norm and isinstance(cm.activation, nn.SiLU)
-            and isinstance(layer.feed_forward.activation, nn.SiLU)
-            and isinstance(layer.feed_forward_macaron.activation, nn.SiLU) and cm.kernel_size in (3, 7, 15, 31)
+    return (_layer_shape_common(layer) and layer.conv_module.kernel_size in (3, 7, 15, 31)
             and layer.size % 8 == 0 and layer.size <= 1024)
 
 
@@ -252,19 +253,15 @@ def proj(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], act: st
          residual: Optional[torch.Tensor] = None, inplace: bool = False) -> torch.Tensor:
     """act(alpha * x w^T + bias) + residual as ONE GEMM with a fused epilogue (no caller passes an activation together with a
     residual); w in nn.Linear layout (N, K)."""
-    if _own_gemm(x, w):
-        N, K = w.shape
-        x2 = x.reshape(-1, K)
-        r2 = residual.reshape(-1, N) if residual is not None else None
-        out = hip_ops.gemm_bf16(x2, w, bias, act, alpha=alpha, residual=r2, out=r2 if (inplace and r2 is not None) else None)
-        return out.view(x.shape[:-1] + (N,))
-    if _skinny(x, w):      # a streaming chunk: few rows, launch-bound
-        N, K = w.shape
-        x2 = x.reshape(-1, K)
-        r2 = residual.reshape(-1, N) if residual is not None else None
-        out = hip_ops.gemm_skinny(x2, w, bias, act, alpha=alpha, residual=r2, out=r2 if (inplace and r2 is not None) else None)
-        return out.view(x.shape[:-1] + (N,))
-    return hip_ops.linear_bias_act(x, w, bias, act, alpha=alpha, residual=residual, inplace=inplace)
+    own = _own_gemm(x, w)
+    if not (own or _skinny(x, w)):
+        return hip_ops.linear_bias_act(x, w, bias, act, alpha=alpha, residual=residual, inplace=inplace)
+    gemm = hip_ops.gemm_bf16 if own else hip_ops.gemm_skinny      # skinny: a streaming chunk, few rows, launch-bound
+    N, K = w.shape
+    x2 = x.reshape(-1, K)
+    r2 = residual.reshape(-1, N) if residual is not None else None
+    out = gemm(x2, w, bias, act, alpha=alpha, residual=r2, out=r2 if (inplace and r2 is not None) else None)
+    return out.view(x.shape[:-1] + (N,))
 
 
 def _ffn_residual(ff: nn.Module, h: torch.Tensor, x: torch.Tensor, scale: float, b2_scaled: torch.Tensor,
@@ -273,6 +270,41 @@ def _ffn_residual(ff: nn.Module, h: torch.Tensor, x: torch.Tensor, scale: float,
     written once and the pre-norm that follows reads ONE tensor."""
     hid = proj(h, ff.w_1.weight, ff.w_1.bias, "silu")
     return proj(hid, ff.w_2.weight, b2_scaled, "none", alpha=scale, residual=x, inplace=inplace)
+
+
+def _ffn_split(ff: nn.Module, w1: torch.Tensor, w2: torch.Tensor, hp: torch.Tensor, x: torch.Tensor, scale: float,
+               b2_scaled: torch.Tensor, inplace: bool) -> torch.Tensor:
+    """_ffn_residual of the fp32 layer on split operands: hp = planes of the normalised rows, w1 / w2 the split weights; the
+    hidden tensor travels as planes, the fp32 stream x takes the add in the w_2 epilogue."""
+    B, T, C = x.shape
+    M = B * T
+    hid = hip_ops.gemm_ph_ex(hp.view(M, 2 * C), w1, ff.w_1.bias, "silu", a_split=True, out_kind="planes")
+    out = x.view(M, C) if inplace else torch.empty((M, C), dtype=torch.float32, device=x.device)
+    return hip_ops.gemm_ph_ex(hid, w2, b2_scaled, alpha=scale, residual=x.view(M, C), out=out, a_split=True,
+                              out_kind="f32").view(B, T, C)
+
+
+def _ffn_lnfold(plan: "LayerPlan", key: str, ff: nn.Module, b2_scaled: torch.Tensor, x2: torch.Tensor, st: torch.Tensor,
+                eps: float, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """_ffn_residual with the pre-norm folded into w_1: x2 = the UN-normalised rows (M, C), st = their statistics, plan.lnf[key]
+    the folded w_1; the sum goes to ``out`` (x2 itself for the in-place add) or to a fresh tensor."""
+    w, b, cs = plan.lnf[key]
+    hid = hip_ops.gemm_bf16_ln(x2, w, b, st, act="silu", csum=cs, eps=eps)
+    return hip_ops.gemm_bf16(hid, ff.w_2.weight, b2_scaled, "none", alpha=plan.layer.ff_scale, residual=x2, out=out)
+
+
+def _ffn_chunk_lnfold(plan: "LayerPlan", x2: torch.Tensor) -> torch.Tensor:
+    """The second FFN of a chunk step, added to its rows x2 (M, C) in place: norm_ff folded into the few-rows w_1 GEMM, which
+    forms the rows' statistics itself (LayerPlan.carry_folds)."""
+    L = plan.layer
+    w1, b1, cs1, ep1 = plan.carry_folds()["ff"]
+    hid = hip_ops.gemm_skinny(x2, w1, b1, "silu", ln_self=True, ln_csum=cs1, ln_eps=ep1)
+    return proj(hid, L.feed_forward.w_2.weight, plan.b2, "none", alpha=L.ff_scale, residual=x2, inplace=True)
+
+
+def _ln(norm: nn.LayerNorm, x: torch.Tensor, y: Optional[torch.Tensor] = None, **kw):
+    """hip_ops.add_layernorm of x (+ y) with gamma, beta and eps of ONE module; returns its (x_new or x, out1, out2)."""
+    return hip_ops.add_layernorm(x, y, 1.0, norm.weight, norm.bias, eps=norm.eps, **kw)
 
 
 def _pw1_glu(plan: "LayerPlan", h2: torch.Tensor) -> torch.Tensor:
@@ -342,8 +374,7 @@ def slot_forward(plan: LayerPlan, h: torch.Tensor, residual: Optional[torch.Tens
         ys = (wkv6_forward(rkv[0].view(B, T, C), rkv[1].view(B, T, C), rkv[2].view(B, T, C), w[0].view(B, T, C),
                            plan.u[0], reverse=rev),)
     for d, y in enumerate(ys):
-        ln = plan.blocks[d].ln_x
-        hip_ops.add_layernorm(y.view(M, C), None, 1.0, ln.weight, ln.bias, out1=ycat[:, d * C:(d + 1) * C], eps=ln.eps)
+        _ln(plan.blocks[d].ln_x, y.view(M, C), out1=ycat[:, d * C:(d + 1) * C])
     if residual is not None and residual.dtype == torch.float32 and ycat.dtype == torch.bfloat16:
         # bf16 slot inside an fp32 stream: the output projection adds straight into the fp32 residual (rwkv_wrapper_
         # bidirectional.py:55-56 `.float()` + encoder_layer.py:232), one rounding less than cast + add
@@ -364,13 +395,36 @@ def _dwconv_norm_silu(cm, p: torch.Tensor, left_pad: int, T: int) -> torch.Tenso
         return hip_ops.depthwise_conv1d_cl_ln_silu(p, cm.depthwise_conv.weight, cm.depthwise_conv.bias, left_pad, T,
                                                    cm.norm.weight, cm.norm.bias, cm.norm.eps)
     dw = hip_ops.depthwise_conv1d_cl(p, cm.depthwise_conv.weight, cm.depthwise_conv.bias, left_pad, T)
-    return hip_ops.add_layernorm(dw, None, 1.0, cm.norm.weight, cm.norm.bias, silu=True, eps=cm.norm.eps)[1]
+    return _ln(cm.norm, dw, silu=True)[1]
+
+
+def _causal_pad(cm, h: torch.Tensor, T: int):
+    """The conv module's input with its left padding: (h, left_pad of the depthwise convolution, rows per sequence).  A causal
+    module zero-pads lorder frames BEFORE pointwise_conv1 (convolution.py:112-118), so the left context the depthwise
+    convolution sees is GLU(bias), not zero -- the zero frames are prepended here as well."""
+    if cm.lorder > 0:
+        return torch.cat([h.new_zeros(h.shape[0], cm.lorder, h.shape[2]), h], dim=1), 0, T + cm.lorder
+    return h, (cm.kernel_size - 1) // 2, T
+
+
+def _final_norms(L: nn.Module, x: torch.Tensor, next_norm: Optional[nn.LayerNorm], *, split_next: bool = False):
+    """The tail of every schedule: (out = norm_final(x), next_norm(out) or None) -- the next layer's first pre-norm, or the
+    encoder's after_norm.  One pass for the pair when the two share an epsilon (the kernel takes one), else two passes;
+    split_next: next_norm(out) comes as split-operand planes."""
+    nf = L.norm_final
+    if next_norm is None:
+        return _ln(nf, x, want_x=False)[1], None
+    if next_norm.eps == nf.eps:
+        _, out, hn = _ln(nf, x, want_x=False, gamma2=next_norm.weight, beta2=next_norm.bias, split2=split_next)
+        return out, hn
+    out = _ln(nf, x, want_x=False)[1]
+    return out, _ln(next_norm, out, want_x=False, split1=split_next)[1]
 
 
 def layer_forward(plan: LayerPlan, x: torch.Tensor, h: torch.Tensor, lens: Optional[torch.Tensor],
                   next_norm: Optional[nn.LayerNorm]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """x: residual stream (B, T, C); h = norm_ff_macaron(x), already computed by the previous step.
-    Returns (layer output = norm_final(...), next_norm(layer output) or None)."""
+    Returns (layer output, next_norm(layer output) or None): _final_norms."""
     L = plan.layer
     B, T, C = x.shape
     slot_dtype = torch.bfloat16 if plan.slot_bf16 else x.dtype
@@ -380,25 +434,18 @@ def layer_forward(plan: LayerPlan, x: torch.Tensor, h: torch.Tensor, lens: Optio
     # first add of a layer writes a fresh tensor (the incoming stream may be a caller-visible layer output), the
     # later ones update the layer-private stream in place.
     x = _ffn_residual(L.feed_forward_macaron, h, x, L.ff_scale, plan.b2_macaron, inplace=False)
-    _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_mha.weight, L.norm_mha.bias, out_dtype=slot_dtype, want_x=False, eps=L.norm_mha.eps)
+    h = _ln(L.norm_mha, x, out_dtype=slot_dtype, want_x=False)[1]
     if not plan.rwkv:
         # another slot from the registry (Mamba-2): the module as is; the rest of the layer stays re-scheduled
         att = L.self_attn(h, h, h)[0]
-        x, h, _ = hip_ops.add_layernorm(x, att.to(x.dtype).contiguous(), 1.0, L.norm_conv.weight, L.norm_conv.bias,
-                                        zero_rows=masked, lens=lens, T=T, eps=L.norm_conv.eps)
+        x, h, _ = _ln(L.norm_conv, x, att.to(x.dtype).contiguous(), zero_rows=masked, lens=lens, T=T)
     elif slot_dtype == x.dtype:
         x = slot_forward(plan, h, residual=x)
-        _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_conv.weight, L.norm_conv.bias, zero_rows=masked, lens=lens,
-                                        T=T, want_x=False, eps=L.norm_conv.eps)
+        h = _ln(L.norm_conv, x, zero_rows=masked, lens=lens, T=T, want_x=False)[1]
     else:
         att = slot_forward(plan, h).to(x.dtype)
-        x, h, _ = hip_ops.add_layernorm(x, att, 1.0, L.norm_conv.weight, L.norm_conv.bias, zero_rows=masked, lens=lens, T=T, eps=L.norm_conv.eps)
-    left_pad, Tc = (cm.kernel_size - 1) // 2, T
-    if cm.lorder > 0:
-        # causal module: the reference zero-pads lorder frames BEFORE pointwise_conv1 (convolution.py:112-118), so the
-        # left context the depthwise convolution sees is GLU(bias), not zero -- prepend the zero frames here as well
-        h = torch.cat([h.new_zeros(B, cm.lorder, C), h], dim=1)
-        left_pad, Tc = 0, T + cm.lorder
+        x, h, _ = _ln(L.norm_conv, x, att, zero_rows=masked, lens=lens, T=T)
+    h, left_pad, Tc = _causal_pad(cm, h, T)
     if plan.pw1_glu is not None and h.dtype == torch.bfloat16:
         # F.glu rides on pointwise_conv1 (half the write, and the depthwise kernel no longer recomputes sigmoids)
         p = _pw1_glu(plan, h.view(B * Tc, C)).view(B, Tc, C)
@@ -406,23 +453,15 @@ def layer_forward(plan: LayerPlan, x: torch.Tensor, h: torch.Tensor, lens: Optio
     else:
         p = hip_ops.linear_bias_act(h, cm.pointwise_conv1.weight.squeeze(-1), cm.pointwise_conv1.bias, "none")
         dw = hip_ops.depthwise_conv1d_cl(p, cm.depthwise_conv.weight, cm.depthwise_conv.bias, left_pad, T, glu=True)
-        _, g, _ = hip_ops.add_layernorm(dw, None, 1.0, cm.norm.weight, cm.norm.bias, silu=True, eps=cm.norm.eps)
+        g = _ln(cm.norm, dw, silu=True)[1]
     if not masked:
         x = proj(g, cm.pointwise_conv2.weight.squeeze(-1), cm.pointwise_conv2.bias, "none", residual=x, inplace=True)
-        _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_ff.weight, L.norm_ff.bias, want_x=False, eps=L.norm_ff.eps)
+        h = _ln(L.norm_ff, x, want_x=False)[1]
     else:   # padded frames of the conv branch count as zero (convolution.py:140-141): the add stays in the norm pass
         c = proj(g, cm.pointwise_conv2.weight.squeeze(-1), cm.pointwise_conv2.bias)
-        x, h, _ = hip_ops.add_layernorm(x, c, 1.0, L.norm_ff.weight, L.norm_ff.bias, lens=lens, T=T, mask_y=True, eps=L.norm_ff.eps)
+        x, h, _ = _ln(L.norm_ff, x, c, lens=lens, T=T, mask_y=True)
     x = _ffn_residual(L.feed_forward, h, x, L.ff_scale, plan.b2, inplace=True)
-    if next_norm is not None and next_norm.eps != L.norm_final.eps:      # the one-pass pair shares one epsilon
-        _, out, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False,
-                                          eps=L.norm_final.eps)
-        _, hn, _ = hip_ops.add_layernorm(out, None, 1.0, next_norm.weight, next_norm.bias, want_x=False, eps=next_norm.eps)
-        return out, hn
-    _, out, hn = hip_ops.add_layernorm(x, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False,
-                                       gamma2=next_norm.weight if next_norm is not None else None,
-                                       beta2=next_norm.bias if next_norm is not None else None, eps=L.norm_final.eps)
-    return out, hn
+    return _final_norms(L, x, next_norm)
 
 
 def lnfold_eligible(plan: LayerPlan, x: torch.Tensor, lens: Optional[torch.Tensor]) -> bool:
@@ -436,63 +475,29 @@ def layer_forward_lnfold(plan: LayerPlan, x: torch.Tensor, st: torch.Tensor, nex
     """layer_forward for the long unmasked bf16 case with the three projection-feeding pre-norms folded into their GEMMs:
     the residual GEMM that produces a row also writes its (sum, sum of squares), the projection that follows reads the
     UN-normalised row and normalises in its epilogue -- norm_ff_macaron(x), norm_conv(x), norm_ff(x) never exist in memory
-    (two of the layer's seven LayerNorm passes, and norm_final's second output, are gone).
+    (two of the layer's seven LayerNorm passes, and the tail's second output, are gone).
     x: residual stream, st: its row statistics (rows, 8, 2).  Returns (layer output, its statistics or next_norm(output))."""
-    L, F = plan.layer, plan.lnf
+    L = plan.layer
     B, T, C = x.shape
     M = B * T
     cm = L.conv_module
     G = hip_ops.gemm_bf16_ln
     new_stats = lambda: torch.empty((M, 8, 2), dtype=torch.float32, device=x.device)
-    x2 = x.view(M, C)
-    w, b, cs = F["ffm"]
-    rb = _FFN_ROW_BLOCK
-    if rb > 0:
-        # experiment (PAFC_FFN_ROW_BLOCK=<rows>): w_1 -> w_2 per row block, so that the block's hidden slice (rows x 2048 bf16) is
-        # still in the 256 MiB Infinity Cache when w_2 reads it back.  Measured and NOT the default: DESIGN section 4, round 5
-        xn = torch.empty_like(x2)
-        for r0 in range(0, M, rb):
-            r1 = min(M, r0 + rb)
-            hb = G(x2[r0:r1], w, b, st[r0:r1], act="silu", csum=cs, eps=L.norm_ff_macaron.eps)
-            hip_ops.gemm_bf16(hb, L.feed_forward_macaron.w_2.weight, plan.b2_macaron, "none", alpha=L.ff_scale, residual=x2[r0:r1], out=xn[r0:r1])
-        x2 = xn
-    else:
-        hid = G(x2, w, b, st, act="silu", csum=cs, eps=L.norm_ff_macaron.eps)
-        x2 = hip_ops.gemm_bf16(hid, L.feed_forward_macaron.w_2.weight, plan.b2_macaron, "none", alpha=L.ff_scale, residual=x2)
-    _, h, _ = hip_ops.add_layernorm(x2.view(B, T, C), None, 1.0, L.norm_mha.weight, L.norm_mha.bias, want_x=False, eps=L.norm_mha.eps)
+    x2 = _ffn_lnfold(plan, "ffm", L.feed_forward_macaron, plan.b2_macaron, x.view(M, C), st, L.norm_ff_macaron.eps, None)
+    h = _ln(L.norm_mha, x2.view(B, T, C), want_x=False)[1]
     st2 = new_stats()
     slot_forward(plan, h, residual=x2.view(B, T, C), stats=st2)
-    w, b, cs = F["pw1"]
+    w, b, cs = plan.lnf["pw1"]
     p = G(x2, w, b, st2, act="glu", csum=cs, eps=L.norm_conv.eps).view(B, T, C)
     g = _dwconv_norm_silu(cm, p, (cm.kernel_size - 1) // 2, T)
     st3 = new_stats()
     G(g.view(M, C), cm.pointwise_conv2.weight.squeeze(-1), cm.pointwise_conv2.bias, st3, residual=x2, out=x2)
-    w, b, cs = F["ff"]
-    if rb > 0:
-        for r0 in range(0, M, rb):
-            r1 = min(M, r0 + rb)
-            hb = G(x2[r0:r1], w, b, st3[r0:r1], act="silu", csum=cs, eps=L.norm_ff.eps)
-            hip_ops.gemm_bf16(hb, L.feed_forward.w_2.weight, plan.b2, "none", alpha=L.ff_scale, residual=x2[r0:r1], out=x2[r0:r1])
-    else:
-        hid = G(x2, w, b, st3, act="silu", csum=cs, eps=L.norm_ff.eps)
-        hip_ops.gemm_bf16(hid, L.feed_forward.w_2.weight, plan.b2, "none", alpha=L.ff_scale, residual=x2, out=x2)
+    _ffn_lnfold(plan, "ff", L.feed_forward, plan.b2, x2, st3, L.norm_ff.eps, x2)
     xo = x2.view(B, T, C)
     if next_fold:       # the next layer's first pre-norm is folded too: it wants this layer's output and its statistics
         stn = new_stats()
-        _, out, _ = hip_ops.add_layernorm(xo, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, eps=L.norm_final.eps,
-                                          stats_out1=stn)
-        return out, stn
-    if next_norm is not None and next_norm.eps != L.norm_final.eps:
-        _, out, _ = hip_ops.add_layernorm(xo, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, eps=L.norm_final.eps)
-        _, hn, _ = hip_ops.add_layernorm(out, None, 1.0, next_norm.weight, next_norm.bias, want_x=False, eps=next_norm.eps)
-        return out, hn
-    _, out, hn = hip_ops.add_layernorm(xo, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False,
-                                       gamma2=next_norm.weight if next_norm is not None else None,
-                                       beta2=next_norm.bias if next_norm is not None else None, eps=L.norm_final.eps)
-    return out, hn
-
-
-_FFN_ROW_BLOCK = int(os.environ.get("PAFC_FFN_ROW_BLOCK", "0"))
+        return _ln(L.norm_final, xo, want_x=False, stats_out1=stn)[1], stn
+    return _final_norms(L, xo, next_norm)
 
 
 # fp32 streams of a model with the bf16 slot shorter than this take exact fp32 products (csrc/gemm_f32.hip); from here on the
@@ -517,22 +522,11 @@ def layer_forward_split(plan: LayerPlan, x: torch.Tensor, hp: torch.Tensor, lens
     masked = lens is not None
     cm = L.conv_module
     G = hip_ops.gemm_ph_ex
-
-    def ffn(ff, w1, w2, b2_scaled, hpl, xr, inplace):
-        hid = G(hpl.view(M, 2 * C), w1, ff.w_1.bias, "silu", a_split=True, out_kind="planes")
-        out = xr.view(M, C) if inplace else torch.empty((M, C), dtype=torch.float32, device=xr.device)
-        return G(hid, w2, b2_scaled, alpha=L.ff_scale, residual=xr.view(M, C), out=out, a_split=True, out_kind="f32").view(B, T, C)
-
-    x = ffn(L.feed_forward_macaron, S["ffm_w1"], S["ffm_w2"], plan.b2_macaron, hp, x, False)
-    _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_mha.weight, L.norm_mha.bias, out_dtype=torch.bfloat16, want_x=False,
-                                    eps=L.norm_mha.eps)
+    x = _ffn_split(L.feed_forward_macaron, S["ffm_w1"], S["ffm_w2"], hp, x, L.ff_scale, plan.b2_macaron, inplace=False)
+    h = _ln(L.norm_mha, x, out_dtype=torch.bfloat16, want_x=False)[1]
     x = slot_forward(plan, h, residual=x)
-    _, hc, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_conv.weight, L.norm_conv.bias, zero_rows=masked, lens=lens, T=T,
-                                     want_x=False, eps=L.norm_conv.eps, split1=True)
-    left_pad, Tc = (cm.kernel_size - 1) // 2, T
-    if cm.lorder > 0:    # causal module: lorder zero frames in front of pointwise_conv1 (convolution.py:112-118)
-        hc = torch.cat([hc.new_zeros(B, cm.lorder, 2 * C), hc], dim=1)
-        left_pad, Tc = 0, T + cm.lorder
+    hc = _ln(L.norm_conv, x, zero_rows=masked, lens=lens, T=T, want_x=False, split1=True)[1]
+    hc, left_pad, Tc = _causal_pad(cm, hc, T)
     if B * Tc <= hip_ops._SPLIT_SMALL_MAX_ROWS and B * Tc * 2 * C <= (1 << 22):
         # few rows (the small-tile kernel has no GLU epilogue): the plain projection, F.glu inside the depthwise convolution
         p = G(hc.view(B * Tc, 2 * C), S["pw1_plain"], cm.pointwise_conv1.bias, a_split=True, out_kind="f32").view(B, Tc, 2 * C)
@@ -540,26 +534,16 @@ def layer_forward_split(plan: LayerPlan, x: torch.Tensor, hp: torch.Tensor, lens
     else:
         p = G(hc.view(B * Tc, 2 * C), S["pw1"], S["pw1_b"], "glu", a_split=True, out_kind="f32").view(B, Tc, C)
         dw = hip_ops.depthwise_conv1d_cl(p, cm.depthwise_conv.weight, cm.depthwise_conv.bias, left_pad, T)
-    _, g, _ = hip_ops.add_layernorm(dw, None, 1.0, cm.norm.weight, cm.norm.bias, silu=True, eps=cm.norm.eps, split1=True)
+    g = _ln(cm.norm, dw, silu=True, split1=True)[1]
     if not masked:
         x2 = x.view(M, C)
         G(g.view(M, 2 * C), S["pw2"], cm.pointwise_conv2.bias, residual=x2, out=x2, a_split=True, out_kind="f32")
-        _, h2, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_ff.weight, L.norm_ff.bias, want_x=False, eps=L.norm_ff.eps, split1=True)
+        h2 = _ln(L.norm_ff, x, want_x=False, split1=True)[1]
     else:   # padded frames of the conv branch count as zero (convolution.py:140-141): the add stays in the norm pass
         c = G(g.view(M, 2 * C), S["pw2"], cm.pointwise_conv2.bias, a_split=True, out_kind="f32").view(B, T, C)
-        x, h2, _ = hip_ops.add_layernorm(x, c, 1.0, L.norm_ff.weight, L.norm_ff.bias, lens=lens, T=T, mask_y=True,
-                                         eps=L.norm_ff.eps, split1=True)
-    x = ffn(L.feed_forward, S["ff_w1"], S["ff_w2"], plan.b2, h2, x, True)
-    if next_norm is not None and next_norm.eps != L.norm_final.eps:      # the one-pass pair shares one epsilon
-        _, out, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, eps=L.norm_final.eps)
-        _, hn, _ = hip_ops.add_layernorm(out, None, 1.0, next_norm.weight, next_norm.bias, want_x=False, eps=next_norm.eps,
-                                         split1=next_split)
-        return out, hn
-    _, out, hn = hip_ops.add_layernorm(x, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False,
-                                       gamma2=next_norm.weight if next_norm is not None else None,
-                                       beta2=next_norm.bias if next_norm is not None else None, eps=L.norm_final.eps,
-                                       split2=next_split and next_norm is not None)
-    return out, hn
+        x, h2, _ = _ln(L.norm_ff, x, c, lens=lens, T=T, mask_y=True, split1=True)
+    x = _ffn_split(L.feed_forward, S["ff_w1"], S["ff_w2"], h2, x, L.ff_scale, plan.b2, inplace=True)
+    return _final_norms(L, x, next_norm, split_next=next_split)
 
 
 def _carry_slot_ok(slot: nn.Module) -> bool:
@@ -579,11 +563,56 @@ def carry_eligible(layer: nn.Module, x: torch.Tensor) -> bool:
     """State-carrying chunk step through the fused kernels: uni-directional bf16 slot, causal conv; B concurrent streams
     of equal chunk length (B = 1 is the reference's forward_chunk contract, B > 1 is B independent streams per step)."""
     cm = layer.conv_module
-    return (cm is not None and _carry_slot_ok(layer.self_attn) and layer.normalize_before
-            and layer.feed_forward_macaron is not None and cm.use_layer_norm and cm.lorder > 0
-            and isinstance(cm.activation, nn.SiLU) and isinstance(layer.feed_forward.activation, nn.SiLU)
-            and isinstance(layer.feed_forward_macaron.activation, nn.SiLU) and cm.kernel_size <= 31
+    return (_layer_shape_common(layer) and _carry_slot_ok(layer.self_attn) and cm.lorder > 0 and cm.kernel_size <= 31
             and layer.size % 64 == 0 and layer.size <= 1024 and x.is_cuda and x.dtype == torch.bfloat16)
+
+
+def _chunk_slot_rwkv(plan: LayerPlan, h: torch.Tensor, x: torch.Tensor, shift: torch.Tensor, s_in: Optional[torch.Tensor], *,
+                     sk: bool, in_place: bool, out: Optional[torch.Tensor] = None):
+    """The uni-directional bf16 RWKV slot of a chunk step, from the LoRA down-projection to the output projection into the
+    residual stream: h (B, T, C) = norm_mha(x), shift (B, 1, C) = the frame before the chunk, which reaches the token-shift
+    kernels through their `prev` pointer, s_in = the carried scan state or None.  sk: a handful of rows -- the few-rows GEMM and
+    its fusions, with the sum written to ``out`` (M, C) when given, else over x; the other branches are the general kernels.
+    in_place: the scan writes the new state over s_in where it can.
+    Returns (x + slot output, the new state -- None when it was written over s_in --, h[:, -1:] = the next step's shift)."""
+    B, T, C = h.shape
+    M = B * T
+    # the chunk step is launch-bound: one kernel each for the two LoRA chains (one_pass)
+    if sk:   # token shift + lerp as the operand producer of the down-projection (one ~5 us launch)
+        t = hip_ops.gemm_skinny(h.view(M, C), plan.W1n[0], None, "tanh", mix_maa=plan.maa_x_n[0], mix_prev=shift, mix_T=T).view(1, M, -1)
+    else:
+        t = hip_ops.tmix_lora_down(h, plan.maa_x_n, plan.W1n, prev=shift, one_pass=True)
+    z = hip_ops.tmix_lora_mix4(h, t, plan.W2t, plan.maa4, prev=shift)                         # (4, 1, M, C)
+    if hip_ops.skinny_ok(M, C, C):
+        rkv = hip_ops.gemm_skinny(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
+    elif M >= _OWN_GEMM_MIN_ROWS:
+        rkv = hip_ops.gemm_bf16(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
+    else:
+        rkv = torch.bmm(z[:3].view(3, M, C), plan.Wrkv).view(3, B, T, C)
+    # (the decay chain and the r / k / v projections are independent, but as two branches of the captured graph -- a second HIP
+    # stream forked and joined by events -- the step got 25 % SLOWER, 1.33 -> 1.66 ms: cross-queue dependencies cost more than
+    # the 5 us they hide; one stream)
+    if sk and plan.D1n.shape[1] == 64:   # one short launch: bf16(tanh(z_w D1)) in LDS, then bf16(. D2) + time_decay, rounded
+        w = hip_ops.decay_lora_skinny(z[3].view(M, C), plan.D1n[0], plan.D2n[0], plan.time_decay.view(C)).view(B, T, C)   # as the op chain rounds
+    elif sk:
+        td = hip_ops.gemm_skinny(z[3].view(M, C), plan.D1n[0], None, "tanh")
+        w = hip_ops.gemm_skinny(td, plan.D2n[0], plan.time_decay.view(C), round_first=True).view(B, T, C)
+    else:
+        w = hip_ops.decay_lora(z[3].view(1, M, C), plan.D1n, plan.D2n, plan.time_decay.view(1, C), one_pass=True).view(B, T, C)
+    if in_place and s_in is not None and hip_ops.wkv6_single_chunk(B, T, C, plan.u[0].shape[0]):
+        y, _ = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, s_out=s_in)      # the state is updated where it lies
+        s_out = None
+    else:
+        y, s_out = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, want_state=True)
+    if sk:   # ln_x folded into the output projection
+        wo, bo, cso, epo = plan.carry_folds()["out"]
+        x2 = x.view(M, C)
+        x = hip_ops.gemm_skinny(y.view(M, C), wo, bo, residual=x2, out=x2 if out is None else out, ln_self=True, ln_csum=cso,
+                                ln_eps=epo).view(B, T, C)
+    else:
+        yn = _ln(plan.blocks[0].ln_x, y.view(M, C), want_x=False)[1]
+        x = proj(yn, plan.Wo, None, "none", residual=x.view(M, C), inplace=True).view(B, T, C)
+    return x, s_out, h[:, -1:]
 
 
 def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict], h0: Optional[torch.Tensor] = None,
@@ -594,7 +623,7 @@ def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict],
     so the step is built to be FEW launches: the frame before the chunk reaches the token-shift kernels through their `prev`
     pointer (no concatenation, no extra row to drop again), the scan starts from the carried state and -- `in_place`, the
     captured step of `stream_chunks`, whose carries are fixed buffers -- writes the new state over it, "shift" and "cnn" are
-    refreshed by one small copy each, and `norm_final` + the next layer's first pre-norm are one pass (h0 = that pre-norm of x
+    refreshed by one small copy each, and the final norm + the next layer's first pre-norm are one pass (h0 = that pre-norm of x
     when the previous layer already produced it; next_norm = the norm to apply to this layer's output for the next one).
     `pending` (with in_place): instead of copying, the (destination, source) pairs of the small carry refreshes are appended
     to it and the caller performs them all in ONE multi-tensor copy after the last layer.  A carry "cx" (B, lorder + T, C) --
@@ -607,10 +636,9 @@ def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict],
     M = B * T
     x = x.contiguous()
     if h0 is None:
-        _, h0, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_ff_macaron.weight, L.norm_ff_macaron.bias, want_x=False, eps=L.norm_ff_macaron.eps)
+        h0 = _ln(L.norm_ff_macaron, x, want_x=False)[1]
     x = _ffn_residual(L.feed_forward_macaron, h0, x, L.ff_scale, plan.b2_macaron, inplace=False)
-    _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_mha.weight, L.norm_mha.bias, want_x=False, eps=L.norm_mha.eps)
-    few = True                                           # the chunk step is launch-bound: one kernel each for the two LoRA chains
+    h = _ln(L.norm_mha, x, want_x=False)[1]
     sk = h.dtype == torch.bfloat16 and hip_ops.skinny_ok(M, C, C)     # a handful of rows: the few-rows GEMM and its fusions
     att = None                                           # a slot output still to be added to the stream (by the norm_conv pass)
     if not plan.rwkv:
@@ -634,64 +662,31 @@ def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict],
             shift = h.new_zeros(B, 1, C)
         elif shift.dtype != h.dtype or not shift.is_contiguous():
             shift = shift.to(h.dtype).contiguous()
-        if sk:   # token shift + lerp as the operand producer of the down-projection (one ~5 us launch)
-            t = hip_ops.gemm_skinny(h.view(M, C), plan.W1n[0], None, "tanh", mix_maa=plan.maa_x_n[0], mix_prev=shift, mix_T=T).view(1, M, -1)
-        else:
-            t = hip_ops.tmix_lora_down(h, plan.maa_x_n, plan.W1n, prev=shift, one_pass=few)
-        z = hip_ops.tmix_lora_mix4(h, t, plan.W2t, plan.maa4, prev=shift)                         # (4, 1, M, C)
-        if hip_ops.skinny_ok(M, C, C):
-            rkv = hip_ops.gemm_skinny(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
-        elif M >= _OWN_GEMM_MIN_ROWS:
-            rkv = hip_ops.gemm_bf16(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
-        else:
-            rkv = torch.bmm(z[:3].view(3, M, C), plan.Wrkv).view(3, B, T, C)
-        # (the decay chain and the r / k / v projections are independent, but as two branches of the captured graph -- a second HIP
-        # stream forked and joined by events -- the step got 25 % SLOWER, 1.33 -> 1.66 ms: cross-queue dependencies cost more than
-        # the 5 us they hide; one stream)
-        if sk and plan.D1n.shape[1] == 64:   # one short launch: bf16(tanh(z_w D1)) in LDS, then bf16(. D2) + time_decay, rounded
-            w = hip_ops.decay_lora_skinny(z[3].view(M, C), plan.D1n[0], plan.D2n[0], plan.time_decay.view(C)).view(B, T, C)   # as the op chain rounds
-        elif sk:
-            td = hip_ops.gemm_skinny(z[3].view(M, C), plan.D1n[0], None, "tanh")
-            w = hip_ops.gemm_skinny(td, plan.D2n[0], plan.time_decay.view(C), round_first=True).view(B, T, C)
-        else:
-            w = hip_ops.decay_lora(z[3].view(1, M, C), plan.D1n, plan.D2n, plan.time_decay.view(1, C), one_pass=few).view(B, T, C)
         s_in = carry.get("wkv")
         new = carry if in_place else {}
-        if in_place and s_in is not None and hip_ops.wkv6_single_chunk(B, T, C, plan.u[0].shape[0]):
-            y, _ = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, s_out=s_in)      # the state is updated where it lies
-        else:
-            y, s_out = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, want_state=True)
+        x, s_out, last = _chunk_slot_rwkv(plan, h, x, shift, s_in, sk=sk, in_place=in_place)
+        if s_out is not None:
             if in_place and s_in is not None:
                 s_in.copy_(s_out)
             else:
                 new["wkv"] = s_out
         if in_place and carry.get("shift") is not None and carry["shift"].dtype == h.dtype:
             if pending is not None:
-                pending.append((carry["shift"], h[:, -1:]))
+                pending.append((carry["shift"], last))
             else:
-                carry["shift"].copy_(h[:, -1:])           # (after the two passes that read the old one)
+                carry["shift"].copy_(last)                # (after the two passes that read the old one)
         else:
-            new["shift"] = h[:, -1:].contiguous()
-        ln = plan.blocks[0].ln_x
-        if sk:   # ln_x folded into the output projection
-            wo, bo, cso, epo = plan.carry_folds()["out"]
-            x2 = x.view(M, C)
-            x = hip_ops.gemm_skinny(y.view(M, C), wo, bo, residual=x2, out=x2, ln_self=True, ln_csum=cso, ln_eps=epo).view(B, T, C)
-        else:
-            _, yn, _ = hip_ops.add_layernorm(y.view(M, C), None, 1.0, ln.weight, ln.bias, eps=ln.eps, want_x=False)
-            x = proj(yn, plan.Wo, None, "none", residual=x.view(M, C), inplace=True).view(B, T, C)
+            new["shift"] = last.contiguous()
     cm = L.conv_module
     cnn = carry.get("cnn")
     cxb = carry.get("cx") if in_place else None
     if cxb is not None and B == 1 and cxb.shape == (1, cm.lorder + T, C) and cxb.dtype == x.dtype and T >= cm.lorder:
         cx = cxb                                      # rows [0, lorder) = the cache, the chunk's rows go behind them
-        xa, _, _ = hip_ops.add_layernorm(x, att, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=att is not None,
-                                         eps=L.norm_conv.eps, out1=cx[0, cm.lorder:])
+        xa, _, _ = _ln(L.norm_conv, x, att, want_x=att is not None, out1=cx[0, cm.lorder:])
         x = xa if att is not None else x
         cnn = None                                    # ("cnn" is rebuilt from cx by stream_chunks when the captured steps end)
     else:
-        xa, hc, _ = hip_ops.add_layernorm(x, att, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=att is not None,
-                                          eps=L.norm_conv.eps)
+        xa, hc, _ = _ln(L.norm_conv, x, att, want_x=att is not None)
         x = xa if att is not None else x
         left = cnn.transpose(1, 2).to(hc.dtype) if cnn is not None and cnn.numel() > 0 else hc.new_zeros(B, cm.lorder, C)
         cx = torch.cat([left, hc], dim=1)                                                     # (B, lorder + T, C)
@@ -723,23 +718,12 @@ def layer_forward_carry(plan: LayerPlan, x: torch.Tensor, carry: Optional[dict],
         x = hip_ops.gemm_skinny(dw.view(M, C), pw2.weight.view(C, C), pw2.bias, residual=x2, out=x2,
                                 norm_silu=(cm.norm.weight, cm.norm.bias, cm.norm.eps)).view(B, T, C)
     else:
-        _, g, _ = hip_ops.add_layernorm(dw, None, 1.0, cm.norm.weight, cm.norm.bias, silu=True, eps=cm.norm.eps)
-        x = proj(g, pw2.weight.squeeze(-1), pw2.bias, "none", residual=x, inplace=True)
-    if sk and hip_ops.skinny_ok(M, L.feed_forward.w_1.weight.shape[0], C):     # norm_ff folded into w_1
-        w1, b1, cs1, ep1 = plan.carry_folds()["ff"]
-        hid = hip_ops.gemm_skinny(x.view(M, C), w1, b1, "silu", ln_self=True, ln_csum=cs1, ln_eps=ep1)
-        x = proj(hid, L.feed_forward.w_2.weight, plan.b2, "none", alpha=L.ff_scale, residual=x.view(M, C), inplace=True).view(B, T, C)
+        x = proj(_ln(cm.norm, dw, silu=True)[1], pw2.weight.squeeze(-1), pw2.bias, "none", residual=x, inplace=True)
+    if sk and hip_ops.skinny_ok(M, L.feed_forward.w_1.weight.shape[0], C):
+        x = _ffn_chunk_lnfold(plan, x.view(M, C)).view(B, T, C)
     else:
-        _, h2, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_ff.weight, L.norm_ff.bias, want_x=False, eps=L.norm_ff.eps)
-        x = _ffn_residual(L.feed_forward, h2, x, L.ff_scale, plan.b2, inplace=True)
-    if next_norm is not None and next_norm.eps == L.norm_final.eps:        # the one-pass pair shares one epsilon
-        _, out, hn = hip_ops.add_layernorm(x, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, gamma2=next_norm.weight,
-                                           beta2=next_norm.bias, eps=L.norm_final.eps)
-        return out, new, hn
-    _, out, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, eps=L.norm_final.eps)
-    hn = None
-    if next_norm is not None:
-        _, hn, _ = hip_ops.add_layernorm(out, None, 1.0, next_norm.weight, next_norm.bias, want_x=False, eps=next_norm.eps)
+        x = _ffn_residual(L.feed_forward, _ln(L.norm_ff, x, want_x=False)[1], x, L.ff_scale, plan.b2, inplace=True)
+    out, hn = _final_norms(L, x, next_norm)
     return out, new, hn
 
 
@@ -747,11 +731,8 @@ def lookahead_eligible(layer: nn.Module, x: torch.Tensor) -> bool:
     """The steady-state look-ahead chunk step (non-causal conv module, the shipped uni YAML) on the fused kernels: one bf16
     stream, uni-directional bf16 slot, pre-norm, layer_norm conv module with an odd kernel <= 31."""
     cm = layer.conv_module      # (a Mamba-2 slot takes the module path of forward_lookahead: stream_chunks_lookahead's eager loop)
-    return (cm is not None and type(layer.self_attn) is RWKV_TmixWrapper and layer.normalize_before
-            and layer.feed_forward_macaron is not None and cm.use_layer_norm and cm.lorder == 0 and cm.kernel_size % 2 == 1
-            and isinstance(cm.activation, nn.SiLU) and isinstance(layer.feed_forward.activation, nn.SiLU)
-            and isinstance(layer.feed_forward_macaron.activation, nn.SiLU) and cm.kernel_size <= 31
-            and layer.size % 64 == 0 and layer.size <= 1024 and x.is_cuda and x.dtype == torch.bfloat16 and x.size(0) == 1
+    return (_layer_shape_common(layer) and type(layer.self_attn) is RWKV_TmixWrapper and cm.lorder == 0
+            and cm.kernel_size % 2 == 1 and cm.kernel_size <= 31 and layer.size % 64 == 0 and layer.size <= 1024 and x.is_cuda and x.dtype == torch.bfloat16 and x.size(0) == 1
             and bool(layer.self_attn.do_bfloat16))
 
 
@@ -774,30 +755,16 @@ def layer_forward_lookahead(plan: LayerPlan, x: torch.Tensor, carry: dict, h0: O
     M = T
     x = x.contiguous()
     if h0 is None:
-        _, h0, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_ff_macaron.weight, L.norm_ff_macaron.bias, want_x=False, eps=L.norm_ff_macaron.eps)
+        h0 = _ln(L.norm_ff_macaron, x, want_x=False)[1]
     x = _ffn_residual(L.feed_forward_macaron, h0, x, L.ff_scale, plan.b2_macaron, inplace=False)
-    _, h, _ = hip_ops.add_layernorm(x, None, 1.0, L.norm_mha.weight, L.norm_mha.bias, want_x=False, eps=L.norm_mha.eps)
-    # slot: token shift + lerp as the down-projection's operand, LoRA-up + lerps, r / k / v, decay LoRA, scan from / into the state
-    t = hip_ops.gemm_skinny(h.view(M, C), plan.W1n[0], None, "tanh", mix_maa=plan.maa_x_n[0], mix_prev=shift, mix_T=T).view(1, M, -1)
-    z = hip_ops.tmix_lora_mix4(h, t, plan.W2t, plan.maa4, prev=shift)
-    rkv = hip_ops.gemm_skinny(z[:3].view(3, M, C), plan.Wrkv_n).view(3, B, T, C)
-    if plan.D1n.shape[1] == 64:
-        w = hip_ops.decay_lora_skinny(z[3].view(M, C), plan.D1n[0], plan.D2n[0], plan.time_decay.view(C)).view(B, T, C)
-    else:
-        td = hip_ops.gemm_skinny(z[3].view(M, C), plan.D1n[0], None, "tanh")
-        w = hip_ops.gemm_skinny(td, plan.D2n[0], plan.time_decay.view(C), round_first=True).view(B, T, C)
-    if hip_ops.wkv6_single_chunk(B, T, C, plan.u[0].shape[0]):
-        y, _ = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, s_out=s_in)
-    else:
-        y, s_out = wkv6_forward(rkv[0], rkv[1], rkv[2], w, plan.u[0], s_in=s_in, want_state=True)
+    h = _ln(L.norm_mha, x, want_x=False)[1]
+    # slot, from / into the state; the new rows of the residual stream go BEHIND the frames still waiting in X2
+    xnew, s_out, last = _chunk_slot_rwkv(plan, h, x, shift, s_in, sk=True, in_place=True, out=X2[0, half:])
+    if s_out is not None:
         s_in.copy_(s_out)
-    pending.append((shift, h[:, -1:]))
-    # ln_x folded into the output projection; the new rows of the residual stream go BEHIND the frames still waiting in X2
-    wo, bo, cso, epo = plan.carry_folds()["out"]
-    x2new = X2[0, half:]
-    hip_ops.gemm_skinny(y.view(M, C), wo, bo, residual=x.view(M, C), out=x2new, ln_self=True, ln_csum=cso, ln_eps=epo)
+    pending.append((shift, last))
     # conv branch, front half: norm_conv -> pointwise_conv1 + GLU, written behind the cached rows of U
-    _, hc, _ = hip_ops.add_layernorm(x2new.view(1, T, C), None, 1.0, L.norm_conv.weight, L.norm_conv.bias, want_x=False, eps=L.norm_conv.eps)
+    hc = _ln(L.norm_conv, xnew, want_x=False)[1]
     pw1 = cm.pointwise_conv1
     hip_ops.gemm_skinny(hc.view(M, C), pw1.weight.view(2 * C, C), pw1.bias, "glu", out=U[0, 2 * half:])
     # back half, on the T frames whose window is now complete (centres = rows [half, half + T) of U = rows [0, T) of X2)
@@ -807,18 +774,7 @@ def layer_forward_lookahead(plan: LayerPlan, x: torch.Tensor, carry: dict, h0: O
                              norm_silu=(cm.norm.weight, cm.norm.bias, cm.norm.eps))
     pending.append((U[:, :2 * half], U[:, T:T + 2 * half]))
     pending.append((X2[:, :half], X2[:, T:T + half]))
-    w1, b1, cs1, ep1 = plan.carry_folds()["ff"]
-    hid = hip_ops.gemm_skinny(x3, w1, b1, "silu", ln_self=True, ln_csum=cs1, ln_eps=ep1)
-    x4 = proj(hid, L.feed_forward.w_2.weight, plan.b2, "none", alpha=L.ff_scale, residual=x3, inplace=True).view(B, T, C)
-    if next_norm is not None and next_norm.eps == L.norm_final.eps:
-        _, out, hn = hip_ops.add_layernorm(x4, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, gamma2=next_norm.weight,
-                                           beta2=next_norm.bias, eps=L.norm_final.eps)
-        return out, hn
-    _, out, _ = hip_ops.add_layernorm(x4, None, 1.0, L.norm_final.weight, L.norm_final.bias, want_x=False, eps=L.norm_final.eps)
-    hn = None
-    if next_norm is not None:
-        _, hn, _ = hip_ops.add_layernorm(out, None, 1.0, next_norm.weight, next_norm.bias, want_x=False, eps=next_norm.eps)
-    return out, hn
+    return _final_norms(L, _ffn_chunk_lnfold(plan, x3).view(B, T, C), next_norm)
 
 
 class EncoderPlan:
@@ -870,7 +826,7 @@ def encoder_layers_forward(plan: EncoderPlan, xs: torch.Tensor, masks: torch.Ten
             xs = h
         return xs, outs
     split = [split_eligible(lp, xs) for lp in plan.layers] + [False]   # (after_norm's output goes to the caller: fp32)
-    _, h, _ = hip_ops.add_layernorm(xs, None, 1.0, first.weight, first.bias, eps=first.eps, split1=split[0])
+    h = _ln(first, xs, split1=split[0])[1]
     for i, lp in enumerate(plan.layers):
         nxt = plan.layers[i + 1].layer.norm_ff_macaron if i + 1 < n else after_norm
         if split[i]:
