@@ -120,6 +120,46 @@ int pafc_lsm_loss_rows(int dtype, long rows, int V, const void *logits, long ldl
 int pafc_lsm_loss_rows_bwd(int dtype, long rows, int V, const void *logits, long ldl, const int32_t *target, float smoothing,
                            const float *lse, const float *g, void *dlogits, long ldd, pafc_stream_t stream);
 
+/* ---- the training half of the Conformer baseline's slot: pafc_mha_band with statistics, and its backward ---- */
+
+/* pafc_mha_band that also writes lse[b*T + i, h] = m' + log(l'), the log of the softmax's denominator of query i and head h
+ * INCLUDING the padding keys' term n0_i e^0 (n0_i = max(0, min(t_pad - 1, i + w) - T + 1)), as float32 (B*T, H) with row pitch
+ * H: what the backward needs to form P again.  out holds the bits pafc_mha_band writes.  lse 4-byte aligned. */
+int pafc_mha_band_lse(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq, const void *k,
+                      const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u, const void *pos_bias_v,
+                      void *out, long ldo, float *lse, pafc_stream_t stream);
+
+/* Bytes of pafc_mha_band_bwd's workspace: the position-row gradient of every batch row (B, T, H*64) and the column sums of
+ * dqu | dqv of every query tile of 16 (B * ceil(T / 16), H, 128) in float32, and delta (B*T, H) in float64; 0 for bad
+ * arguments. */
+size_t pafc_mha_band_bwd_workspace_bytes(int B, int T, int H);
+
+/* The backward of pafc_mha_band: from its operands, the out and lse of pafc_mha_band_lse and the upstream gradient dout.  Per
+ * batch row and head, with qu_i = q_i + u, qv_i = q_i + v_bias, P_ij = exp(s_ij - lse_i) for the real keys of the band,
+ * delta_i = sum_d dout_id out_id and dS_ij = P_ij (dout_i . v_j - delta_i):
+ *   dqu_i = sum_j dS_ij k_j / sqrt(dk),  dqv_i = sum_j dS_ij p_j / sqrt(dk),  dq_i = dqu_i + dqv_i,
+ *   dk_j = sum_i dS_ij qu_i / sqrt(dk),  dv_j = sum_i P_ij dout_i,
+ *   dp_j = sum_b sum_i dS_ij qv_i / sqrt(dk)   (the position rows are shared by the batch),
+ *   du = sum_{b,i} dqu_i,  dvb = sum_{b,i} dqv_i.
+ * The padding keys have a constant score and a zero value: they enter through lse alone and receive no gradient.
+ * dtype as in the forward: PAFC_F32 takes every product exactly on the fp32 matrix cores; PAFC_BF16 runs on the bf16 matrix
+ *   cores with fp32 accumulation, P and dS rounded to bf16 for the products that consume them, and uses the forward's
+ *   rounded q + u and q + v (that rounding is treated as the identity).
+ * out / dout / dq: B*T rows of ldo / lddo / lddq elements; dk_out, dv_out: B*T rows of lddkv elements (pointers into one
+ *   stacked buffer, or separate ones); dp: T rows of lddp elements; all in `dtype`.  du, dvb: (H, dk) contiguous FLOAT32, the
+ *   sums over every row of the batch.  Every pitch >= H*dk and a multiple of 16 bytes; every operand, dq, dk_out, dv_out, dp
+ *   and the workspace 16-byte aligned; lse, du, dvb 4-byte aligned.  Nothing past row T - 1 of any operand is read.
+ * Every row of every output is written: the caller zeroes nothing.  No atomics: every sum has a fixed order, two runs on the
+ *   same input give the same bits, and dq / dk / dv of a batch row do not depend on the other rows.
+ * workspace: pafc_mha_band_bwd_workspace_bytes(B, T, H) bytes.  Limits on B, T, H, w, t_pad as in pafc_mha_band, and
+ *   T * H / 16 + 2 H < 2^31 (the blocks of the reduce launch): PAFC_ERR_BAD_DIMS otherwise.
+ * dk != 64: PAFC_ERR_UNSUPPORTED. */
+int pafc_mha_band_bwd(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq, const void *k,
+                      const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u, const void *pos_bias_v,
+                      const void *out, long ldo, const void *dout, long lddo, const float *lse, void *dq, long lddq,
+                      void *dk_out, void *dv_out, long lddkv, void *dp, long lddp, float *du, float *dvb, void *workspace,
+                      size_t workspace_bytes, pafc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

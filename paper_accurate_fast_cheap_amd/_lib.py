@@ -67,6 +67,10 @@ SIGNATURES = {
     "pafc_mha_rows_bwd": (I, [I, I, I, I, G, P, G, P, P, G, P, G, P, G, P, P, P, P, I, P, G, P, P, G, P, Z, P]),
     "pafc_lsm_loss_rows": (I, [I, G, I, P, G, P, F, P, P, P, P]),
     "pafc_lsm_loss_rows_bwd": (I, [I, G, I, P, G, P, F, P, P, P, G, P]),
+    "pafc_mha_band_lse": (I, [I, I, I, I, I, I, I, P, G, P, P, G, P, G, P, P, P, G, P, P]),
+    "pafc_mha_band_bwd_workspace_bytes": (Z, [I, I, I]),
+    "pafc_mha_band_bwd": (I, [I, I, I, I, I, I, I, P, G, P, P, G, P, G, P, P, P, G, P, G, P, P, G, P, P, G, P, G, P, P, P, Z,
+                              P]),
     # include/pafc_attn_search.h
     "pafc_mha_step": (I, [I, I, I, I, I, I, P, G, P, P, P, P, P, G, P]),
     "pafc_attn_beam_select_workspace_bytes": (Z, [I, I]),

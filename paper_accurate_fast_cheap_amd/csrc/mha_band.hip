@@ -23,6 +23,8 @@
 //     with its own L2, so the tile index is remapped to give every XCD one contiguous run of a head's tiles (a bijection for
 //     every grid width; placement changes speed only).
 // w >= t_pad makes the band cover everything: full attention with the positional term.
+// pafc_mha_band_lse is the same kernel instantiated with one more store per query and head, lse = m' + log(l') (the padding
+// keys' term included), for the backward (mha_band_bwd.hip); the arithmetic of `out` is untouched, so it carries the same bits.
 #include "pafc_attention.h"
 #include "mha_tile_body.h"
 
@@ -38,6 +40,7 @@ struct BandArgs {
     const void *p; long ldp;
     const void *u, *vb;
     void *out; long ldo;
+    float *lse;                // (B*T, H), written by the LSE instantiation only
 };
 
 // blockIdx.x -> query tile: the blocks x, x + 8, x + 16, ... (one XCD under round-robin placement) get consecutive tiles
@@ -45,8 +48,6 @@ __device__ __forceinline__ int band_tile_of_block(int bid, int n) {
     const int q = n >> 3, r = n & 7, x = bid & 7, idx = bid >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
 }
-
-__device__ __forceinline__ bool band_sees(int key, int i, int w, int T) { return key < T && key >= i - w && key <= i + w; }
 
 // the padding keys of query i (score 0, value 0), folded into the finished walk
 __device__ __forceinline__ void band_fold_padding(const BandArgs &A, int i, float &m, float &l, f32x4 *o) {
@@ -133,45 +134,11 @@ __device__ __forceinline__ void band_tile(const BandArgs &A, const BandFragBf16 
     pv_tile_bf16(s, vp, o);
 }
 
-// the biased query fragments [q + u | q + v] of the lane's query, in the layout the tile body multiplies
-__device__ __forceinline__ void band_query(const float *qp, const float *up, const float *vbp, float *qa, float *qb) {
-    float uu[16], vv[16];
-    load8<float>(qp, qa);
-    load8<float>(qp + 8, qa + 8);
-    load8<float>(up, uu);
-    load8<float>(up + 8, uu + 8);
-    load8<float>(vbp, vv);
-    load8<float>(vbp + 8, vv + 8);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        qb[e] = qa[e] + vv[e];
-        qa[e] = qa[e] + uu[e];
-    }
-}
-__device__ __forceinline__ void band_query(const bf16_t *qp, const bf16_t *up, const bf16_t *vbp, uint4 *qa, uint4 *qb) {
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {                 // dimensions 8 lq + [0, 8) and 32 + 8 lq + [0, 8)
-        float q[8], uu[8], vv[8], su[8], sv[8];
-        load8<bf16_t>(qp + 32 * part, q);
-        load8<bf16_t>(up + 32 * part, uu);
-        load8<bf16_t>(vbp + 32 * part, vv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            su[e] = q[e] + uu[e];
-            sv[e] = q[e] + vv[e];
-        }
-        qa[part] = make_uint4(pack_bf16_rne(su[0], su[1]), pack_bf16_rne(su[2], su[3]), pack_bf16_rne(su[4], su[5]),
-                              pack_bf16_rne(su[6], su[7]));
-        qb[part] = make_uint4(pack_bf16_rne(sv[0], sv[1]), pack_bf16_rne(sv[2], sv[3]), pack_bf16_rne(sv[4], sv[5]),
-                              pack_bf16_rne(sv[6], sv[7]));
-    }
-}
-
 template <typename ET> struct BandFrag;
 template <> struct BandFrag<float> { typedef float type; typedef BandFragF32 keys; static constexpr int kN = 16, kTile = 16, kLane = 16; };
 template <> struct BandFrag<bf16_t> { typedef uint4 type; typedef BandFragBf16 keys; static constexpr int kN = 2, kTile = 32, kLane = 8; };
 
-template <typename ET> __global__ __launch_bounds__(kBandWaves * kWave) void mha_band_kernel(BandArgs A) {
+template <typename ET, bool LSE> __global__ __launch_bounds__(kBandWaves * kWave) void mha_band_kernel(BandArgs A) {
     typedef BandFrag<ET> F;
     const int tile = band_tile_of_block(blockIdx.x, gridDim.x);
     const int h = blockIdx.y;
@@ -203,15 +170,16 @@ template <typename ET> __global__ __launch_bounds__(kBandWaves * kWave) void mha
         cur = nxt;
     }
     band_fold_padding(A, i, m, l, o);
+    if (LSE && lq == 0 && a + lr < T) A.lse[(row0 + a + lr) * A.H + h] = m + logf(l);
     store_tile<ET>(A.out, A.ldo, h, row0 + a + lr, a + lr < T, lq, o, 1.f / l);
 }
 
 }  // namespace pafc
 
-extern "C" int pafc_mha_band(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq, const void *k,
-                             const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u, const void *pos_bias_v,
-                             void *out, long ldo, pafc_stream_t stream) {
-    if (!q || !k || !v || !p || !pos_bias_u || !pos_bias_v || !out) return PAFC_ERR_NULL_POINTER;
+static int mha_band_launch(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq, const void *k,
+                           const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u, const void *pos_bias_v,
+                           void *out, long ldo, float *lse, bool want_lse, pafc_stream_t stream) {
+    if (!q || !k || !v || !p || !pos_bias_u || !pos_bias_v || !out || (want_lse && !lse)) return PAFC_ERR_NULL_POINTER;
     if (dtype != PAFC_F32 && dtype != PAFC_BF16) return PAFC_ERR_DTYPE;
     if (B <= 0 || T <= 0 || H <= 0 || dk <= 0 || w < 0 || t_pad < T || B > 65535 || H > 65535 || t_pad > (1 << 30))
         return PAFC_ERR_BAD_DIMS;
@@ -222,13 +190,35 @@ extern "C" int pafc_mha_band(int dtype, int B, int T, int H, int dk, int w, int 
     if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)p | (uintptr_t)pos_bias_u | (uintptr_t)pos_bias_v |
          (uintptr_t)out) & 15)
         return PAFC_ERR_ALIGNMENT;
+    if (want_lse && ((uintptr_t)lse & 3)) return PAFC_ERR_ALIGNMENT;
     // |j - i| < t_pad for every pair: a wider band is the same band, and i + w stays far from the int range
-    pafc::BandArgs a{T, H, w < t_pad ? w : t_pad, t_pad, q, ldq, k, v, ldkv, p, ldp, pos_bias_u, pos_bias_v, out, ldo};
+    pafc::BandArgs a{T, H, w < t_pad ? w : t_pad, t_pad, q, ldq, k, v, ldkv, p, ldp, pos_bias_u, pos_bias_v, out, ldo, lse};
     const dim3 grid((unsigned)((T + 63) / 64), (unsigned)H, (unsigned)B), block(pafc::kBandWaves * pafc::kWave);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == PAFC_F32)
-        hipLaunchKernelGGL((pafc::mha_band_kernel<float>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((pafc::mha_band_kernel<pafc::bf16_t>), grid, block, 0, s, a);
+    if (dtype == PAFC_F32) {
+        if (want_lse)
+            hipLaunchKernelGGL((pafc::mha_band_kernel<float, true>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((pafc::mha_band_kernel<float, false>), grid, block, 0, s, a);
+    } else {
+        if (want_lse)
+            hipLaunchKernelGGL((pafc::mha_band_kernel<pafc::bf16_t, true>), grid, block, 0, s, a);
+        else
+            hipLaunchKernelGGL((pafc::mha_band_kernel<pafc::bf16_t, false>), grid, block, 0, s, a);
+    }
     return hipGetLastError() == hipSuccess ? PAFC_OK : PAFC_ERR_LAUNCH;
+}
+
+extern "C" int pafc_mha_band(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq, const void *k,
+                             const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u, const void *pos_bias_v,
+                             void *out, long ldo, pafc_stream_t stream) {
+    return mha_band_launch(dtype, B, T, H, dk, w, t_pad, q, ldq, k, v, ldkv, p, ldp, pos_bias_u, pos_bias_v, out, ldo, nullptr,
+                           false, stream);
+}
+
+extern "C" int pafc_mha_band_lse(int dtype, int B, int T, int H, int dk, int w, int t_pad, const void *q, long ldq,
+                                 const void *k, const void *v, long ldkv, const void *p, long ldp, const void *pos_bias_u,
+                                 const void *pos_bias_v, void *out, long ldo, float *lse, pafc_stream_t stream) {
+    return mha_band_launch(dtype, B, T, H, dk, w, t_pad, q, ldq, k, v, ldkv, p, ldp, pos_bias_u, pos_bias_v, out, ldo, lse, true,
+                           stream);
 }

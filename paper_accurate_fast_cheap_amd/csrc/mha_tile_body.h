@@ -102,4 +102,42 @@ __device__ __forceinline__ void pv_tile_f32(const float *s, const float *const *
         for (int r = 0; r < 4; ++r) o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[r][16 * c], s[r], o[c], 0, 0, 0);
 }
 
+// ---- shared by the banded kernels (mha_band.hip, mha_band_bwd.hip) ----
+// does query i see key `key` (|key - i| <= w, a real key)?
+__device__ __forceinline__ bool band_sees(int key, int i, int w, int T) { return key < T && key >= i - w && key <= i + w; }
+
+// the biased query fragments [q + u | q + v] of the lane's query, in the layout the tile body multiplies
+__device__ __forceinline__ void band_query(const float *qp, const float *up, const float *vbp, float *qa, float *qb) {
+    float uu[16], vv[16];
+    load8<float>(qp, qa);
+    load8<float>(qp + 8, qa + 8);
+    load8<float>(up, uu);
+    load8<float>(up + 8, uu + 8);
+    load8<float>(vbp, vv);
+    load8<float>(vbp + 8, vv + 8);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        qb[e] = qa[e] + vv[e];
+        qa[e] = qa[e] + uu[e];
+    }
+}
+__device__ __forceinline__ void band_query(const bf16_t *qp, const bf16_t *up, const bf16_t *vbp, uint4 *qa, uint4 *qb) {
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {                 // dimensions 8 lq + [0, 8) and 32 + 8 lq + [0, 8)
+        float q[8], uu[8], vv[8], su[8], sv[8];
+        load8<bf16_t>(qp + 32 * part, q);
+        load8<bf16_t>(up + 32 * part, uu);
+        load8<bf16_t>(vbp + 32 * part, vv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            su[e] = q[e] + uu[e];
+            sv[e] = q[e] + vv[e];
+        }
+        qa[part] = make_uint4(pack_bf16_rne(su[0], su[1]), pack_bf16_rne(su[2], su[3]), pack_bf16_rne(su[4], su[5]),
+                              pack_bf16_rne(su[6], su[7]));
+        qb[part] = make_uint4(pack_bf16_rne(sv[0], sv[1]), pack_bf16_rne(sv[2], sv[3]), pack_bf16_rne(sv[4], sv[5]),
+                              pack_bf16_rne(sv[6], sv[7]));
+    }
+}
+
 }  // namespace pafc

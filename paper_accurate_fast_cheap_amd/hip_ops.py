@@ -824,6 +824,48 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) 
     return torch.nn.functional.linear(x, weight, bias)
 
 
+class _LinearOwnF32(torch.autograd.Function):
+    """x @ W^T + b of an fp32 model on the hand-written fp32 GEMM, forward and backward: the forward is linear_fused's exact
+    product (the bits of the inference path), dX = dY W and dW = dY^T X go through the same kernel on transposed copies (the
+    reduction over the rows zero-padded to a multiple of 4, which the kernel's K needs), db is a column sum."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return linear_fused(x, weight.detach(), None if bias is None else bias.detach(), "none", split_ok=False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        N, K = weight.shape
+        dy2 = dy.reshape(-1, N).contiguous()
+        x2 = x.reshape(-1, K)
+        R = dy2.shape[0]
+
+        def rows_last(t):                                  # (R, C) -> (C, R rounded up to 4), zeros in the padding
+            o = t.new_zeros(t.shape[1], -(-R // 4) * 4)
+            o[:, :R] = t.t()
+            return o
+        dx = gemm_f32(dy2, weight.detach().t().contiguous()).view(x.shape) if ctx.needs_input_grad[0] else None
+        dw = gemm_f32(rows_last(dy2), rows_last(x2)) if ctx.needs_input_grad[1] else None
+        db = dy2.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dw, db
+
+
+def linear_own(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """The projections of a module whose inference path runs on this package's GEMMs, under autograd: an fp32 model outside
+    autocast keeps those GEMMs in both directions (_LinearOwnF32: the forward carries the inference path's bits); everything
+    else is `linear` (the bf16 training GEMMs under bf16 autocast).  The conditions cover the backward's operands too: its
+    three products run on fresh contiguous copies (16-byte aligned, rows padded to a multiple of 4), so beyond the forward's
+    form they need only N % 4 == 0, the K of dX = dY W (tests/test_lca_train_gpu.py holds y, dX, dW and db to float64)."""
+    if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and not torch.is_autocast_enabled()
+            and (bias is None or bias.dtype == torch.float32) and weight.shape[0] % 4 == 0
+            and gemm_f32_ok(x.reshape(-1, weight.shape[1]), weight)):
+        return _LinearOwnF32.apply(x, weight, bias)
+    return linear(x, weight, bias)
+
+
 def _weight_group(ws) -> Optional[torch.Tensor]:
     """Z equally shaped weights as ONE (Z, N, K) bf16 operand, inside train_shadows() only (None elsewhere).
     bf16 parameters (the time-mix slot): the parameters THEMSELVES are moved into one buffer the first time they are asked for
@@ -3495,34 +3537,8 @@ def mha_band(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor,
     sees the keys j with |j - i| <= w, 0 <= j < t_pad; the keys of [T, t_pad) are the reference's unmasked zero padding (score
     0, value 0) and are never read.  t_pad None: T rounded up to a multiple of 2 w, the reference's value.  Returns out
     (batch * T, H * 64)."""
-    d = heads * 64
-    for name, t in (("q", q), ("k", k), ("v", v), ("p", p)):
-        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype or t.shape[1] < d:
-            raise _lib.PafcError(f"mha_band: {name} is a 2-D GPU tensor of q's dtype with at least H * 64 columns and unit stride "
-                                 f"along them")
-    if q.dtype not in (torch.float32, torch.bfloat16):
-        raise _lib.PafcError(f"mha_band: fp32 or bf16 operands, got {q.dtype}")
-    if batch < 1 or heads < 1 or q.shape[0] % batch:
-        raise _lib.PafcError(f"mha_band: q has {q.shape[0]} rows, not a multiple of batch = {batch}")
-    T = q.shape[0] // batch
-    if T < 1 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0] or p.shape[0] != T:
-        raise _lib.PafcError(f"mha_band: q, k, v hold batch * T rows and p holds T = {T} rows "
-                             f"(k {k.shape[0]}, v {v.shape[0]}, p {p.shape[0]})")
-    if k.stride(0) != v.stride(0):
-        raise _lib.PafcError("mha_band: k and v must share their row pitch")
-    if w < 0:
-        raise _lib.PafcError(f"mha_band: w = {w} is negative")
-    if t_pad is None:
-        t_pad = -(-T // (2 * w)) * 2 * w if w > 0 else T
-    if t_pad < T:
-        raise _lib.PafcError(f"mha_band: t_pad = {t_pad} is below T = {T}")
-    per16 = 16 // q.element_size()
-    for name, t in (("q", q), ("k", k), ("v", v), ("p", p)):
-        if t.stride(0) % per16 or t.data_ptr() % 16:
-            raise _lib.PafcError(f"mha_band: {name} needs a 16-byte aligned base and a row pitch that is a multiple of 16 bytes")
-    for name, t in (("pos_bias_u", pos_bias_u), ("pos_bias_v", pos_bias_v)):
-        if not t.is_cuda or t.dtype != q.dtype or tuple(t.shape) != (heads, 64) or not t.is_contiguous() or t.data_ptr() % 16:
-            raise _lib.PafcError(f"mha_band: {name} is a contiguous, 16-byte aligned (H, 64) GPU tensor of q's dtype")
+    d, per16 = heads * 64, 16 // q.element_size()
+    T, t_pad = _mha_band_operands("mha_band", q, k, v, p, pos_bias_u, pos_bias_v, batch, heads, w, t_pad)
     if out is None:
         out = torch.empty(q.shape[0], d, dtype=q.dtype, device=q.device)
     elif (not out.is_cuda or out.dtype != q.dtype or out.dim() != 2 or out.stride(1) != 1 or tuple(out.shape) != (q.shape[0], d)
@@ -3671,6 +3687,168 @@ def mha_rows_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_off: tor
     """mha_rows with gradients for q, k and v (which may be slices of one stacked projection).  The key ranges of two groups
     with query rows must not overlap (mha_rows_bwd)."""
     return _MhaRowsTrain.apply(q, k, v, q_off, kv_off, kv_len, heads, causal)
+
+
+# ---- training the Conformer baseline's slot (include/pafc_attention.h, csrc/mha_band_bwd.hip) --------------------------------
+def _mha_band_operands(who: str, q, k, v, p, pos_bias_u, pos_bias_v, batch: int, heads: int, w: int, t_pad):
+    """The argument checks of mha_band for the training pair; -> (T, t_pad)."""
+    d = heads * 64
+    for name, t in (("q", q), ("k", k), ("v", v), ("p", p)):
+        if not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype or t.shape[1] < d:
+            raise _lib.PafcError(f"{who}: {name} is a 2-D GPU tensor of q's dtype with at least H * 64 columns and unit stride "
+                                 f"along them")
+    if q.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.PafcError(f"{who}: fp32 or bf16 operands, got {q.dtype}")
+    if batch < 1 or heads < 1 or q.shape[0] % batch:
+        raise _lib.PafcError(f"{who}: q has {q.shape[0]} rows, not a multiple of batch = {batch}")
+    T = q.shape[0] // batch
+    if T < 1 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0] or p.shape[0] != T:
+        raise _lib.PafcError(f"{who}: q, k, v hold batch * T rows and p holds T = {T} rows "
+                             f"(k {k.shape[0]}, v {v.shape[0]}, p {p.shape[0]})")
+    if k.stride(0) != v.stride(0):
+        raise _lib.PafcError(f"{who}: k and v must share their row pitch")
+    if w < 0:
+        raise _lib.PafcError(f"{who}: w = {w} is negative")
+    if t_pad is None:
+        t_pad = -(-T // (2 * w)) * 2 * w if w > 0 else T
+    if t_pad < T:
+        raise _lib.PafcError(f"{who}: t_pad = {t_pad} is below T = {T}")
+    per16 = 16 // q.element_size()
+    for name, t in (("q", q), ("k", k), ("v", v), ("p", p)):
+        if t.stride(0) % per16 or t.data_ptr() % 16:
+            raise _lib.PafcError(f"{who}: {name} needs a 16-byte aligned base and a row pitch that is a multiple of 16 bytes")
+    for name, t in (("pos_bias_u", pos_bias_u), ("pos_bias_v", pos_bias_v)):
+        if not t.is_cuda or t.dtype != q.dtype or tuple(t.shape) != (heads, 64) or not t.is_contiguous() or t.data_ptr() % 16:
+            raise _lib.PafcError(f"{who}: {name} is a contiguous, 16-byte aligned (H, 64) GPU tensor of q's dtype")
+    return T, int(t_pad)
+
+
+def _mha_band_rows(who: str, name: str, t, like, rows: int, d: int):
+    per16 = 16 // like.element_size()
+    if (not t.is_cuda or t.dtype != like.dtype or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != rows or t.shape[1] < d
+            or t.stride(0) % per16 or t.data_ptr() % 16):
+        raise _lib.PafcError(f"{who}: {name} is ({rows}, >= H * 64) in the operands' dtype, unit stride along the heads, 16-byte "
+                             f"aligned rows")
+
+
+def mha_band_lse(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, pos_bias_u: torch.Tensor,
+                 pos_bias_v: torch.Tensor, batch: int, heads: int, w: int, t_pad: Optional[int] = None):
+    """mha_band that also returns lse (batch * T, H) float32, the log of every query's softmax denominator per head with the
+    padding keys' term in it (pafc_mha_band_lse): -> (out with the bits of mha_band, lse)."""
+    T, t_pad = _mha_band_operands("mha_band_lse", q, k, v, p, pos_bias_u, pos_bias_v, batch, heads, w, t_pad)
+    out = torch.empty(q.shape[0], heads * 64, dtype=q.dtype, device=q.device)
+    lse = torch.empty(q.shape[0], heads, dtype=torch.float32, device=q.device)
+    rc = _lib.lib().pafc_mha_band_lse(_lib.dtype_code(q.dtype), batch, T, heads, 64, int(w), t_pad, _lib.ptr(q), q.stride(0),
+                                      _lib.ptr(k), _lib.ptr(v), k.stride(0), _lib.ptr(p), p.stride(0), _lib.ptr(pos_bias_u),
+                                      _lib.ptr(pos_bias_v), _lib.ptr(out), out.stride(0), _lib.ptr(lse), _lib.stream_of(q))
+    _lib.check(rc, "pafc_mha_band_lse")
+    return out, lse
+
+
+def mha_band_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, pos_bias_u: torch.Tensor,
+                 pos_bias_v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, batch: int, heads: int,
+                 w: int, t_pad: Optional[int] = None, dq: Optional[torch.Tensor] = None, dk: Optional[torch.Tensor] = None,
+                 dv: Optional[torch.Tensor] = None, dp: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None):
+    """(dq, dk, dv, dp, du, dvb) of mha_band from its operands, the out / lse of mha_band_lse and the upstream gradient dout
+    (pafc_mha_band_bwd: three launches, no atomics, two runs give the same bits).  dq, dk, dv (batch * T, >= H * 64; dk and dv
+    with one row pitch) and dp (T, >= H * 64) may be handed in, column slices of stacked buffers included; every row of them is
+    written.  du, dvb: (H, 64) float32, the sums over every row of the batch.  workspace: a uint8 GPU tensor of at least
+    pafc_mha_band_bwd_workspace_bytes bytes, allocated here when None."""
+    T, t_pad = _mha_band_operands("mha_band_bwd", q, k, v, p, pos_bias_u, pos_bias_v, batch, heads, w, t_pad)
+    d, rows = heads * 64, q.shape[0]
+    _mha_band_rows("mha_band_bwd", "out", out, q, rows, d)
+    _mha_band_rows("mha_band_bwd", "dout", dout, q, rows, d)
+    if not lse.is_cuda or lse.dtype != torch.float32 or tuple(lse.shape) != (rows, heads) or not lse.is_contiguous():
+        raise _lib.PafcError("mha_band_bwd: lse is (batch * T, H) float32, contiguous")
+    if dq is None:
+        dq = torch.empty(rows, d, dtype=q.dtype, device=q.device)
+    if dk is None or dv is None:
+        dkv = torch.empty(rows, 2 * d, dtype=q.dtype, device=q.device)
+        dk, dv = dkv[:, :d], dkv[:, d:]
+    if dp is None:
+        dp = torch.empty(T, d, dtype=q.dtype, device=q.device)
+    for name, t, n in (("dq", dq, rows), ("dk", dk, rows), ("dv", dv, rows), ("dp", dp, T)):
+        _mha_band_rows("mha_band_bwd", name, t, q, n, d)
+    if dk.stride(0) != dv.stride(0):
+        raise _lib.PafcError("mha_band_bwd: dk and dv must share their row pitch")
+    du = torch.empty(heads, 64, dtype=torch.float32, device=q.device)
+    dvb = torch.empty(heads, 64, dtype=torch.float32, device=q.device)
+    L = _lib.lib()
+    nbytes = L.pafc_mha_band_bwd_workspace_bytes(batch, T, heads)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise _lib.PafcError("mha_band_bwd: workspace is a contiguous uint8 GPU tensor")
+    from .profiling import op_timer
+    # 896 flop per (query, key) pair and pass: a 128-deep score, a 64-deep dP and two or three 64-wide products
+    with op_timer("mha_band_bwd_w%d" % w, sample=12, flops=1792.0 * batch * heads * T * min(T, 2 * w + 1)):
+        rc = L.pafc_mha_band_bwd(_lib.dtype_code(q.dtype), batch, T, heads, 64, int(w), t_pad, _lib.ptr(q), q.stride(0),
+                                 _lib.ptr(k), _lib.ptr(v), k.stride(0), _lib.ptr(p), p.stride(0), _lib.ptr(pos_bias_u),
+                                 _lib.ptr(pos_bias_v), _lib.ptr(out), out.stride(0), _lib.ptr(dout), dout.stride(0),
+                                 _lib.ptr(lse), _lib.ptr(dq), dq.stride(0), _lib.ptr(dk), _lib.ptr(dv), dk.stride(0),
+                                 _lib.ptr(dp), dp.stride(0), _lib.ptr(du), _lib.ptr(dvb), _lib.ptr(workspace),
+                                 workspace.numel(), _lib.stream_of(q))
+    _lib.check(rc, "pafc_mha_band_bwd")
+    return dq, dk, dv, dp, du, dvb
+
+
+def _thirds_of_one_buffer(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d: int) -> bool:
+    """Are q, k, v the column thirds [Q | K | V] of one (rows, 3 d) buffer?"""
+    es = q.element_size()
+    return (q.shape[1] == d and k.shape[1] == d and v.shape[1] == d and q.stride(0) == 3 * d and k.stride(0) == 3 * d
+            and v.stride(0) == 3 * d and k.data_ptr() == q.data_ptr() + d * es and v.data_ptr() == q.data_ptr() + 2 * d * es)
+
+
+class _MhaBandTrain(torch.autograd.Function):
+    """mha_band under autograd: pafc_mha_band_lse forward, pafc_mha_band_bwd backward.  When q, k and v are the column thirds of
+    one stacked projection the three gradients are the thirds of one (rows, 3 D) buffer, as _MhaRowsTrain's are (q, k, v arrive
+    as three slice views, so autograd still adds three zero-padded thirds before the QKV GEMM's backward).  The biases may be fp32 parameters under a bf16 kernel (autocast): they are cast as _param_as does
+    and their gradients come back in their own dtype."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, p, pos_bias_u, pos_bias_v, batch, heads, w, t_pad):
+        u, vb = _param_as(pos_bias_u, q.dtype).contiguous(), _param_as(pos_bias_v, q.dtype).contiguous()
+        out, lse = mha_band_lse(q, k, v, p, u, vb, batch, heads, w, t_pad)
+        ctx.save_for_backward(q, k, v, p, u, vb, out, lse)
+        ctx.cfg = (batch, heads, w, t_pad, pos_bias_u.dtype, pos_bias_v.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, p, u, vb, out, lse = ctx.saved_tensors
+        batch, heads, w, t_pad, u_dtype, vb_dtype = ctx.cfg
+        d = heads * 64
+        if dout.dtype != q.dtype:
+            dout = dout.to(q.dtype)
+        if dout.stride(1) != 1 or (dout.stride(0) * dout.element_size()) % 16 or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        dq = dk = dv = None
+        stacked = _thirds_of_one_buffer(q, k, v, d)
+        if stacked:                                        # one buffer for the three: the stacked projection's gradient
+            buf = torch.empty(q.shape[0], 3 * d, dtype=q.dtype, device=q.device)
+            dq, dk, dv = buf[:, :d], buf[:, d:2 * d], buf[:, 2 * d:]
+        dq, dk, dv, dp, du, dvb = mha_band_bwd(q, k, v, p, u, vb, out, dout, lse, batch, heads, w, t_pad, dq, dk, dv)
+        if not stacked:                                    # gradients of the inputs' shapes (wider inputs: zero beyond H * 64)
+            dq, dk, dv, dp = (_grad_like(g, t, d) for g, t in ((dq, q), (dk, k), (dv, v), (dp, p)))
+        else:
+            dp = _grad_like(dp, p, d)
+        return dq, dk, dv, dp, du.to(u_dtype), dvb.to(vb_dtype), None, None, None, None
+
+
+def _grad_like(g: torch.Tensor, t: torch.Tensor, d: int) -> torch.Tensor:
+    if t.shape[1] == d:
+        return g
+    full = torch.zeros(t.shape, dtype=g.dtype, device=g.device)
+    full[:, :d] = g
+    return full
+
+
+def mha_band_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, pos_bias_u: torch.Tensor,
+                   pos_bias_v: torch.Tensor, batch: int, heads: int, w: int, t_pad: Optional[int] = None) -> torch.Tensor:
+    """mha_band with gradients for q, k, v, p and the two biases (q, k, v may be slices of one stacked projection; the biases
+    may be fp32 parameters of a bf16 call)."""
+    return _MhaBandTrain.apply(q, k, v, p, pos_bias_u, pos_bias_v, batch, heads, w, t_pad)
 
 
 def _lsm_operands(who: str, logits: torch.Tensor, target: torch.Tensor):

@@ -5,7 +5,8 @@ second pass on the GPU packs the rows and runs hip_ops.mha_rows instead (transfo
 
 LimitedRelPositionMultiHeadedAttention is the encoder slot of the Conformer baseline (reference: attention.py:406-645,
 `selfattention_layer_type: limited_rel_selfattn`): self-attention over a band of +-w frames with the key's position row as a
-second score term, on hip_ops.mha_band and this package's GEMMs.  Inference on the GPU only."""
+second score term, on hip_ops.mha_band and this package's GEMMs.  Inference on the GPU; with `trainable` set (ConformerEncoder
+sets it on the slots it builds) also training, through hip_ops.mha_band_train."""
 import math
 from typing import Optional, Tuple
 
@@ -50,6 +51,10 @@ class LimitedRelPositionMultiHeadedAttention(torch.nn.Module):
     blocked layout and are not masked (score 0, value 0), and `mask` does not reach the output (attention.py:552 is commented
     out): padded frames of a batch row are keys like any other.  Trained checkpoints have seen both, so both are kept.
     Parameter names are the reference's: a checkpoint loads with strict=True."""
+
+    # with gradients enabled: run the training path (hip_ops.mha_band_train, differentiable projections) instead of refusing.
+    # Set by an encoder that builds the slot (ConformerEncoder, next to own_gemm); a bare module keeps the inference-only error.
+    trainable: bool = False
 
     def __init__(self, n_head: int, n_feat: int, dropout_rate: float, key_bias: bool = True, att_context_size=(500, 500),
                  global_tokens: int = 0, global_tokens_spacing: int = 1, global_attn_separate: bool = False, layer_id: int = 0):
@@ -114,9 +119,11 @@ class LimitedRelPositionMultiHeadedAttention(torch.nn.Module):
         if cache.numel() > 0:
             raise ValueError("cache: limited-context attention takes no key/value cache (the reference asserts q.size() == "
                              "k.size(), so it fails for a non-empty one too); pass the empty cache")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("limited_rel_selfattn is inference only: call it under torch.no_grad() (training the "
-                                      "Conformer baseline is not implemented)")
+        train = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or (
+            self.trainable and (query.requires_grad or key.requires_grad or value.requires_grad)))   # (frozen slot, live input)
+        if train and not self.trainable:
+            raise NotImplementedError("limited_rel_selfattn is inference only: call it under torch.no_grad() (a module built "
+                                      "outside ConformerEncoder trains only with its `trainable` attribute set)")
         if self.training and self.dropout.p > 0:
             raise NotImplementedError("limited_rel_selfattn: attention dropout is a training feature; call .eval() first")
         if self.d_k != 64:
@@ -127,6 +134,8 @@ class LimitedRelPositionMultiHeadedAttention(torch.nn.Module):
             raise ValueError("key / value: self-attention takes key and value of the query's shape")
         if pos_emb.dim() != 3 or pos_emb.size(0) != 1 or pos_emb.size(1) != T or pos_emb.size(2) != D:
             raise ValueError(f"pos_emb: expected the (1, {T}, {D}) position rows of the input's frames, got {tuple(pos_emb.shape)}")
+        if train:
+            return self._forward_train(query, key, value, pos_emb)
         lin = lambda x, w, b: hip_ops.linear_fused(x, w, b, "none", split_ok=False)       # exact fp32 products in an fp32 model
         if key is query and value is query:
             w_qkv, b_qkv = self._stacked_qkv()
@@ -140,6 +149,36 @@ class LimitedRelPositionMultiHeadedAttention(torch.nn.Module):
             k, v = kv[:, :D], kv[:, D:]
         p = lin(pos_emb.reshape(T, D).to(q.dtype), self.linear_pos.weight, None)
         att = hip_ops.mha_band(q, k, v, p, self.pos_bias_u, self.pos_bias_v, B, self.h, self.att_context_size[0])
+        new_cache = torch.cat((k.view(B, T, self.h, self.d_k).transpose(1, 2), v.view(B, T, self.h, self.d_k).transpose(1, 2)),
+                              dim=-1)
+        out = lin(att, self.linear_out.weight, self.linear_out.bias)
+        return out.view(B, T, D), new_cache
+
+    def _forward_train(self, query, key, value, pos_emb):
+        """The same computation under autograd: the projections through hip_ops.linear_own (this package's GEMMs forward and
+        backward; under bf16 autocast hip_ops.linear's bf16 training GEMMs), the attention through hip_ops.mha_band_train.
+        The stacked [Wq; Wk; Wv] of the inference path is a detached copy, so the self-attention case stacks the three
+        weights with a differentiable cat instead: still one product.  (mha_band_train writes dq | dk | dv into one (B T, 3 D)
+        buffer; q, k, v reach it as three slice views, so autograd still adds three zero-padded thirds in front of the GEMM's
+        backward, as it does for mha_rows_train.)"""
+        from .. import hip_ops
+        B, T, D = query.shape
+        lin = hip_ops.linear_own
+        if key is query and value is query:
+            w_qkv = torch.cat((self.linear_q.weight, self.linear_k.weight, self.linear_v.weight))
+            kb = self.linear_k.bias if self.linear_k.bias is not None else torch.zeros_like(self.linear_q.bias)
+            b_qkv = torch.cat((self.linear_q.bias, kb, self.linear_v.bias))
+            qkv = lin(query.reshape(B * T, D), w_qkv, b_qkv)
+            q, k, v = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
+        else:
+            q = lin(query.reshape(B * T, D), self.linear_q.weight, self.linear_q.bias)
+            kv = torch.cat((lin(key.reshape(B * T, D), self.linear_k.weight, self.linear_k.bias),
+                            lin(value.reshape(B * T, D), self.linear_v.weight, self.linear_v.bias)), dim=1)
+            k, v = kv[:, :D], kv[:, D:]                                                   # k and v share a row pitch
+        p = lin(pos_emb.reshape(T, D).to(query.dtype), self.linear_pos.weight, None)
+        if p.dtype != q.dtype:                                                           # (a short T under autocast: F.linear's dtype)
+            p = p.to(q.dtype)
+        att = hip_ops.mha_band_train(q, k, v, p, self.pos_bias_u, self.pos_bias_v, B, self.h, self.att_context_size[0])
         new_cache = torch.cat((k.view(B, T, self.h, self.d_k).transpose(1, 2), v.view(B, T, self.h, self.d_k).transpose(1, 2)),
                               dim=-1)
         out = lin(att, self.linear_out.weight, self.linear_out.bias)

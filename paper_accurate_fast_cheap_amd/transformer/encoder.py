@@ -4,7 +4,7 @@ Reference: wenet/transformer/encoder.py:38-402 (BaseEncoder: forward, forward_ch
 and :453-602 (ConformerEncoder: slot constructor arguments :545-569, layer list :589-602).  Same constructor
 keys as conf/rwkv/*.yaml `encoder_conf`, same sub-module names (embed, encoders.N, after_norm, global_cmvn),
 same return shapes.  Scope: num_langs == 0, the recurrent slot keys and the Conformer baseline's limited-context attention
-(`limited_rel_selfattn`, inference, on the module path); full-context MHA, the LSL variant and the plain TransformerEncoder
+(`limited_rel_selfattn`, inference and training, on the module path); full-context MHA, the LSL variant and the plain TransformerEncoder
 are not part of the accelerated path.
 """
 import os
@@ -649,3 +649,4 @@ class ConformerEncoder(BaseEncoder):
                 for m in (layer.feed_forward, layer.feed_forward_macaron, layer.conv_module):
                     if m is not None:
                         m.own_gemm = True
+                layer.self_attn.trainable = True        # with gradients enabled the slot trains (hip_ops.mha_band_train)
