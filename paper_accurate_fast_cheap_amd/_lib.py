@@ -167,6 +167,11 @@ SIGNATURES = {
     "pafc_fbank_stream_plan": (I, [I, G, P, P]),
     "pafc_fbank_stream": (I, [P, I, P, G, G, I, P, P, P, P, P, I, F, F, P, I, G, G, P]),
     "pafc_fbank_stream_rows": (I, [P, I, P, P, I, P, G, G, P, P, P, P, P, I, F, F, P, I, I, P]),
+    # include/pafc_resample.h
+    "pafc_resample_num_out": (G, [G, I, I]),
+    "pafc_resample_stream_plan": (I, [I, I, I, I, G, P, P]),
+    "pafc_resample_batch": (I, [P, G, P, I, G, I, I, I, P, P, I, P, G, P, P]),
+    "pafc_resample_rows": (I, [P, G, I, P, P, I, P, G, G, I, I, I, P, P, I, P, G, P]),
     # include/pafc_search.h
     "pafc_ctc_greedy": (I, [I, I, I, I, P, P, I, P, P, P, P, P]),
     "pafc_log_softmax_rows": (I, [I, G, I, P, P, P]),

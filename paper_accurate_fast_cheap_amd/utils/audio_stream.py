@@ -65,12 +65,16 @@ class AudioStreamer:
     latest partial result -- CTC: the partial DecodeResults of CtcStreamer.feed, as on_partial sees them; RNN-T: the new tokens
     per row of the windows this feed ran -- or None if no window ran.  finish() runs the last window and returns the final
     List[DecodeResult]: exactly what the model's stream_* function returns for fbank_batch of the whole audio.  `.committed`:
-    per row the tokens that can no longer change (it only grows).  reset() starts new streams."""
+    per row the tokens that can no longer change (it only grows).  reset() starts new streams.
+
+    sample_rate: the rate of the samples feed() takes.  At another rate than 16 000 Hz a dataset.resample.ResampleStreamer turns
+    every packet into 16 kHz samples on the device first and finish() flushes it into the fbank before the last window: the
+    results are exactly those of an AudioStreamer fed resample_batch of the whole audio.  At 16 000 none is constructed."""
 
     def __init__(self, model: torch.nn.Module, batch_size: int, decoding_chunk_size: int, mode: str = "ctc_prefix_beam_search",
                  beam_size: int = 10, context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0,
                  on_partial: Optional[Callable] = None, max_total_frames: int = 4096, n_steps: int = 64,
-                 on_tokens: Optional[Callable] = None, num_mel_bins: int = 80):
+                 on_tokens: Optional[Callable] = None, num_mel_bins: int = 80, sample_rate: int = 16000):
         from ..dataset.fbank import FbankStreamer
         if mode not in MODES:
             raise ValueError(f"AudioStreamer: mode must be one of {MODES}, got {mode!r}")
@@ -83,6 +87,11 @@ class AudioStreamer:
         self._lookahead = any(l.conv_module is not None and l.conv_module.lorder == 0 for l in enc.encoders)
         self.plan = WindowRelease(enc.embed, decoding_chunk_size)
         self.fbank = FbankStreamer(batch_size, num_mel_bins, p.dtype, p.device)
+        self.sample_rate = sample_rate
+        self.resampler = None
+        if sample_rate != 16000:
+            from ..dataset import resample as _resample
+            self.resampler = _resample.ResampleStreamer(batch_size, sample_rate, 16000, p.device)
         self._buf = torch.empty(batch_size, 2 * (self.plan.window + self.plan.stride), num_mel_bins, dtype=p.dtype, device=p.device)
         self._base = 0                  # absolute frame of _buf[:, 0]
         self._held = 0                  # frames in _buf
@@ -107,6 +116,8 @@ class AudioStreamer:
 
     def reset(self):
         self.fbank.reset()
+        if self.resampler is not None:
+            self.resampler.reset()
         self.plan.reset()
         self.decoder.reset()
         self._base = self._held = self._windows = 0
@@ -152,9 +163,14 @@ class AudioStreamer:
 
     @torch.no_grad()
     def feed(self, samples: torch.Tensor):
-        from ..dataset.fbank import stream_plan
         if self.plan.finished:
             raise ValueError("AudioStreamer.feed: the streams were finished; reset() starts new ones")
+        if self.resampler is not None:
+            samples = self.resampler.feed(samples)
+        return self._feed_16k(samples)
+
+    def _feed_16k(self, samples: torch.Tensor):
+        from ..dataset.fbank import stream_plan
         frames, _ = stream_plan(self.fbank.carry_len, samples.size(1) if samples.dim() == 2 else 0)
         need = self._held + frames
         if need > self._buf.size(1):                            # one packet may bring any number of frames
@@ -169,6 +185,8 @@ class AudioStreamer:
 
     @torch.no_grad()
     def finish(self):
+        if self.resampler is not None and not self.plan.finished:
+            self._feed_16k(self.resampler.flush())          # the outputs that were waiting for samples behind the last one
         self._run(self.plan.finish())
         self._drop_consumed()
         return self.decoder.results()

@@ -215,6 +215,12 @@ class StreamPool:
     batch size eager.  A stream that passes max_total_frames raises PafcError naming its sid after the feed has served the
     others; it takes no more frames, close() returns what it had taken and lists its sid in `truncated`.
 
+    sample_rate: the rate of the samples feed() takes.  At another rate than 16 000 Hz a dataset.resample.ResampleSlotStreamer
+    turns the rows of a feed into 16 kHz samples on the device first (one more launch pair; the counts are host arithmetic), the
+    resampled rows are cut against the ring as a 16 kHz packet is, and close() flushes the stream's resampler into the fbank
+    before its last window: the results are exactly those of a pool fed resample_batch of every stream's whole audio.  At
+    16 000 none is constructed.
+
     Not offered, with a ValueError: rnnt_beam_search (its streaming bench ended in a device exception whose cause is open),
     encoders that cannot stream, and the look-ahead model (non-causal conv module): its layers emit a number of frames that
     depends on the age of the stream, so streams of different ages cannot share a dense batch."""
@@ -222,7 +228,8 @@ class StreamPool:
     def __init__(self, model: torch.nn.Module, slots: int, decoding_chunk_size: int, mode: str = "ctc_prefix_beam_search",
                  beam_size: int = 10, context_graph=None, blank_id: int = 0, blank_penalty: float = 0.0,
                  max_total_frames: int = 4096, n_steps: int = 64, max_step_rows: Optional[int] = None, use_graph: bool = True,
-                 on_encoder_out: Optional[Callable] = None, num_mel_bins: int = 80, ring_frames: Optional[int] = None):
+                 on_encoder_out: Optional[Callable] = None, num_mel_bins: int = 80, ring_frames: Optional[int] = None,
+                 sample_rate: int = 16000):
         if mode == "rnnt_beam_search":
             raise ValueError("StreamPool: rnnt_beam_search is not offered in the pool: its streaming bench ended in a device "
                              "exception whose cause is still open, and the pool adds no new way to reach it")
@@ -249,6 +256,11 @@ class StreamPool:
         from ..dataset.fbank import FbankSlotStreamer
         self.fbank = FbankSlotStreamer(slots, self.sched.ring_frames, num_mel_bins, p.dtype, p.device)
         self._frame_bytes = num_mel_bins * self.fbank.ring.element_size()
+        self.sample_rate = sample_rate
+        self.resampler = None
+        if sample_rate != 16000:
+            from ..dataset import resample as _resample
+            self.resampler = _resample.ResampleSlotStreamer(slots, sample_rate, 16000, p.device)
         if mode == "rnnt_greedy_search":
             from ..transducer.search.greedy_search import GreedyStreamer
             self.decoder = GreedyStreamer(model, slots, decoding_chunk_size, n_steps)
@@ -268,6 +280,8 @@ class StreamPool:
         sid = self.sched.open()
         slot = self.sched.slot_of(sid)
         self.fbank.reset(slot)
+        if self.resampler is not None:
+            self.resampler.reset(slot)
         self.decoder.reset([slot])       # (a slot is reset when it is freed as well: nothing of an earlier stream is left)
         self._partial[slot] = None
         return sid
@@ -297,11 +311,24 @@ class StreamPool:
         lengths = [n_max] * len(sids) if lengths is None else [int(v) for v in lengths]
         if len(lengths) != len(sids) or any(not 0 <= n <= n_max for n in lengths):
             raise ValueError(f"StreamPool.feed: lengths must be {len(sids)} values in [0, {n_max}]")
-        row_of = {sid: i for i, sid in enumerate(sids)}
-        left = {sid: [0, n] for sid, n in zip(sids, lengths)}
         for slot in slots:
             self._ran[slot] = False
         self._over = []
+        if self.resampler is not None:
+            samples, lengths = self.resampler.feed_rows(slots, samples, lengths)
+        self._feed_16k(sids, samples, lengths)
+        out = {}
+        for sid, slot in zip(sids, slots):
+            out[sid] = self._partial[slot] if self._ran[slot] else None
+            if self.mode == "rnnt_greedy_search":
+                self._partial[slot] = None
+        self._raise_over()
+        return out
+
+    def _feed_16k(self, sids: List[int], samples: torch.Tensor, lengths: List[int]):
+        """Rows of 16 kHz samples into the fbank, cut against the rings, and every window they complete."""
+        row_of = {sid: i for i, sid in enumerate(sids)}
+        left = {sid: [0, n] for sid, n in zip(sids, lengths)}
         while any(ol[1] > 0 for ol in left.values()):
             pieces = self.sched.cut(left)
             if not pieces:
@@ -319,13 +346,6 @@ class StreamPool:
             for (sid, slot, _, n, c, first), f in zip(pieces, got):
                 assert (f, self.fbank.frames_emitted[slot]) == (_frames(c, n)[0], self.sched.slots[slot].frames)
             self._run_rounds()
-        out = {}
-        for sid, slot in zip(sids, slots):
-            out[sid] = self._partial[slot] if self._ran[slot] else None
-            if self.mode == "rnnt_greedy_search":
-                self._partial[slot] = None
-        self._raise_over()
-        return out
 
     @torch.no_grad()
     def close(self, sids):
@@ -335,6 +355,11 @@ class StreamPool:
         if len(set(sids)) != len(sids):
             raise ValueError("StreamPool.close: a stream may be named once")
         self._over = []
+        if self.resampler is not None:      # the outputs that were waiting for samples behind the last one
+            live = [(sid, slot) for sid, slot in zip(sids, slots) if not self.sched.slots[slot].closing]
+            if live:
+                tail, counts = self.resampler.feed_rows([slot for _, slot in live], None, None, final=True)
+                self._feed_16k([sid for sid, _ in live], tail, counts)
         self.sched.close(sids)
         self._run_rounds()                  # (only the closing streams have windows left)
         results = self.decoder.results()
