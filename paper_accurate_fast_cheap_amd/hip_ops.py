@@ -107,10 +107,25 @@ def train_kernels_enabled() -> bool:
     return os.environ.get("PAFC_TRAIN_KERNELS", "1") != "0"
 
 
+def _conv_rows_ld(x: torch.Tensor, who: str) -> int:
+    """Row stride (elements) of a convolution input x (B, T, C'): contiguous, or a column slice of a wider (B, T, W) buffer --
+    unit channel stride, frames x.stride(1) apart, sequences T frames apart, a channel pair aligned."""
+    if not x.is_cuda:
+        raise _lib.PafcError("this op runs on the MI355X only (tensor is on %s); there is no CPU fallback" % x.device)
+    if x.is_contiguous():
+        return x.shape[-1]
+    if x.dim() != 3 or x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1) or x.stride(1) < x.shape[2] or x.stride(1) % 2 \
+            or x.data_ptr() % (2 * x.element_size()):
+        raise _lib.PafcError(f"{who}: x (B, T, C) with unit channel stride, rows of one even stride, an aligned channel pair")
+    return x.stride(1)
+
+
 def depthwise_conv1d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], left_pad: int,
                         out_len: int, glu: bool = False, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Channels-last depthwise conv1d: x (B, T, C) [or (B, T, 2C) with glu], weight (C, 1, K) -> (B, out_len, C)."""
-    _lib.require_gpu(x, weight, bias, lens)
+    """Channels-last depthwise conv1d: x (B, T, C) [or (B, T, 2C) with glu], weight (C, 1, K) -> (B, out_len, C).  x may be a
+    column slice of a wider buffer (_conv_rows_ld); any other layout is refused."""
+    _lib.require_gpu(weight, bias, lens)
+    ldx = _conv_rows_ld(x, "depthwise_conv1d_cl")
     B, T, Cx = x.shape
     C = Cx // 2 if glu else Cx
     K = weight.shape[-1]
@@ -119,9 +134,9 @@ def depthwise_conv1d_cl(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     if lens is not None and lens.dtype != torch.int32:
         raise _lib.PafcError("lens must be int32")
     y = torch.empty(B, out_len, C, dtype=x.dtype, device=x.device)
-    rc = _lib.lib().pafc_dwconv1d_cl(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x),
-                                     _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), int(glu), _lib.ptr(lens),
-                                     _lib.stream_of(x))
+    rc = _lib.lib().pafc_dwconv1d_cl_ex(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x), ldx,
+                                        _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), int(glu), _lib.ptr(lens),
+                                        _lib.stream_of(x))
     _lib.check(rc, "pafc_dwconv1d_cl")
     return y
 
@@ -136,19 +151,18 @@ def depthwise_conv1d_cl_ln_silu(x: torch.Tensor, weight: torch.Tensor, bias: Opt
                                 gamma: torch.Tensor, beta: torch.Tensor, eps: float, lens: Optional[torch.Tensor] = None):
     """SiLU(LayerNorm(depthwise_conv1d_cl(x, ...))) in one pass (convolution.py:131-138 with cnn_module_norm: layer_norm): the
     convolution's epilogue normalises its own rows.  x (B, T, 512) bf16, weight (512, 1, K), K in {15, 31}."""
-    _lib.require_gpu(x, weight, bias, gamma, beta, lens)
+    _lib.require_gpu(weight, bias, gamma, beta, lens)
+    ldx = _conv_rows_ld(x, "depthwise_conv1d_cl_ln_silu")
     B, T, C = x.shape
     K = weight.shape[-1]
     if not dwconv_ln_silu_ok(x, weight) or weight.shape != (C, 1, K) or any(
             t is not None and (t.dtype != x.dtype or not t.is_contiguous()) for t in (weight, bias, gamma, beta)):
         raise _lib.PafcError("depthwise_conv1d_cl_ln_silu: bf16, C = 512, K in (15, 31), contiguous parameters in the activation dtype")
-    if x.stride(2) != 1 or x.stride(0) != T * x.stride(1):
-        raise _lib.PafcError("depthwise_conv1d_cl_ln_silu: x (B, T, C) with unit channel stride")
     if lens is not None and lens.dtype != torch.int32:
         raise _lib.PafcError("lens must be int32")
     L = _lib.lib()
     y = torch.empty(B, out_len, C, dtype=x.dtype, device=x.device)
-    rc = L.pafc_dwconv1d_cl_ln_silu(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x), x.stride(1), _lib.ptr(weight),
+    rc = L.pafc_dwconv1d_cl_ln_silu(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, out_len, _lib.ptr(x), ldx, _lib.ptr(weight),
                                     _lib.ptr(bias), _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(y), _lib.ptr(lens),
                                     _lib.stream_of(x))
     _lib.check(rc, "pafc_dwconv1d_cl_ln_silu")
@@ -157,17 +171,17 @@ def depthwise_conv1d_cl_ln_silu(x: torch.Tensor, weight: torch.Tensor, bias: Opt
 
 def depthwise_conv1d_cl_wgrad(x: torch.Tensor, dy: torch.Tensor, K: int, left_pad: int, want_bias: bool = True):
     """(dw (C, 1, K), dbias (C) or None) in float32 for y = depthwise_conv1d_cl(x, w, bias, left_pad, dy.shape[1])."""
-    _lib.require_gpu(x, dy)
+    _lib.require_gpu(dy)
+    ldx = _conv_rows_ld(x, "depthwise_conv1d_cl_wgrad")
     B, T, C = x.shape
-    if dy.shape[0] != B or dy.shape[2] != C or dy.dtype != x.dtype or not dy.is_contiguous() or x.stride(2) != 1 \
-            or x.stride(0) != T * x.stride(1):
-        raise _lib.PafcError("dy must be contiguous (B, T_out, C) in x's dtype; x (B, T, C) with unit channel stride")
+    if dy.shape[0] != B or dy.shape[2] != C or dy.dtype != x.dtype:
+        raise _lib.PafcError("dy must be contiguous (B, T_out, C) in x's dtype")
     L = _lib.lib()
     nbytes = L.pafc_dwconv1d_cl_wgrad_workspace_bytes(B, dy.shape[1], C, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     dw = torch.empty(C, 1, K, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device) if want_bias else None
-    rc = L.pafc_dwconv1d_cl_wgrad(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, dy.shape[1], _lib.ptr(x), x.stride(1),
+    rc = L.pafc_dwconv1d_cl_wgrad(_lib.dtype_code(x.dtype), B, T, C, K, left_pad, dy.shape[1], _lib.ptr(x), ldx,
                                   _lib.ptr(dy), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), nbytes, _lib.stream_of(x))
     _lib.check(rc, "pafc_dwconv1d_cl_wgrad")
     return dw, db
