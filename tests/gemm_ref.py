@@ -40,7 +40,8 @@ U32 = 2.0 ** -24
 _U_OUT = {"f32": 2.0 ** -24, "planes": 2.0 ** -16, "bf16": 2.0 ** -8}
 _LIP = {"none": 1.0, "relu": 1.0, "tanh": 1.0, "silu": 1.1, "glu": 1.0}
 
-# every instantiation pafc_gemm_ph_ex2 can launch (the CONV and folded-LayerNorm ones have their own entry points)
+# every instantiation pafc_gemm_ph_ex2 can launch.  (The CONV ones have their own entry points and their own battery on this
+# reference: tests/conv_ref.py, tests/test_conv_sub_f64_gpu.py; the folded-LayerNorm ones have their own entry points too.)
 SHARED_FRAGMENT_FORMS = {
     "split-f32": Form(True, "f32", "none", None),
     "split-f32-res": Form(True, "f32", "none", "f32"),

@@ -22,6 +22,9 @@ The kernel is called through the bound library (pafc_gemm_ph_ex2), so that batch
     <1, 0, 0, 0>, <0, 0, 1, 0>                  bf16-glu, bf16-res                        test_plain_bf16_forms
     <0, 0, 0, 1>, <1, 0, 0, 1>, <0, 0, 2, 1>    f32, f32-glu, f32-res                     test_plain_bf16_forms
     <0, 0, 0, 2>, <0, 1, 0, 2>                  planes, planes-silu                       test_plain_bf16_forms
+  CONV = true (conv_ph_launch: the second subsampling convolution)
+    <0, 0 / 3, 0, 0, CONV>                      bf16, bf16-relu         tests/test_conv_sub_f64_gpu.py: test_conv2_bf16_ph
+    <0, 0 / 3, 0, 2, CONV, 0, SPL>              split-planes (+ ReLU)   tests/test_conv_sub_f64_gpu.py: test_conv2_split_ph
 
 Each such case walks M in {1, tile_m - 1, tile_m, tile_m + 1, 2 tile_m + 7} at one (N, K) and every (N, K) of
 {8, 264, 512, 1000} x {128, 384, 1024} (GLU: {256, 768}) at M = 2 tile_m + 7.  Row strides, lo_off and sentinels:
