@@ -139,7 +139,9 @@ int pafc_layernorm_silu_bwd(int dtype_x, int dtype_g, long rows, int C, const vo
  * LayerNorm in front of the projection, folded (as pafc_gemm_bf16_ph_ln): ln_stats_in = float2 [M][ln_parts_in] partial
  * (sum, sum of squares) of the UN-normalised A rows, ln_csum[N] = column sums of W' = bf16(gamma * W), bias = b + W beta;
  * out = act(rstd (A W'^T - mean csum) + bias).  ln_stats_out (or null) receives float2 [batch][M][N_out / 16] partial
- * statistics of the rows written (as stored, after rounding) for the next folded LayerNorm. */
+ * statistics of the rows written (as stored, after rounding) for the next folded LayerNorm.  A folded LayerNorm (ln_stats_in
+ * or, in the _ex form, ln_self) takes batch == 1 only -- the statistics and ln_csum have no batch stride -- and any other
+ * batch returns PAFC_ERR_BAD_DIMS. */
 int pafc_gemm_skinny_bf16(long M, int N, int K, int batch, const void *A, long lda, long strideA, const void *W, long ldw,
                           long strideW, const void *bias, long strideBias, const void *residual, long ldr, long strideR,
                           void *out, long ldo, long strideO, float alpha, int act, const float *ln_stats_in, int ln_parts_in,

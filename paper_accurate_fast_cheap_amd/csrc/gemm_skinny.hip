@@ -385,6 +385,8 @@ extern "C" int pafc_gemm_skinny_bf16_ex(long M, int N, int K, int batch, const v
     if (glu && residual) return PAFC_ERR_UNSUPPORTED;
     const bool folded = ln_stats_in != nullptr || ln_self != 0;
     if (folded != (ln_csum != nullptr) || (ln_stats_in && (ln_parts_in <= 0 || ln_self))) return PAFC_ERR_BAD_DIMS;
+    // ln_stats_in and ln_csum are indexed by row and column alone: entries 1.. of a batch would be normalised with entry 0's
+    if (folded && batch != 1) return PAFC_ERR_BAD_DIMS;
     if (mix_maa && (mix_T <= 0 || M % mix_T != 0 || batch != 1 || glu)) return PAFC_ERR_BAD_DIMS;
     if (!mix_maa && mix_prev) return PAFC_ERR_BAD_DIMS;
     if ((norm_gamma != nullptr) != (norm_beta != nullptr) || (norm_gamma && (mix_maa || folded || glu || batch != 1)))

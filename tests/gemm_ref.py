@@ -1,5 +1,6 @@
-"""float64 reference of the fused-epilogue GEMMs (csrc/gemm_ph.hip, csrc/gemm_bf16.hip) and a derived per-element error
-bound.  Plain torch, CPU or GPU, no kernels of this package.
+"""float64 reference of the fused-epilogue GEMMs (csrc/gemm_ph.hip, csrc/gemm_bf16.hip, csrc/gemm_f32.hip) and of the
+weight-gradient GEMM (csrc/gemm_tn.hip), and a derived per-element error bound.  Plain torch, CPU or GPU, no kernels of
+this package.
 
 `ideal(form, operands)` is the float64 value of what a kernel is specified to compute from the operands AS IT RECEIVES
 THEM (the bf16 values, the planes of a split operand), so it depends on torch alone:
@@ -8,6 +9,7 @@ THEM (the bf16 values, the planes of a split operand), so it depends on torch al
          = hi W0^T + lo W1^T + hi W2^T             split operands: A = [hi | lo], W = [W0 | W1 | W2] = [hi_w | hi_w | lo_w]
     pre  = alpha P + bias
     out  = act(pre) + residual                     the activation BEFORE the residual
+         = act(pre + residual)                     operands["act_after_residual"]: csrc/gemm_f32.hip (pafc_gemm_f32)
     GLU:   out[t h + c] = pre[2h t + c] * sigmoid(pre[2h t + h + c]),  h = 32 (operands["glu_half"])
 
 `bound(form, operands)` is what a correct kernel may differ from `ideal` by, per element.  With u = 2^-24:
@@ -23,6 +25,14 @@ THEM (the bf16 values, the planes of a split operand), so it depends on torch al
                                 float64 over the case's own pre-activation values (4 x: fast exponentials and reciprocals).
                                 A measured number of torch's, not of the kernel; tests write it to the parity log.
     bound = E + out + act
+
+With operands["act_after_residual"] E is the same L c (S + |residual|) and the activation term is measured over pre + residual.
+
+The accumulation constant c (E = L c S, c = (Kw + 8) u above) counts the roundings on the longest path to one output element:
+    bf16 operands     (Kw + 8) u       a product of two bf16 values is an fp32 number: one rounding per column added
+    fp32 operands     (2 Kw + 8) u     operands["f32_operands"]: the product of two fp32 values rounds before it is added
+    operands["roundings"] = n          c = n u, counted by whoever builds the operands: tn_problem() below does, for the
+                                       weight-gradient GEMM (csrc/gemm_tn.hip), whose walk is not one K loop
 
 The bf16 term is 2^-8 |x|, not 2^-9 |x|: half a bf16 step is 2^(e - 8) for |x| in [2^e, 2^(e + 1)), which is 2^-8 |x| at the
 bottom of the binade (x = 1 + 2^-8 rounds to 1 or 1 + 2^-7, either way 2^-8 off).  tests/test_gemm_ref.py shows that a
@@ -190,15 +200,26 @@ def _act(form: Form, pre: torch.Tensor, half: int) -> torch.Tensor:
 
 
 def pre_activation(form: Form, ops: dict) -> torch.Tensor:
+    """What the activation is applied to: alpha P + bias, and the residual too with operands["act_after_residual"]."""
     P, _, _ = products(form, ops)
-    return float(ops.get("alpha", 1.0)) * P + _row_vec(ops.get("bias"))
+    pre = float(ops.get("alpha", 1.0)) * P + _row_vec(ops.get("bias"))
+    if ops.get("act_after_residual") and ops.get("residual") is not None:
+        pre = pre + ops["residual"].double()
+    return pre
 
 
 def ideal(form: Form, ops: dict) -> torch.Tensor:
     out = _act(form, pre_activation(form, ops), ops.get("glu_half", 32))
-    if ops.get("residual") is not None:
+    if ops.get("residual") is not None and not ops.get("act_after_residual"):
         out = out + ops["residual"].double()
     return out
+
+
+def accumulation_constant(ops: dict, Kw: int) -> float:
+    """c of the module docstring: the roundings on the longest path to one element, times u."""
+    if ops.get("roundings") is not None:
+        return float(ops["roundings"]) * U32
+    return ((2 if ops.get("f32_operands") else 1) * Kw + 8) * U32
 
 
 def activation_term(form: Form, ops: dict) -> float:
@@ -216,7 +237,7 @@ def bound(form: Form, ops: dict, act_term: float = None) -> torch.Tensor:
     if ops.get("bias") is not None:
         S = S + _row_vec(ops["bias"]).abs()
     res = ops["residual"].double().abs() if ops.get("residual") is not None else 0.0
-    c = (Kw + 8) * U32
+    c = accumulation_constant(ops, Kw)
     if form.act == "glu":
         half = ops.get("glu_half", 32)
         Ea, Eb = _glu_parts(c * S, half)
@@ -241,9 +262,11 @@ def round_to(form: Form, x: torch.Tensor) -> torch.Tensor:
 
 
 def make_operands(form: Form, M: int, N: int, K: int, seed: int, batch: int = 0, alpha: float = 1.0, plane_block: int = 0,
-                  shared_bias: bool = False, device="cpu") -> dict:
+                  shared_bias: bool = False, device="cpu", f32_operands: bool = False) -> dict:
     """Seeded operands as the kernel receives them: randn A, W scaled by K^-0.5, bias by 0.3, residual by 1; bias and
-    residual in the types the form takes.  batch > 0 adds a leading batch dimension.  GLU: N counts the weight rows."""
+    residual in the types the form takes.  batch > 0 adds a leading batch dimension.  GLU: N counts the weight rows.
+    f32_operands (plain forms): A and W stay fp32, and the bound counts a rounding per product."""
+    assert not (f32_operands and form.a_split)
     g = torch.Generator().manual_seed(seed)
     lead = (batch,) if batch else ()
     rnd = lambda *s: torch.randn(lead + s, generator=g)
@@ -251,9 +274,9 @@ def make_operands(form: Form, M: int, N: int, K: int, seed: int, batch: int = 0,
     b = (torch.randn((N,), generator=g) if shared_bias else rnd(N)) * 0.3
     No = N // 2 if form.act == "glu" else N
     r = rnd(M, No)
-    ops = {"alpha": alpha, "plane_block": plane_block}
-    ops["A"] = split_a(a, plane_block) if form.a_split else a.bfloat16()
-    ops["W"] = split_w(w) if form.a_split else w.bfloat16()
+    ops = {"alpha": alpha, "plane_block": plane_block, "f32_operands": f32_operands}
+    ops["A"] = split_a(a, plane_block) if form.a_split else (a if f32_operands else a.bfloat16())
+    ops["W"] = split_w(w) if form.a_split else (w if f32_operands else w.bfloat16())
     ops["bias"] = b.bfloat16() if form.out == "bf16" else b
     ops["residual"] = None if form.res is None else (r.bfloat16() if form.res == "bf16" else r)
     ops["a32"], ops["w32"] = a, w                # the fp32 operands the planes were split from
@@ -261,7 +284,8 @@ def make_operands(form: Form, M: int, N: int, K: int, seed: int, batch: int = 0,
 
 
 def make_grid_operands(form: Form, M: int, N: int, K: int, seed: int, plane_block: int = 0, alpha: float = 1.0,
-                       glu_half: int = 32, device="cpu") -> dict:
+                       glu_half: int = 32, device="cpu", f32_operands: bool = False, batch: int = 0,
+                       shared_bias: bool = False) -> dict:
     """Operands on a grid, for which fp32 accumulation is EXACT in any order and in any number of K shares: the hi plane of
     A (or a plain A) and the weights are integers in [-3, 3]; the lo plane of A, lo_w, the bias and the residual are integers
     times 2^-6 (in [-3, 3] 2^-6 and [-31, 31] 2^-6).  A kernel multiplies the planes it is given: they need not be the
@@ -271,25 +295,30 @@ def make_grid_operands(form: Form, M: int, N: int, K: int, seed: int, plane_bloc
         max(|A| |W|^T + |bias| + |residual|) 2^7 < 2^24
 
     so `round_to(form, ideal(form, ops))` is what a correct kernel gives BIT FOR BIT for act "none", and a K-step that is
-    dropped, walked twice or taken from the wrong plane changes nearly every element (tests/test_gemm_ref.py)."""
+    dropped, walked twice or taken from the wrong plane changes nearly every element (tests/test_gemm_ref.py).
+    f32_operands: the same integers as fp32 A and W (plain forms).  batch > 0 adds a leading batch dimension (the bias per
+    entry, or one for all with shared_bias)."""
     assert alpha in (1.0, 0.5), alpha
+    assert not (f32_operands and form.a_split)
     g = torch.Generator().manual_seed(seed)
-    ints = lambda lim, *s: torch.randint(-lim, lim + 1, s, generator=g).float()
+    lead = (batch,) if batch else ()
+    ints = lambda lim, *s: torch.randint(-lim, lim + 1, lead + s, generator=g).float()
     No = N // 2 if form.act == "glu" else N
-    ops = {"alpha": alpha, "plane_block": plane_block, "glu_half": glu_half}
+    ops = {"alpha": alpha, "plane_block": plane_block, "glu_half": glu_half, "f32_operands": f32_operands}
     if form.a_split:
         hi, lo = ints(3, M, K), ints(3, M, K) * 2.0 ** -6
         if plane_block:
-            sh = (M, K // plane_block, plane_block)
-            A = torch.cat([hi.reshape(sh), lo.reshape(sh)], dim=-1).reshape(M, 2 * K)
+            sh = lead + (M, K // plane_block, plane_block)
+            A = torch.cat([hi.reshape(sh), lo.reshape(sh)], dim=-1).reshape(lead + (M, 2 * K))
         else:
             A = torch.cat([hi, lo], dim=-1)
         hi_w = ints(3, N, K)
         W = torch.cat([hi_w, hi_w, ints(3, N, K) * 2.0 ** -6], dim=-1)
     else:
         A, W = ints(3, M, K), ints(3, N, K)
-    b, r = ints(31, N) * 2.0 ** -6, ints(31, M, No) * 2.0 ** -6
-    ops["A"], ops["W"] = A.bfloat16(), W.bfloat16()
+    b = (torch.randint(-31, 32, (N,), generator=g).float() if shared_bias else ints(31, N)) * 2.0 ** -6
+    r = ints(31, M, No) * 2.0 ** -6
+    ops["A"], ops["W"] = (A, W) if f32_operands else (A.bfloat16(), W.bfloat16())
     assert torch.equal(ops["A"].float(), A) and torch.equal(ops["W"].float(), W)
     ops["bias"] = b.bfloat16() if form.out == "bf16" else b
     ops["residual"] = None if form.res is None else (r.bfloat16() if form.res == "bf16" else r)
@@ -302,7 +331,48 @@ def grid_bits(form: Form, ops: dict) -> float:
     """log2 of max(|A| |W|^T + |bias| + |residual|) 2^7: the significand bits the grid operands' sums need (< 24: exact)."""
     import math
     _, Sp, _ = products(form, ops)
-    S = Sp + _row_vec(ops.get("bias")).abs()
+    S = Sp if ops.get("bias") is None else Sp + _row_vec(ops["bias"]).abs()
     if ops.get("residual") is not None and form.act != "glu":
         S = S + ops["residual"].double().abs()
     return math.log2(float(S.max()) * 2.0 ** 7)
+
+
+# ---- the transposed product of the training step: dW = dY^T X, dbias = column sums of dY (csrc/gemm_tn.hip) ---------------
+def make_tn_operands(R: int, M: int, N: int, seed: int, batch: int = 0, grid: bool = False, device="cpu"):
+    """(dy (.., R, M), x (.., R, N)) bf16: randn, or integers in [-3, 3] (`grid`: every sum is an fp32 number far beyond the R
+    of the tests -- 9 R < 2^24 -- in any order, in any number of splits)."""
+    g = torch.Generator().manual_seed(seed)
+    lead = (batch,) if batch else ()
+    if grid:
+        dy, x = (torch.randint(-3, 4, lead + (R, n), generator=g).float() for n in (M, N))
+    else:
+        dy, x = (torch.randn(lead + (R, n), generator=g) for n in (M, N))
+    return dy.bfloat16().to(device), x.bfloat16().to(device)
+
+
+def tn_plan(R: int, s: int):
+    """The documented plan arithmetic for a split count s: rows per split in whole 64-row K-steps, and the S that leaves no
+    split empty.  -> (S, rows per split)"""
+    rps = -(-(-(-R // s)) // 64) * 64
+    return -(-R // rps), rps
+
+
+def tn_problem(dy: torch.Tensor, x: torch.Tensor, out: str, S: int, rps: int):
+    """dW = dY^T X as the plain form Form(False, out, "none", None) with A = dY^T, W = X^T, Kw = R, and the bias gradient as
+    the same form against a column of ones.  -> (form, operands of dW, operands of dbias (.., M, 1))
+
+    roundings = min(rps, R) + 1 + S + 1, the sum over the longest path to one element of dW:
+        min(rps, R)   a K group of a block adds the rows of its split in fp32, one rounding per row -- the products of two
+                      bf16 values are exact (each group walks half of the rows of every K-step; the count stays with the
+                      whole split, an upper bound)
+        + 1           where the two K groups' sums meet, in the block's epilogue
+        + S           the reducing kernel adds the S partials (the quarter sums and their two final additions included)
+        + 1           the fp32 value the output is written from (the `out` term of bound() then rounds it to the output type)."""
+    form = Form(False, out, "none", None)
+    R = dy.shape[-2]
+    n = min(rps, R) + 1 + S + 1
+    A = dy.transpose(-1, -2)
+    dw = {"A": A, "W": x.transpose(-1, -2), "bias": None, "residual": None, "alpha": 1.0, "roundings": n}
+    ones = torch.ones((1, R), dtype=dy.dtype, device=dy.device)
+    db = {"A": A, "W": ones, "bias": None, "residual": None, "alpha": 1.0, "roundings": n}
+    return form, dw, db

@@ -104,6 +104,16 @@ def test_argument_validation_returns_error_codes_without_a_gpu(so_path):
     assert L.pafc_gemm_f32(8, 8, 6, 1, one, 8, 0, one, 8, 0, NULL, 0, NULL, 0, 0, one, 8, 0, 1.0, 0, NULL) == -7    # K % 4
     assert L.pafc_gemm_f32(8, 8, 8, 1, P(8), 8, 0, one, 8, 0, NULL, 0, NULL, 0, 0, one, 8, 0, 1.0, 0, NULL) == -8   # alignment
     assert L.pafc_gemm_f32(8, 8, 8, 1, one, 8, 0, one, 8, 0, NULL, 0, NULL, 0, 0, one, 8, 0, 1.0, 4, NULL) == -7    # no GLU here
+    # the skinny GEMM: a folded LayerNorm has no batch stride for its statistics, so batch > 1 with one is refused
+    L.pafc_gemm_skinny_bf16_ex.argtypes = [G, I, I, I, P, G, G, P, G, G, P, G, P, G, G, P, G, G, F, I, I, P, I, I, P, F, P, P, P, I,
+                                           P, P, F, P]
+    sk = lambda batch, stats, parts, ln_self, csum: L.pafc_gemm_skinny_bf16_ex(
+        16, 16, 32, batch, one, 32, 512, one, 32, 0, NULL, 0, NULL, 0, 0, one, 16, 256, 1.0, 0, 0, stats, parts, ln_self, csum, 1e-5,
+        NULL, NULL, NULL, 0, NULL, NULL, 0.0, NULL)
+    assert sk(2, one, 1, 0, one) == ERR_DIMS            # ln_stats_in, batched
+    assert sk(2, NULL, 0, 1, one) == ERR_DIMS           # ln_self, batched
+    assert sk(1, one, 1, 1, one) == ERR_DIMS            # (both at once: refused before, as now)
+    assert sk(0, NULL, 0, 0, NULL) == ERR_DIMS
     # the CTC loss kernels: workspace query and argument checks
     Z = ctypes.c_size_t
     L.pafc_ctc_loss_workspace_bytes.restype = Z

@@ -235,3 +235,174 @@ def test_every_grid_shape_of_the_small_tile_tests_is_exact():
         form = T.form_of(name)
         ops = gemm_ref.make_grid_operands(form, M, N, K, seed=1, plane_block=pb, alpha=alpha)
         assert gemm_ref.grid_bits(form, ops) < 23.0, (name, M, N, K)
+
+
+# ---- fp32 operands and the activation after the residual (csrc/gemm_f32.hip; tests/test_gemm_f32_f64_gpu.py) ---------------
+F32_RES = Form(False, "f32", "none", "f32")
+
+
+def _f32_ops(K, act="none", n=263, seed=5):
+    form = Form(False, "f32", act, "f32")
+    ops = gemm_ref.make_operands(form, n, n, K, seed, alpha=0.5, f32_operands=True)
+    ops["act_after_residual"] = True
+    return form, ops
+
+
+def _ratio(got, form, ops):
+    return float(((got - gemm_ref.ideal(form, ops)).abs() / gemm_ref.bound(form, ops)).max())
+
+
+@pytest.mark.parametrize("K", [4, 36, 100, 384])
+def test_fp32_operand_constant_holds_float32_torch_and_sees_a_wrong_kernel(K):
+    """c = (2 Kw + 8) u for fp32 operands, derived, not fitted: the same product in float32 torch stays below 0.15 of the
+    bound on 263 x 263 outputs, while a dropped last quad of K and a bias placed under alpha each put more than 99 % of the
+    elements outside it."""
+    form, ops = _f32_ops(K)
+    assert ops["A"].dtype == torch.float32 and ops["W"].dtype == torch.float32
+    assert gemm_ref.accumulation_constant(ops, K) == (2 * K + 8) * gemm_ref.U32
+    A, W, b, r = ops["A"], ops["W"], ops["bias"], ops["residual"]
+    f32 = (0.5 * (A @ W.t()) + b + r).double()
+    assert _ratio(f32, form, ops) < 0.15
+    P, _, _ = gemm_ref.products(form, ops)
+    Ad, Wd = A.double(), W.double()
+    dropped = 0.5 * (P - Ad[:, K - 4:] @ Wd[:, K - 4:].t()) + b.double() + r.double()
+    assert _outside(gemm_ref.round_to(form, dropped), form, ops) > 0.99
+    under = 0.5 * (P + b.double()) + r.double()
+    assert _outside(gemm_ref.round_to(form, under), form, ops) > 0.99
+
+
+@pytest.mark.parametrize("act", ["silu", "tanh", "relu"])
+def test_activation_after_the_residual_is_a_switch(act):
+    form, ops = _f32_ops(36, act, n=71)
+    P, _, _ = gemm_ref.products(form, ops)
+    lin = 0.5 * P + ops["bias"].double()
+    fn = {"silu": F.silu, "tanh": torch.tanh, "relu": torch.relu}[act]
+    torch.testing.assert_close(gemm_ref.ideal(form, ops), fn(lin + ops["residual"].double()), rtol=1e-12, atol=1e-12)
+    before = dict(ops, act_after_residual=False)
+    torch.testing.assert_close(gemm_ref.ideal(form, before), fn(lin) + ops["residual"].double(), rtol=1e-12, atol=1e-12)
+    assert bool(torch.isfinite(gemm_ref.bound(form, ops)).all())
+    assert _outside(gemm_ref.round_to(form, gemm_ref.ideal(form, ops)), form, ops) == 0.0
+
+
+def test_grid_operands_as_fp32_are_the_same_integers_and_batches_stack():
+    form = F32_RES
+    bf = gemm_ref.make_grid_operands(form, 70, 264, 128, seed=3, alpha=0.5)
+    f32 = gemm_ref.make_grid_operands(form, 70, 264, 128, seed=3, alpha=0.5, f32_operands=True)
+    assert f32["A"].dtype == torch.float32 and torch.equal(f32["A"], bf["A"].float()) and torch.equal(f32["W"], bf["W"].float())
+    assert torch.equal(f32["bias"], bf["bias"]) and torch.equal(f32["residual"], bf["residual"])
+    ops = gemm_ref.make_grid_operands(form, 33, 40, 100, seed=4, alpha=0.5, f32_operands=True, batch=3, shared_bias=True)
+    assert ops["A"].shape == (3, 33, 100) and ops["bias"].shape == (40,)
+    want = gemm_ref.ideal(form, ops)
+    one = {k: (v[2] if isinstance(v, torch.Tensor) and v.dim() == 3 else v) for k, v in ops.items() if k != "_prod"}
+    assert torch.equal(gemm_ref.ideal(form, one), want[2])
+    big = gemm_ref.make_grid_operands(form, 263, 263, 1028, seed=1, alpha=0.5, f32_operands=True)
+    assert gemm_ref.grid_bits(form, big) < 20.0
+
+
+def _cached_f32_problem():
+    from tests import test_gemm_f32_f64_gpu as T
+    import functools
+
+    @functools.lru_cache(maxsize=None)
+    def get(M, N, K, grid, batch):
+        return T.make_ops("none", M, N, K, grid, batch, False, "cpu")
+    return T, get
+
+
+def _drop_last_quad(ops):
+    P, Sp, Kw = ops["_prod"]
+    A, W = ops["A"].double(), ops["W"].double()
+    return dict(ops, _prod=(P - A[..., Kw - 4:] @ W[..., Kw - 4:].transpose(-1, -2), Sp, Kw))
+
+
+def test_planted_faults_fail_the_random_cases_of_the_fp32_gemm_tests():
+    """The random case list of tests/test_gemm_f32_f64_gpu.py, with two wrong kernels written as mutated results: the
+    activation applied before the residual, and one K quad dropped.  In every family (tile edge x activation) each fault it
+    applies to puts more than half of the elements of at least one case outside the bound; a correctly rounded result none."""
+    T, get = _cached_f32_problem()
+    quad, order = {}, {}
+    for act, M, N, K, batch, bias, res in T.random_problems():
+        form = Form(False, "f32", act, "f32" if res else None)
+        ops = T.variant(get(M, N, K, False, batch), bias, res)
+        assert _outside(gemm_ref.round_to(form, gemm_ref.ideal(form, ops)), form, ops) == 0.0
+        fam = (M, act)
+        got = gemm_ref.round_to(form, gemm_ref.ideal(form, _drop_last_quad(ops)))
+        quad[fam] = max(quad.get(fam, 0.0), _outside(got, form, ops))
+        if res and act != "none":
+            got = gemm_ref.round_to(form, gemm_ref.ideal(form, dict(ops, act_after_residual=False)))
+            order[fam] = max(order.get(fam, 0.0), _outside(got, form, ops))
+    assert len(quad) == 12 and len(order) == 9
+    assert min(quad.values()) > 0.5, quad
+    assert min(order.values()) > 0.5, order
+
+
+def test_planted_faults_change_the_grid_cases_of_the_fp32_gemm_tests():
+    """The grid case list of tests/test_gemm_f32_f64_gpu.py: the generator's precondition holds with bits to spare, fp32
+    accumulation gives the float64 value bit for bit, and a dropped K quad changes more than half of the elements of EVERY
+    problem."""
+    T, get = _cached_f32_problem()
+    rows = {}
+    for M, N, K, batch, alpha in T.grid_problems(cus=256):
+        assert alpha in (0.5, 1.0)
+        rows[(N, K, batch)] = max(M, rows.get((N, K, batch), 0))
+    assert len(rows) >= 60
+    for (N, K, batch), M in rows.items():
+        batch = min(batch, 8)                    # (the plan's batches of one small tile per CU: eight entries of them)
+        ops = get(M, N, K, True, batch)
+        form = F32_RES
+        assert gemm_ref.grid_bits(form, ops) < 20.0, (M, N, K)
+        want = gemm_ref.ideal(form, ops)
+        f32 = torch.baddbmm(ops["residual"], ops["A"], ops["W"].transpose(-1, -2), alpha=0.5) if batch else \
+            torch.addmm(ops["residual"], ops["A"], ops["W"].t(), alpha=0.5)
+        f32 = f32 + (ops["bias"].unsqueeze(-2) if batch else ops["bias"])
+        assert torch.equal(f32.double(), want) and torch.equal(gemm_ref.round_to(form, want), want)
+        assert float((gemm_ref.ideal(form, _drop_last_quad(ops)) != want).double().mean()) > 0.5, (M, N, K)
+
+
+# ---- the transposed product (csrc/gemm_tn.hip; tests/test_gemm_tn_f64_gpu.py) --------------------------------------------
+def test_tn_plan_arithmetic_and_rounding_count():
+    assert [gemm_ref.tn_plan(577, s) for s in range(1, 6)] == [(1, 640), (2, 320), (3, 256), (4, 192), (5, 128)]
+    assert gemm_ref.tn_plan(129, 2) == (2, 128) and gemm_ref.tn_plan(1, 1) == (1, 64) and gemm_ref.tn_plan(300, 2) == (2, 192)
+    dy, x = gemm_ref.make_tn_operands(300, 136, 72, seed=1)
+    form, ops_w, ops_b = gemm_ref.tn_problem(dy, x, "f32", 2, 192)
+    assert form == Form(False, "f32", "none", None) and ops_w["roundings"] == 192 + 1 + 2 + 1
+    assert gemm_ref.accumulation_constant(ops_w, 300) == 196 * gemm_ref.U32
+    torch.testing.assert_close(gemm_ref.ideal(form, ops_w), dy.double().t() @ x.double(), rtol=1e-13, atol=1e-13)
+    torch.testing.assert_close(gemm_ref.ideal(form, ops_b)[:, 0], dy.double().sum(0), rtol=1e-13, atol=1e-13)
+    assert gemm_ref.products(form, ops_w)[2] == 300
+
+
+def test_planted_faults_fail_the_cases_of_the_tn_tests():
+    """The case list of tests/test_gemm_tn_f64_gpu.py with two wrong kernels: the last row of R left out of dW, and the bias
+    gradient taken over one row too few.  Random operands: each puts more than half of the elements of at least one case
+    outside the bound, for both output types (and float32 torch, split as the plan splits, stays inside it).  Grid
+    operands: each changes more than half of the elements of at least one case of every family, and a correctly rounded
+    result is what round_to gives back."""
+    from tests import test_gemm_tn_f64_gpu as T
+    fams = {"ring": T.cases_ring_fills(), "splits": T.cases_splits(), "columns": T.cases_column_walk(),
+            "renumbering": T.cases_renumbering(), "batched": T.cases_batched(), "random": T.cases_random()}
+    assert sum(len(v) for v in fams.values()) == len(T.all_cases())
+    for fam, cases in fams.items():
+        worst = {}
+        for case in cases:
+            dy, x = T.make(case, "cpu")
+            S, rps = T.expected_S(case)
+            for out in ("f32", "bf16"):
+                form, ops_w, ops_b = gemm_ref.tn_problem(dy, x, out, S, rps)
+                _, short_w, short_b = gemm_ref.tn_problem(dy[..., :-1, :], x[..., :-1, :], out, S, rps)
+                for what, ops, short in (("dw", ops_w, short_w), ("dbias", ops_b, short_b)):
+                    want = gemm_ref.round_to(form, gemm_ref.ideal(form, ops))
+                    got = gemm_ref.round_to(form, gemm_ref.ideal(form, short))
+                    if case.grid:
+                        assert gemm_ref.grid_bits(form, ops) < 20.0
+                        if out == "f32":
+                            assert torch.equal(want, gemm_ref.ideal(form, ops))
+                        frac = float((got != want).double().mean())
+                    else:
+                        assert _outside(want, form, ops) == 0.0
+                        parts = [ops["A"][..., s * rps:(s + 1) * rps].float() @ ops["W"][..., s * rps:(s + 1) * rps].float().transpose(-1, -2)
+                                 for s in range(S)]
+                        assert _ratio(gemm_ref.round_to(form, sum(parts).double()), form, ops) <= 1.0
+                        frac = _outside(got, form, ops)
+                    worst[(what, out)] = max(worst.get((what, out), 0.0), frac)
+        assert len(worst) == 4 and min(worst.values()) > 0.5, (fam, worst)
